@@ -2,9 +2,23 @@
 optimizer.optimize(nIterations), reference Modules/Optimization/g2oBundleAdjustment.cc:959-962) at
 config C2 of BASELINE.json: 100k two-view correspondences.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--corr 100000] [--no-cpu-baseline]
-                  [--analytic] [--solver pcg|direct] [--sharded] [--cpu-full-iteration]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--corr 100000]
+                  [--analytic] [--solver pcg|direct] [--sharded]
+  python bench.py --full [--no-cpu-baseline] [--no-e2e] [--no-legs] [--cpu-full-iteration] ...
   python bench.py --workload ba [--ba-points 500000] [--ba-kfs 8] [--ba-scaling strong|weak] ...
+
+A plain run does what the headline figure needs and no more: build the scene, upload, W warm-up
+iterations, the K timed steps, the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step; the keys of the legs below are null).  --steps is the number of timed steps whatever the
+LM trajectory: if the LM stops early (g2o's Terminate) the state is reset and the remaining steps run
+as a fresh solve inside the timed region.  --dump-outputs DIR writes what the timed path left after
+its last step — the arrays a caller downloads (points, scales, pair transforms; BA: poses, points)
+and the chi2 history of the report — as DIR/<name>.npy in float64, at most 64 MB (over that, a fixed
+seeded sample of the rows, their indices in <name>_rows.npy).  The scene is seeded, so two runs with
+the same arguments solve the same problem.
+
+--full adds everything else described below: the profiled trial and its roofline, the CPU baseline,
+the end-to-end arapOptimization timing and the extra legs (each with its own --no-* switch).
 
 A "step" is one LM iteration of the device solver (linearize with g2o's numeric ARAP/depth
 Jacobians — the reference's arithmetic — assemble H, then up to 10 damped trials, each a step
@@ -23,14 +37,14 @@ north star's size) split the same way.  --weak: one problem of N x 100k correspo
 per-problem rate).  --solver direct runs the sharded multifrontal LDL^T instead.  The barrier and the
 max-over-ranks time use torch.distributed.
 
-Legs of the default C2 line (--no-legs skips them): `north_star_500k` (above, any N); at N > 1 `c4`:
+Legs of the C2 line under --full (--no-legs skips them): `north_star_500k` (above, any N); at N > 1 `c4`:
 BASELINE C4 (8 keyframes x 500k, all 28 pairs, 12M unknowns) point-sharded over the same ranks, 1 +
 min(steps, 3) LM iterations (strong scaling; the multi-pair graph's sharded chain); and, at N = 1,
 `regimes.realcolon`: the C2 scene under Realcolon.yaml's weights and camera (arap 0.1, sigma_d 1e-6 m,
 KB8 d0..d3; Data/Realcolon.yaml:15-23,101,110), a CG-heavy regime (the Simulation.yaml headline
 run is near-stalled: ~5 CG iterations per trial at lambda ~1e21).
 
-Printed roofline (the iterative plan, the default): the CG iteration's kernels — at C2 (one rank, one
+Printed roofline (--full; the iterative plan, the default): the CG iteration's kernels — at C2 (one rank, one
 pair: tile mode) k_sp_tile (the matrix-free product, every ARAP edge read once) + k_sp_tupd (the
 update); otherwise k_sp_phase1 + k_sp_phase2 (the product with the update folded in) — HBM-bound, from a profiled trial
 right after the timed region (HIP events on the solver's own stream, active launches only).  Two
@@ -44,7 +58,7 @@ committed rocprofv3 PMC pass when it matches the plan, with the calibrated FETCH
 A "step" is one LM iteration; with PCG steps each trial is setup + CG iterations (product, heavy
 rows, update) instead of scatter + factorization + substitution.
 
-CPU baseline: the oracle (oracle/deftri_oracle.c: the reference LM restated in scalar C, g2o
+CPU baseline (--full): the oracle (oracle/deftri_oracle.c: the reference LM restated in scalar C, g2o
 numeric Jacobians, SimplicialLDLT) on the SAME full-size C2 problem with the device plan's
 elimination order, 1 thread: one linearization and one trial are measured; the per-iteration
 figure is linearization + (GPU trials per iteration) x trial.  --cpu-full-iteration times a
@@ -228,28 +242,35 @@ def main_ba(args, world, rank, gpu, backend):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rep = ctx.solve_lm(args.steps)
+    rep, solves = timed_steps(ctx.solve_lm, lambda: ctx.set_state(poses=prob.poses, points=prob.points), args.steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if world > 1:
         dist.barrier()
-    log(f"[rank {rank}] BA {rep['iterations']} iterations / {rep['trials_total']} trials in {dt * 1e3:.1f} ms; "
+    log(f"[rank {rank}] BA {rep['iterations']} iterations / {rep['trials_total']} trials in {dt * 1e3:.1f} ms"
+        f"{f' ({solves} solves: the LM stopped early)' if solves > 1 else ''}; "
         f"chi2 {rep['chi2_initial']:.6e} -> {rep['chi2_final']:.6e}")
     iters = rep["iterations"]
     t_max, _, _ = reduce_stats(dt, iters, rep["trials_total"], world, "cuda" if backend == "nccl" else "cpu")
     value = iters / t_max
-    stats = ctx.profile_trial(rep["lambda_final"])
-    # roofline: the edge linearization kernel (the dominant HBM stream): algorithmic bytes of one
-    # trial's two ba_edges launches / their device time
-    ed = stats.get("ba_edges", {"ms": 0.0, "bytes": 0.0, "launches": 0})
-    achieved = ed["bytes"] / max(ed["ms"] * 1e-3, 1e-12) / 1e9
-    roofline = {"bound": "hbm", "kernel": "ba_edges", "achieved": round(achieved, 1), "peak": 8000.0,
-                "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
-                "bytes_per_trial": ed["bytes"], "launches": ed["launches"],
-                "avg_launch_us": round(1e3 * ed["ms"] / max(ed["launches"], 1), 3)}
-    trial_ms = {k: round(v["ms"], 4) for k, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])}
+    if rank == 0 and args.dump_outputs:
+        poses, pts = ctx.download()
+        dump_outputs(args.dump_outputs, {"poses": poses, "points": pts, "chi2_iter": rep["chi2_iter"],
+                                         "chi2": [rep["chi2_initial"], rep["chi2_final"]]})
+    roofline, trial_ms = None, None
+    if args.full:
+        stats = ctx.profile_trial(rep["lambda_final"])
+        # roofline: the edge linearization kernel (the dominant HBM stream): algorithmic bytes of one
+        # trial's two ba_edges launches / their device time
+        ed = stats.get("ba_edges", {"ms": 0.0, "bytes": 0.0, "launches": 0})
+        achieved = ed["bytes"] / max(ed["ms"] * 1e-3, 1e-12) / 1e9
+        roofline = {"bound": "hbm", "kernel": "ba_edges", "achieved": round(achieved, 1), "peak": 8000.0,
+                    "unit": "GB/s", "frac": round(achieved / 8000.0, 4), "traffic": None,
+                    "bytes_per_trial": ed["bytes"], "launches": ed["launches"],
+                    "avg_launch_us": round(1e3 * ed["ms"] / max(ed["launches"], 1), 3)}
+        trial_ms = {k: round(v["ms"], 4) for k, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = ba_cpu_baseline(prob)
         log(f"BA cpu baseline: {cpu}")
     if rank == 0:
@@ -258,6 +279,7 @@ def main_ba(args, world, rank, gpu, backend):
             "value": value, "unit": "LM iterations/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": 1e3 * t_max / max(iters, 1), "higher_is_better": True,
             "scaling": args.ba_scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "full": args.full, "timed_solves": solves,
             "config": {"workload": f"BA-{full.n_points // 1000}k-x{full.n_poses}", "points": full.n_points,
                        "keyframes": full.n_poses, "edges": full.n_edges, "points_per_gpu": hi - lo,
                        "free_pose_dofs": 6 * (full.n_poses - 1),
@@ -284,6 +306,8 @@ def main_deformation(args, world, rank, gpu):
     import copy
     from deftri import optimization
     from deftri.settings import Settings
+    if args.dump_outputs:
+        raise SystemExit("--dump-outputs covers the LM workloads (c2-c5, ba), not --workload deformation")
     n = args.corr or 1000
     st = Settings(path=str(ROOT / "tests" / "golden" / "sim_default" / "settings.yaml"))
     st.depth_weight = 3.0
@@ -305,7 +329,7 @@ def main_deformation(args, world, rank, gpu):
     n_eval = sum(len(r.get("evaluations", [])) + 1 for r in out_rounds)
     log(f"deformation: {len(out_rounds)} rounds, {n_eval} arapOptimization calls in {dt:.2f} s")
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # one arapOptimization of the loop (the first Nelder-Mead evaluation: the map's clone at the
         # Simulation.yaml weights, 25 LM iterations) on the oracle — ~13 s of one core at 1k; the
         # whole first round (8 calls) is ~100 s
@@ -353,6 +377,59 @@ def job_rate(t_max, iters, units=1):
     shares one iteration of the problem covers (weak scaling: N, each rank holding one share), so
     value counts the correspondence-iterations of all ranks in units of the N = 1 iteration."""
     return iters * units / t_max, 1e3 * t_max / max(iters, 1)
+
+
+_SUMMED = ("iterations", "trials_total", "trials_rejected", "trials_executed", "pcg_trials", "pcg_fallbacks",
+           "pcg_iterations", "pcg_continuations", "pcg_given_up", "ms_total", "ms_linearize", "ms_pcg",
+           "ms_factor", "ms_solve", "ms_update")
+
+
+def timed_steps(solve, reset, steps):
+    """Exactly `steps` LM iterations: one solve(steps) when the LM runs them all (the usual case).  If it
+    stops early (g2o's Terminate: every trial of an iteration rejected, or lambda no longer finite),
+    reset() puts the initial state back and the remaining steps run as a fresh solve, until `steps`
+    are done.  Returns (report, solves): the counters and times summed over the solves, chi2_initial
+    of the first, everything else of the last."""
+    rep = solve(steps)
+    solves = 1
+    while 0 < rep["iterations"] < steps:
+        reset()
+        nxt = solve(steps - rep["iterations"])
+        if nxt["iterations"] <= 0:
+            break
+        solves += 1
+        merged = dict(nxt)
+        for k in _SUMMED:
+            if k in rep and k in nxt:
+                merged[k] = rep[k] + nxt[k] if (rep[k] >= 0 and nxt[k] >= 0) else nxt[k]
+        merged["chi2_initial"] = rep["chi2_initial"]
+        rep = merged
+    return rep, solves
+
+
+DUMP_BUDGET = 60_000_000              # payload bytes of one --dump-outputs (64 MB with room for the headers)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: one float64 .npy per array.  Over the budget, the arrays above 1 MB keep a fixed
+    seeded sample of their rows (sorted; the row indices in <name>_rows.npy)."""
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET:
+        big = [k for k, a in arrays.items() if a.nbytes > (1 << 20)]
+        share = (DUMP_BUDGET - sum(a.nbytes for k, a in arrays.items() if k not in big)) // len(big)
+        rng = np.random.default_rng(20240521)
+        for k in big:
+            a = arrays[k]
+            rows = share // (8 * (a.size // len(a)) + 8)
+            if rows < len(a):
+                idx = np.sort(rng.choice(len(a), rows, replace=False))
+                arrays[k] = a[idx]
+                arrays[k + "_rows"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(d / f"{k}.npy", a)
+    log(f"dumped {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} to {d}")
 
 
 # BASELINE workloads of the ARAP LM (SURVEY §8d): scene recipe, weights (rep, arap, depth sigma) and
@@ -575,6 +652,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=25, help="LM iterations timed (Simulation.yaml numberOfIterations: 25)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the profiled trial and its roofline, the CPU baseline, "
+                         "the end-to-end arapOptimization timing, the extra legs (north star 500k, Realcolon regime, c4)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the timed path left (what a caller downloads, and "
+                         "the report's chi2 history) as DIR/<name>.npy, float64, at most 64 MB")
     ap.add_argument("--trace-markers", action="store_true",
                     help="a tiny torch kernel right before and after the timed region (kernel-trace windows)")
     ap.add_argument("--corr", type=int, default=0, help="correspondences per keyframe (default: the workload's)")
@@ -678,7 +761,7 @@ def main():
         marker.mul_(2.0)                  # a kernel trace's window start (tools/trace_gaps.py --window mul)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    rep = ctx.solve_lm(args.steps, analytic=analytic)
+    rep, solves = timed_steps(lambda k: ctx.solve_lm(k, analytic=analytic), ctx.reset_state, args.steps)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if marker is not None:
@@ -690,8 +773,16 @@ def main():
         f"chi2 {rep['chi2_initial']:.6e} -> {rep['chi2_final']:.6e}; lambda {rep['lambda_final']:.3e}; "
         f"pcg {rep['pcg_trials']} / failed {rep['pcg_fallbacks']}, {rep['pcg_iterations']} CG iterations")
     iters = rep["iterations"]
+    if solves > 1:
+        log(f"[rank {rank}] the LM stopped early: the {iters} timed iterations are {solves} solves, each from the initial state")
     if iters != args.steps:
-        log(f"[rank {rank}] WARNING: LM terminated after {iters} of {args.steps} iterations")
+        log(f"[rank {rank}] WARNING: {iters} of {args.steps} iterations ran")
+    if rank == 0 and args.dump_outputs:
+        # the state the last timed step left (rank 0's download), before anything else touches the context
+        pts, sc, tg = ctx.download()
+        dump_outputs(args.dump_outputs, {"points": pts, "scales": sc, "pair_transforms": tg,
+                                         "chi2_iter": rep["chi2_iter"],
+                                         "chi2": [rep["chi2_initial"], rep["chi2_final"]]})
     # one problem (sharded): every rank ran the same iterations, the job takes the slowest rank;
     # replicas: the slowest rank's time for its own problem (value = per-problem rate, never a sum)
     t_max, _, _ = reduce_stats(dt, iters, rep["trials_total"], world, red_dev)
@@ -699,10 +790,11 @@ def main():
 
     # profiled trial (HIP events on the solver stream) at the final lambda of the timed run (a
     # collective on a sharded context: each rank times its own part of the same trial)
-    stats = ctx.profile_trial(rep["lambda_final"])
-    roofline = product_roofline(stats, rep, ctx, rank) if args.solver == "pcg" else None
+    full = args.full
+    stats = ctx.profile_trial(rep["lambda_final"]) if full else None
+    roofline = product_roofline(stats, rep, ctx, rank) if full and args.solver == "pcg" else None
     roofline_f, stats_f = None, None
-    if plan == "multifrontal" and not sharded:
+    if full and plan == "multifrontal" and not sharded:
         if args.solver == "pcg":
             ctx.set_linear_solver("direct")
             stats_f = ctx.profile_trial(rep["lambda_final"])
@@ -712,11 +804,11 @@ def main():
         roofline_f = factor_roofline(stats_f, rank)
     if roofline is None:
         roofline = roofline_f
-    trial_ms = {k: round(v["ms"], 4) for k, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])}
+    trial_ms = {k: round(v["ms"], 4) for k, v in sorted(stats.items(), key=lambda kv: -kv[1]["ms"])} if full else None
 
     cpu = None
     trials_per_it = rep["trials_total"] / max(iters, 1)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         if wl == "c2":
             # the oracle eliminates in a nested-dissection order of the same problem (the host-only
@@ -733,7 +825,7 @@ def main():
         log(f"cpu baseline {time.perf_counter() - t0:.1f}s: {cpu}")
 
     e2e = None
-    if world == 1 and not args.no_e2e and wl == "c2" and REGIME == "simulation" and n == 100000:
+    if full and world == 1 and not args.no_e2e and wl == "c2" and REGIME == "simulation" and n == 100000:
         def configure(c):
             c.set_plan(args.plan)
             c.set_jacobian_storage(1 if args.jacobian_fp32 else 0)
@@ -744,7 +836,7 @@ def main():
 
     legs_500k, regimes, legs_c4 = None, None, None
     headline = wl == "c2" and REGIME == "simulation" and n == 100000 and not args.replicas and not weak
-    if headline and not args.no_legs and args.solver == "pcg":
+    if full and headline and not args.no_legs and args.solver == "pcg":
         ctx.close()
         ctx = None
         p5 = build_problem(500000, 1)[0]
@@ -779,7 +871,7 @@ def main():
             "value": value, "unit": "LM iterations/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "weak" if (world > 1 and (weak or not sharded)) else "strong", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": full, "timed_solves": solves,
             "config": {"workload": workload, "correspondences_per_keyframe": n, "keyframes": spec["k"],
                        "pairs": prob.n_pairs, "pair_window": window,
                        "points": prob.n_points, "arap_edges": len(prob.arap_pair), "unknowns": rep["n_unknowns"],

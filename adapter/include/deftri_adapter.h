@@ -30,7 +30,10 @@ Sophus::SE3f se3f_from7(const double t7[7]);
 
 // A deftri_map view of a Map: the keyframes in the Map's own iteration order (the order every
 // reference loop takes), their slots, observations, keypoints, simulated depths and calibration,
-// and the global-transformation store queried for every ordered keyframe pair.
+// and the global-transformation store queried for every ordered keyframe pair.  The keyframes' depth
+// images (KeyFrame::getDepthIm) are registered on the calling thread's context
+// (deftri_set_depth_images) when the set differs from the one it holds, and cleared when no
+// keyframe has one: a keyframe with an image takes its depth measurements from it.
 class MapView {
 public:
     explicit MapView(Map *pMap);

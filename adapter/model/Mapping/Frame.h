@@ -55,6 +55,9 @@ public:
     float getSigma2(int octave) { return vSigma2_[octave]; }
     float getInvSigma2(int octave) { return vInvSigma2_[octave]; }
     double getDepthScale() { return imageDepthScale_; }
+    // real images (Frame.cc:367-396): the frame keeps its own copy of the depth image
+    void setDepthIm(cv::Mat &im) { depthIm_ = im.clone(); }
+    cv::Mat getDepthIm() { return depthIm_.clone(); }
     double getEstimatedDepthScale() { return estimatedDepthScale_; }
     void setEstimatedDepthScale(double scale) { estimatedDepthScale_ = scale; }
     float getDepthError() { return depthError_; }
@@ -66,6 +69,7 @@ private:
     std::shared_ptr<CameraModel> calibration_, phcalibration_;
     double imageDepthScale_ = 0.0, estimatedDepthScale_ = 1.0;
     float depthError_ = 0.0f;
+    cv::Mat depthIm_;
     Sophus::SE3f Tcw_;
     std::vector<float> vScaleFactor_, vInvScaleFactor_, vSigma2_, vInvSigma2_;
 };

@@ -8,7 +8,8 @@
 //   Eigen:   Vector3f/Vector3d/Vector2f (x(), y(), z(), operator(), cast<T>(), norm()),
 //            Quaternionf/Quaterniond (ctor (w, x, y, z), x() y() z() w(), cast<T>())
 //   Sophus:  SE3f (ctor (Quaternionf, Vector3f), unit_quaternion(), translation(), inverse())
-//   OpenCV:  cv::KeyPoint (pt.x, pt.y, octave), cv::Point2f
+//   OpenCV:  cv::KeyPoint (pt.x, pt.y, octave), cv::Point2f, cv::Mat (CV_32F: rows, cols, empty(),
+//            ptr<float>(), clone())
 //
 // Arithmetic that reaches the solver follows the restatements the native library already pins:
 // SO3 construction from a quaternion normalizes in float by the reciprocal of its norm, and the
@@ -19,6 +20,10 @@
 
 #include <cmath>
 #include <cstddef>
+#include <memory>
+#include <stdexcept>
+#include <type_traits>
+#include <vector>
 
 namespace Eigen {
 
@@ -163,5 +168,39 @@ struct KeyPoint {
     Point2f pt;
     float size = 0.f, angle = -1.f, response = 0.f;
     int octave = 0, class_id = -1;
+};
+// cv::Mat as the depth-image path uses it: one channel of CV_32F, continuous, the pixel data shared
+// between copies (as cv::Mat's reference-counted header) and duplicated by clone()
+#ifndef CV_32F
+#define CV_32F 5
+#endif
+class Mat {
+public:
+    int rows = 0, cols = 0;
+    Mat() = default;
+    Mat(int nRows, int nCols, int type) : rows(nRows), cols(nCols), data_(std::make_shared<std::vector<float>>((size_t)nRows * nCols)) {
+        if (type != CV_32F) throw std::invalid_argument("model cv::Mat holds CV_32F only");
+    }
+    bool empty() const { return !data_ || rows == 0 || cols == 0; }
+    template <typename T>
+    T *ptr(int row = 0) {
+        static_assert(std::is_same<T, float>::value, "model cv::Mat holds CV_32F only");
+        return data_->data() + (size_t)row * cols;
+    }
+    template <typename T>
+    const T *ptr(int row = 0) const {
+        static_assert(std::is_same<T, float>::value, "model cv::Mat holds CV_32F only");
+        return data_->data() + (size_t)row * cols;
+    }
+    Mat clone() const {
+        Mat m;
+        m.rows = rows;
+        m.cols = cols;
+        if (data_) m.data_ = std::make_shared<std::vector<float>>(*data_);
+        return m;
+    }
+
+private:
+    std::shared_ptr<std::vector<float>> data_;
 };
 }  // namespace cv

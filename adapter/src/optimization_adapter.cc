@@ -35,6 +35,7 @@ struct ThreadContexts {
 thread_local ThreadContexts t_ctx;
 thread_local deftri_report t_report;
 thread_local deftri_deformation_report t_def_report;
+thread_local std::vector<uint64_t> t_image_sig;   // the depth image set the thread's context holds
 }  // namespace
 
 void set_device(int device) { g_device = device; }
@@ -119,6 +120,7 @@ MapView::MapView(Map *pMap) {
             A.oct[j] = keys[j].octave;
             // the per-index simulated depth (KeyFrame.cc:123-125); the image lookup of :816,846 throws
             // in the simulation
+            // (a keyframe with a depth image takes the lookup from the image registered below)
             A.dep[j] = kf.getDepthMeasure(j);
         }
         const int nScales = kf.getNumberOfScales();
@@ -164,6 +166,37 @@ MapView::MapView(Map *pMap) {
     std::copy(identity7, identity7 + 7, m_.global_t);
     m_.n_global = (int32_t)globals_.size();
     m_.globals = globals_.data();
+    // the keyframes' depth images (real keyframes): on the context, re-sent only when the set changed
+    std::vector<cv::Mat> images;
+    std::vector<deftri_depth_image> desc;
+    std::vector<uint64_t> sig;
+    for (size_t k = 0; k < K; k++) {
+        cv::Mat im = order_[k]->getDepthIm();
+        if (im.empty()) continue;
+        deftri_depth_image d{};
+        d.kf_id = (int64_t)order_[k]->getId();
+        d.rows = im.rows;
+        d.cols = im.cols;
+        d.pixels = im.ptr<float>(0);
+        d.image_depth_scale = order_[k]->getDepthScale();
+        std::shared_ptr<CameraModel> ph = order_[k]->getPHCalibration();
+        for (int i = 0; i < 4; i++) d.ph[i] = ph->getParameter(i);
+        uint64_t h = 1469598103934665603ull;                               // FNV-1a over the description and the pixels
+        auto mix = [&h](const void *p, size_t n) {
+            const unsigned char *c = static_cast<const unsigned char *>(p);
+            for (size_t i = 0; i < n; i++) h = (h ^ c[i]) * 1099511628211ull;
+        };
+        mix(&d.kf_id, sizeof(d.kf_id)); mix(&d.rows, sizeof(d.rows)); mix(&d.cols, sizeof(d.cols));
+        mix(&d.image_depth_scale, sizeof(d.image_depth_scale)); mix(d.ph, sizeof(d.ph));
+        mix(d.pixels, sizeof(float) * (size_t)d.rows * d.cols);
+        sig.push_back(h);
+        images.push_back(im);
+        desc.push_back(d);
+    }
+    if (sig != t_image_sig) {
+        deftri_ctx *ctx = context();
+        if (ctx && deftri_set_depth_images(ctx, (int32_t)desc.size(), desc.data()) == 0) t_image_sig = sig;
+    }
 }
 
 void MapView::write_back(Map *pMap) {

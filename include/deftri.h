@@ -398,7 +398,7 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
 /* sizeof() of the ABI structs for binding checks: 0 deftri_problem_desc, 1 deftri_lm_params,
    2 deftri_report, 3 deftri_keyframe, 4 deftri_map, 5 deftri_ba_desc, 6 deftri_pixels_error,
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
-   10 deftri_deformation_eval. */
+   10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors. */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -417,7 +417,9 @@ typedef struct deftri_keyframe {
     const int32_t *obs_index;   /* [n_slots] Map::isMapPointInKeyFrame(point, kf) (< 0 = none) */
     const float *kp_uv;         /* [n_obs*2] keypoints by observation index */
     const int32_t *kp_octave;   /* [n_obs] */
-    const float *depth;         /* [n_obs] simulated depth per observation index (KeyFrame.cc:123-125) */
+    const float *depth;         /* [n_obs] simulated depth per observation index (KeyFrame.cc:123-125);
+                                   unused, and may be NULL, for a keyframe with a depth image on the
+                                   context (deftri_set_depth_images) */
     int32_t n_obs;
 } deftri_keyframe;
 
@@ -490,6 +492,72 @@ typedef struct deftri_rel_errors {
 } deftri_rel_errors;
 int deftri_measure_relative_map_errors(int32_t device, const deftri_map *map, deftri_rel_errors *out,
                                        int32_t max_pairs, int32_t *n_pairs);
+
+/* ---- real-image input: keyframe depth images ------------------------------------------------
+   With real keyframes the reference takes every depth measurement from the keyframe's depth image:
+   KeyFrame::getDepthMeasure(x, y, scaled) (KeyFrame.cc:181-202) = the bilinear Interpolate
+   (Geometry.cc:607-620, fp32) of the CV_32F image, (double)interp / 100, and — for scaled == 0; the
+   reference's flag name reads backwards, KeyFrame.cc:196-201 — times imageDepthScale_.
+   arapOptimization's depth edges (g2oBundleAdjustment.cc:816,846) and measureRelativeMapErrors
+   (Measurements.cc:439-440) call it with scaled = false, measureRealAbsoluteMapErrors (:179-180)
+   with the default true.
+   deftri_set_depth_images copies the images to memory owned by the context (device memory on a
+   device context), where they stay until the next call replaces the set (n = 0 clears it).  From then
+   on every graph build on the context (deftri_arap_build_graph, deftri_arap_optimization, every
+   clone and round of deftri_deformation_optimization) reads the depth measurement of a keyframe
+   that has an image from the image at the observation's keypoint; such a keyframe's `depth` may be
+   NULL.  Keyframes without an image use depth[] as before (mixed maps are legal).  The depths of a
+   keyframe are sampled once per (image set, keyframe, keypoints) and cached on the context.
+   Status per pixel: 0 ok; 1 x >= cols or y >= rows (the reference throws std::out_of_range); 2 the
+   reference would read outside the buffer (a negative or non-finite coordinate, or one of the four
+   linear indices r*cols+c, +1, (r+1)*cols+c, +1 at or beyond rows*cols, e.g. y in the last row).
+   The reference's row-major spill into the next row at x in [cols-1, cols) of a row that is not the
+   last is defined memory and is reproduced.  A pixel with a non-zero status is never loaded and its
+   depth is NaN; a graph build or measurement fails with DEFTRI_E_ARG only when an observation it
+   uses has a non-zero status (the message names the keyframe id, the observation index and the
+   pixel), leaving the map unchanged. */
+typedef struct deftri_depth_image {
+    int64_t kf_id;             /* KeyFrame id */
+    int32_t rows, cols;        /* CV_32F, row-major, continuous */
+    const float *pixels;       /* [rows*cols], host, read during the call only */
+    double image_depth_scale;  /* KeyFrame::imageDepthScale_ */
+    float ph[4];               /* KeyFrame::phcalibration_: fx fy cx cy (PinHole.h:42) */
+} deftri_depth_image;
+int deftri_set_depth_images(deftri_ctx *ctx, int32_t n, const deftri_depth_image *images);
+/* getDepthMeasure(uv[2k], uv[2k+1], scaled) of keyframe kf_id's image for n pixels: depth [n] and
+   status [n] (either may be NULL).  On a device context the device samples (k_depth_sample); a
+   host-only context runs the same function on the host. */
+int deftri_depth_measure(deftri_ctx *ctx, int64_t kf_id, int32_t n, const float *uv, int32_t scaled,
+                         double *depth, uint8_t *status);
+/* Images copied by deftri_set_depth_images and keyframe samplings (cache misses) over the context's
+   life; both stay 0 on a context that never received an image. */
+int deftri_depth_image_stats(const deftri_ctx *ctx, int64_t *uploads, int64_t *samplings);
+
+/* measureRealAbsoluteMapErrors (Measurements.cc:101-348) with the context's depth images: per pair
+   (camera 1 = k2) and matched slot, both keypoints unprojected with keyframe 1's pinhole calibration,
+   scaled by each keyframe's own getDepthMeasure(x, y) and taken to the world by T.inverse().matrix();
+   a second pass per pair divides by the running scales.  n_points, scale1 and scale2 carry across
+   the pairs as in the reference (scale = scale / n_points after each pair's first pass).  Figures
+   in mm; the per-slot terms are summed in fp64 in a fixed order and the totals cast to float before
+   the reference's float divisions.  Every keyframe needs an image; kf2.n_slots <
+   kf1.n_slots or an observation index out of range is DEFTRI_E_ARG (the reference indexes
+   unchecked). */
+typedef struct deftri_real_abs_errors {
+    double average_movement;           /* "Av. movement" (:335) */
+    double average_error;              /* "Av. error" */
+    double rmse;                       /* "RMSE" */
+    double average_up_to_scale_error;  /* "Av. up-to-scale error in 3D" */
+    int64_t point_count;               /* Map::getMapPoints().size() */
+    int64_t n_points;                  /* matched slots over all pairs (testing) */
+    double scale1, scale2;             /* the float accumulators after the last pair (testing) */
+} deftri_real_abs_errors;
+int deftri_measure_real_absolute_map_errors(deftri_ctx *ctx, const deftri_map *map, deftri_real_abs_errors *out);
+/* deftri_measure_relative_map_errors with the depth measurements of keyframes that have an image
+   taken from the context's images (getDepthMeasure(u, v, false)), on the context's device.  As the
+   reference (Measurements.cc:432,440), the pixel looked up in keyframe 2's image is keyframe 1's
+   keypoint idx2; idx2 >= kf1.n_obs is DEFTRI_E_ARG. */
+int deftri_measure_relative_map_errors_images(deftri_ctx *ctx, const deftri_map *map, deftri_rel_errors *out,
+                                              int32_t max_pairs, int32_t *n_pairs);
 
 
 /* Mapping::triangulateSimulatedMapPoints (Modules/Mapping/Mapping.cc:280-349) for Triangulation.method

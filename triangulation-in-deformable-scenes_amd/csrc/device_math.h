@@ -189,5 +189,41 @@ __device__ __forceinline__ void kb8_project_jac(const float *k, const float p[3]
     J[5] = -k[1] * fd * p[1] / (r2 + z2);
 }
 
+// ---- keyframe depth image lookup (host and device) ------------------------------------------
+// KeyFrame::getDepthMeasure(x, y, scaled) (KeyFrame.cc:181-202) over Interpolate (Geometry.cc:
+// 607-620), fp32 without contraction as the reference's build.  The status is decided before any
+// load (deftri.h): 1 where the reference throws std::out_of_range (x >= cols || y >= rows, its first
+// test), 2 where it would read outside the buffer — a negative or non-finite coordinate (the
+// (int) casts), or the last of its four linear indices, (r+1)*cols + c + 1, at or beyond rows*cols.
+// The spill into the next row at x in [cols-1, cols) of a row that is not the last stays inside the
+// buffer and is reproduced.
+__host__ __device__ __forceinline__ int depth_pixel_status(float x, float y, int rows, int cols) {
+    if (x >= (float)cols || y >= (float)rows) return 1;
+    if (!(x >= 0.0f) || !(y >= 0.0f)) return 2;          // negative, NaN (-inf too; +inf went above)
+    const long long r = (long long)y, c = (long long)x;
+    return ((r + 1) * cols + c + 1 >= (long long)rows * cols) ? 2 : 0;
+}
+
+__host__ __device__ __forceinline__ double depth_measure_px(const float *mat, int rows, int cols, double image_depth_scale,
+                                                            float x, float y, int scaled, unsigned char *status) {
+#pragma clang fp contract(off)
+    const int st = depth_pixel_status(x, y, rows, cols);
+    *status = (unsigned char)st;
+    if (st) return __builtin_nan("");
+    float x_, y_;
+    const float _x = modff(x, &x_), _y = modff(y, &y_);
+    const float w00 = (1.f - _x) * (1.f - _y);
+    const float w01 = (1.f - _x) * _y;
+    const float w10 = _x * (1.f - _y);
+    const float w11 = 1.f - w00 - w01 - w10;
+    const int r = (int)y_, c = (int)x_;
+    const float g = mat[r * cols + c] * w00 + mat[r * cols + c + 1] * w10 + mat[(r + 1) * cols + c] * w01 +
+                    mat[(r + 1) * cols + c + 1] * w11;
+    const double depth = (double)g / 100;
+    // the reference's flag reads backwards (KeyFrame.cc:196-201): scaled returns the plain depth,
+    // !scaled multiplies by imageDepthScale_
+    return scaled ? depth : depth * image_depth_scale;
+}
+
 }  // namespace dev
 }  // namespace deftri

@@ -269,12 +269,14 @@ void append(std::vector<unsigned char> &k, const void *p, size_t n) {
 template <class T> void append_v(std::vector<unsigned char> &k, const T &v) { append(k, &v, sizeof(T)); }
 // values = false: the structure key — everything but the positions, the depth scales and the global
 // transformations' values (what deformationOptimization's write-back changes between rounds)
-std::vector<unsigned char> graph_key(const deftri_map &map, int pair_window, bool values = true) {
+// a keyframe with a depth image (dv[a].meas): the doubles sampled from the image stand in place of f.depth
+std::vector<unsigned char> graph_key(const deftri_map &map, int pair_window, const std::vector<DepthView> &dv,
+                                     bool values = true) {
     std::vector<unsigned char> k;
     size_t sz = 64;
     for (int a = 0; a < map.n_keyframes; a++) {
         const deftri_keyframe &f = map.keyframes[a];
-        sz += 160 + (size_t)std::max(f.n_slots, 0) * 24 + (size_t)std::max(f.n_obs, 0) * 16 + 4 * (size_t)std::max(f.n_scales, 0);
+        sz += 160 + (size_t)std::max(f.n_slots, 0) * 24 + (size_t)std::max(f.n_obs, 0) * 20 + 4 * (size_t)std::max(f.n_scales, 0);
     }
     k.reserve(sz + (size_t)std::max(map.n_global, 0) * sizeof(deftri_global_entry));
     append_v(k, map.n_keyframes); append_v(k, pair_window); append_v(k, map.n_global);
@@ -294,7 +296,13 @@ std::vector<unsigned char> graph_key(const deftri_map &map, int pair_window, boo
             if (values) append(k, f.point_pos, 12 * (size_t)f.n_slots);
             append(k, f.obs_index, 4 * (size_t)f.n_slots);
         }
-        if (f.n_obs > 0) { append(k, f.kp_uv, 8 * (size_t)f.n_obs); append(k, f.kp_octave, 4 * (size_t)f.n_obs); append(k, f.depth, 4 * (size_t)f.n_obs); }
+        if (f.n_obs > 0) { append(k, f.kp_uv, 8 * (size_t)f.n_obs); append(k, f.kp_octave, 4 * (size_t)f.n_obs); }
+        const unsigned char from_image = dv[a].meas ? 1 : 0;
+        append_v(k, from_image);
+        if (f.n_obs > 0) {
+            if (from_image) append(k, dv[a].meas, 8 * (size_t)f.n_obs);
+            else append(k, f.depth, 4 * (size_t)f.n_obs);
+        }
     }
     return k;
 }
@@ -435,13 +443,13 @@ int refresh_graph(const deftri_map &map, double rep_weight, double arap_weight, 
     return 0;
 }
 
-bool map_ok(const deftri_map &map, std::string &err) {
+bool map_ok(const deftri_map &map, const std::vector<DepthView> &dv, std::string &err) {
     if (map.n_keyframes < 0 || (map.n_keyframes > 0 && !map.keyframes)) { err = "bad map"; return false; }
     if (map.n_global > 0 && !map.globals) { err = "bad map: globals"; return false; }
     for (int a = 0; a < map.n_keyframes; a++) {
         const deftri_keyframe &f = map.keyframes[a];
         if (f.n_slots < 0 || f.n_obs < 0 || f.n_scales < 0 || (f.n_slots > 0 && (!f.point_id || !f.point_pos || !f.obs_index)) ||
-            (f.n_obs > 0 && (!f.kp_uv || !f.kp_octave || !f.depth)) || (f.n_scales > 0 && !f.inv_sigma2)) {
+            (f.n_obs > 0 && (!f.kp_uv || !f.kp_octave || (!f.depth && !dv[a].meas))) || (f.n_scales > 0 && !f.inv_sigma2)) {
             err = "bad map: keyframe arrays";
             return false;
         }
@@ -449,6 +457,9 @@ bool map_ok(const deftri_map &map, std::string &err) {
     return true;
 }
 }  // namespace
+
+// marks a scan error that is the caller's argument (DEFTRI_E_ARG), not a graph failure
+static const std::string kDepthArg = "\x01";
 
 // one pair's edge layout, fixed by the sequential pass of build_arap_graph
 struct PairEmit {
@@ -463,7 +474,8 @@ constexpr int kEmitChunk = 1 << 14;
 
 // one pair's slot walk (:765-953's loop): the observation checks, the edge counts per slot chunk and
 // the first-encounter order of the slots (a slot with both MapPoints, then its ARAP neighbours)
-void scan_pair(const deftri_map &map, PairEmit &pe, const GraphResult::MeshData &MD, std::string &err) {
+void scan_pair(const deftri_map &map, PairEmit &pe, const GraphResult::MeshData &MD, const std::vector<DepthView> &dv,
+               std::string &err) {
     const deftri_keyframe &kf1 = map.keyframes[pe.b], &kf2 = map.keyframes[pe.a];
     const int ns12 = pe.ns12;
     std::vector<uint8_t> seen((size_t)ns12, 0);
@@ -480,6 +492,9 @@ void scan_pair(const deftri_map &map, PairEmit &pe, const GraphResult::MeshData 
         if (o1 >= kf1.n_obs || o2 >= kf2.n_obs) { err = "observation index out of range"; return; }
         const int32_t oc1 = kf1.kp_octave[o1], oc2 = kf2.kp_octave[o2];
         if (oc1 < 0 || oc1 >= kf1.n_scales || oc2 < 0 || oc2 >= kf2.n_scales) { err = "keypoint octave out of range"; return; }
+        // a depth edge of an observation the image lookup cannot serve (deftri.h: status 1 / 2)
+        if (dv[pe.b].status && dv[pe.b].status[o1]) { err = kDepthArg + depth_status_message(kf1.id, o1, kf1.kp_uv + 2 * (size_t)o1, dv[pe.b].status[o1]); return; }
+        if (dv[pe.a].status && dv[pe.a].status[o2]) { err = kDepthArg + depth_status_message(kf2.id, o2, kf2.kp_uv + 2 * (size_t)o2, dv[pe.a].status[o2]); return; }
         pe.n_obs++;
         if (mp >= MD.n1) continue;
         const int i = MD.inv[mp];
@@ -496,7 +511,8 @@ void scan_pair(const deftri_map &map, PairEmit &pe, const GraphResult::MeshData 
 // the reprojection (:765-812), depth (:816-856) and ARAP (:871-953) edges of one pair, written
 // into the pair's ranges; the same filters as the counting pass, so the counts agree
 void emit_pair_edges(const deftri_map &map, const PairEmit &pe, int chunk, const GraphResult::MeshData &MD, double rep_weight,
-                     double info_dep, GraphResult &g) {
+                     double info_dep, const std::vector<DepthView> &dv, GraphResult &g) {
+    const double *im1 = dv[pe.b].meas, *im2 = dv[pe.a].meas;   // getDepthMeasure(u, v, false) of the keyframes' images
     const deftri_keyframe &kf1 = map.keyframes[pe.b], &kf2 = map.keyframes[pe.a];
     const int32_t *sp = pe.slot_pt.data();
     const double *w = g.wcat.data() + pe.w_off;
@@ -515,9 +531,9 @@ void emit_pair_edges(const deftri_map &map, const PairEmit &pe, int chunk, const
         g.rep_obs[2 * r + 2] = (double)kf2.kp_uv[2 * o2]; g.rep_obs[2 * r + 3] = (double)kf2.kp_uv[2 * o2 + 1];
         g.rep_base[r + 1] = base2; g.rep_info[r + 1] = base2 * rep_weight;
         g.dep_point[r] = p1; g.dep_scale[r] = pe.s1; g.dep_cam[r] = pe.c1;
-        g.dep_meas[r] = (double)kf1.depth[o1]; g.dep_info[r] = info_dep;
+        g.dep_meas[r] = im1 ? im1[o1] : (double)kf1.depth[o1]; g.dep_info[r] = info_dep;
         g.dep_point[r + 1] = p2; g.dep_scale[r + 1] = pe.s2; g.dep_cam[r + 1] = pe.c2;
-        g.dep_meas[r + 1] = (double)kf2.depth[o2]; g.dep_info[r + 1] = info_dep;
+        g.dep_meas[r + 1] = im2 ? im2[o2] : (double)kf2.depth[o2]; g.dep_info[r + 1] = info_dep;
         r += 2;
         if (mp >= MD.n1) continue;
         const int i = MD.inv[mp];
@@ -538,12 +554,19 @@ void emit_pair_edges(const deftri_map &map, const PairEmit &pe, int chunk, const
 }
 
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
-                      GraphResult &g, std::string &err, int pair_window, GraphDevice *gdev) {
-    if (!map_ok(map, err)) return false;
+                      GraphResult &g, std::string &err, int pair_window, GraphDevice *gdev, DepthImages *images) {
+    g.err_code = 0;
+    // the keyframes with a depth image on the context: their depth measurements come from the image
+    std::vector<DepthView> dv((size_t)std::max(map.n_keyframes, 0));
+    if (images && images->any() && map.n_keyframes > 0 && map.keyframes) {
+        const int rc = images->views(map, dv, err);
+        if (rc) { g.err_code = rc; return false; }
+    }
+    if (!map_ok(map, dv, err)) return false;
     const double info_dep = 1.0 / ((double)depth_error * (double)depth_error);
     static const bool no_memo = std::getenv("DEFTRI_NO_GRAPH_MEMO") != nullptr;
     const auto t_build = std::chrono::steady_clock::now();
-    std::vector<unsigned char> key = graph_key(map, pair_window);
+    std::vector<unsigned char> key = graph_key(map, pair_window, dv);
     if (!no_memo && g.memo_valid && key == g.memo_key) {
         // the same map: only the weights can differ; recompute the information entries they scale
         for (size_t e = 0; e < g.rep_info.size(); e++) g.rep_info[e] = g.rep_base[e] * rep_weight;
@@ -553,7 +576,7 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
         g.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
         return true;
     }
-    std::vector<unsigned char> skey = graph_key(map, pair_window, false);
+    std::vector<unsigned char> skey = graph_key(map, pair_window, dv, false);
     static const bool no_struct = std::getenv("DEFTRI_NO_STRUCT_MEMO") != nullptr;
     if (!no_memo && !no_struct && g.struct_valid && skey == g.struct_key) {
         // refresh_graph writes the values pair by pair: until it succeeds neither memo describes g
@@ -763,10 +786,15 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
         auto ts = tnow();
         std::vector<std::string> perr(emits.size());
         parallel_for((int)emits.size(), 1, [&](int lo, int hi) {
-            for (int e = lo; e < hi; e++) scan_pair(map, emits[e], *g.meshes[e].mesh, perr[e]);
+            for (int e = lo; e < hi; e++) scan_pair(map, emits[e], *g.meshes[e].mesh, dv, perr[e]);
         });
         for (size_t e = 0; e < emits.size(); e++)
-            if (!perr[e].empty()) { err = perr[e]; return false; }   // the first pair's first error
+            if (!perr[e].empty()) {                                  // the first pair's first error
+                err = perr[e];
+                // the graph under construction is dropped whole: no memo may answer for it
+                if (err.compare(0, kDepthArg.size(), kDepthArg) == 0) { err.erase(0, kDepthArg.size()); g.err_code = DEFTRI_E_ARG; }
+                return false;
+            }
         const auto ts_scan = tnow();
         // (ii) the points, created in the pairs' order, each at its first encounter; a slot's two
         //      MapPoints are fixed within the pair, so their graph indices are looked up once
@@ -893,7 +921,7 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
         parallel_for((int)tasks.size(), 1, [&](int lo, int hi) {
             for (int t = lo; t < hi; t++) {
                 const int e = tasks[t].first;
-                emit_pair_edges(map, emits[e], tasks[t].second, *g.meshes[e].mesh, rep_weight, info_dep, g);
+                emit_pair_edges(map, emits[e], tasks[t].second, *g.meshes[e].mesh, rep_weight, info_dep, dv, g);
             }
         });
         if (timing) std::fprintf(stderr, "[deftri graph] edges written: %.1f ms (arrays %.1f)\n", ms(t0, tnow()), ms(t0, t1));

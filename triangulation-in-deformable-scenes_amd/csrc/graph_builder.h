@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/deftri.h"
+#include "depth_image.h"
 
 namespace deftri {
 
@@ -65,6 +66,7 @@ struct GraphResult {
     int64_t struct_hits = 0;                  // calls answered by the structure memo
     int64_t mesh_repairs = 0, mesh_flips = 0; // full builds' meshes flip-repaired from the previous round (kept)
     double ms_last = 0;                       // host time of the last build (either path)
+    int err_code = 0;                         // a failed build: the error code when it is not DEFTRI_E_GRAPH
 };
 
 // The per-pair geometry on the device (graph_dev.hip): the cot weights of the pair's CSR mesh (one
@@ -92,7 +94,8 @@ class GraphDevice {
 // pair_window > 0: only keyframe pairs (a, b) with b - a <= pair_window in map order (the
 // sliding-window deviation of BASELINE C5; 0 = every pair, the reference's loop :640-645)
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
-                      GraphResult &g, std::string &err, int pair_window = 0, GraphDevice *gdev = nullptr);
+                      GraphResult &g, std::string &err, int pair_window = 0, GraphDevice *gdev = nullptr,
+                      DepthImages *images = nullptr);
 
 void writeback_arap(deftri_map &map, const GraphResult &g, const std::vector<double> &points,
                     const std::vector<double> &scales, const std::vector<double> &tg, double *optimization_update);

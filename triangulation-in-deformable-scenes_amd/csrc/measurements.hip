@@ -16,7 +16,9 @@
 
 #include "../../include/deftri.h"
 #include "graph_builder.h"
+#include "depth_image.h"
 #include "kernels.h"
+#include "measure_scratch.h"
 
 namespace deftri {
 namespace dev {
@@ -94,15 +96,6 @@ __global__ void k_depth_terms(int n, const float *__restrict__ pw, const double 
 
 namespace {
 
-static inline unsigned nblk(int64_t n, int bs) { return (unsigned)((n + bs - 1) / bs); }
-
-// fixed-order sums of `cnt` consecutive arrays of n doubles (device) -> host
-int sums(const double *d_terms, int64_t n, int cnt, double *part, double *d_out, double *h_out, hipStream_t st) {
-    for (int c = 0; c < cnt; c++) launch_sum(n, d_terms + c * n, nullptr, 0, 0, part, 256, d_out + c, st);
-    if (hipMemcpyAsync(h_out, d_out, sizeof(double) * cnt, hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
-    return hipStreamSynchronize(st) == hipSuccess ? 0 : -1;
-}
-
 void quat_to_R(const double *q, double *R) {     // unit quaternion (x y z w) -> row-major R
     const double x = q[0], y = q[1], z = q[2], w = q[3];
     const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
@@ -116,26 +109,6 @@ void quat_to_R(const double *q, double *R) {     // unit quaternion (x y z w) ->
 }  // namespace deftri
 
 using namespace deftri;
-
-// device scratch of one measurement call (freed before returning)
-struct Scratch {
-    std::vector<void *> p;
-    ~Scratch() { for (void *q : p) hipFree(q); }
-    template <class T>
-    T *put(const std::vector<T> &v) {
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(T) * std::max<size_t>(v.size(), 1)) != hipSuccess) return nullptr;
-        p.push_back(d);
-        if (!v.empty()) hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
-        return (T *)d;
-    }
-    double *alloc(size_t n) {
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(double) * std::max<size_t>(n, 1)) != hipSuccess) return nullptr;
-        p.push_back(d);
-        return (double *)d;
-    }
-};
 
 extern "C" int deftri_measure_sim_absolute_map_errors(int32_t device, const deftri_map *map, int32_t n_points,
                                                       const float *original, const float *moved,
@@ -199,10 +172,22 @@ extern "C" int deftri_measure_sim_absolute_map_errors(int32_t device, const deft
 extern "C" int deftri_measure_relative_map_errors(int32_t device, const deftri_map *map, deftri_rel_errors *out,
                                                   int32_t max_pairs, int32_t *n_pairs) {
     if (!map || !n_pairs || map->n_keyframes < 0 || (max_pairs > 0 && !out)) return DEFTRI_E_ARG;
+    std::string err;
+    return measure_relative(nullptr, device, nullptr, *map, out, max_pairs, n_pairs, err);
+}
+
+int deftri::measure_relative(DepthImages *di, int device, hipStream_t st, const deftri_map &map_ref, deftri_rel_errors *out,
+                             int32_t max_pairs, int32_t *n_pairs, std::string &err_out) {
+    const deftri_map *map = &map_ref;
     *n_pairs = 0;
     const int K = map->n_keyframes;
     if (hipSetDevice(device) != hipSuccess) return DEFTRI_E_NODEVICE;
-    hipStream_t st = nullptr;
+    // keyframes with an image on the context: getDepthMeasure(u, v, false) from the image
+    std::vector<DepthView> dv(K);
+    if (di && di->any()) {
+        const int rc = di->views(*map, dv, err_out);
+        if (rc) return rc;
+    }
     // accumulators carried across the pairs, as in the reference
     double depthError = 0, globalT = 0, meanSq = 0;
     int64_t validPairs = 0, nMatches = 0;
@@ -257,6 +242,8 @@ extern "C" int deftri_measure_relative_map_errors(int32_t device, const deftri_m
             std::vector<float> dpw;
             std::vector<double> dm;
             std::vector<int32_t> ij;
+            std::vector<float> uv2;                               // keyframe 2's image: the pixels to look up
+            std::vector<int32_t> obs2;
             int64_t pairMatches = 0, pairValid = 0;
             const int ns = std::min(kf1.n_slots, kf2.n_slots);
             for (int i = 0; i < ns; i++) {
@@ -268,8 +255,27 @@ extern "C" int deftri_measure_relative_map_errors(int32_t device, const deftri_m
                 for (int c = 0; c < 3; c++) dpw.push_back(kf2.point_pos[3 * i + c]);
                 // getDepthMeasure(u, v, false) reads a depth image the simulation never sets (it throws
                 // there): the per-index simulated depth, as the solver's depth edges
-                dm.push_back((double)kf1.depth[idx1]);
-                dm.push_back((double)kf2.depth[idx2]);
+                // a keyframe with an image on the context: the image lookup.  The reference looks keyframe
+                // 1's keypoint idx2 up in keyframe 2's image (Measurements.cc:432,440): reproduced
+                if (dv[b].meas) {
+                    if (dv[b].status[idx1]) {
+                        err_out = depth_status_message(kf1.id, idx1, kf1.kp_uv + 2 * (size_t)idx1, dv[b].status[idx1]);
+                        return DEFTRI_E_ARG;
+                    }
+                    dm.push_back(dv[b].meas[idx1]);
+                } else {
+                    if (!kf1.depth) { err_out = "keyframe without a depth image needs depth[]"; return DEFTRI_E_ARG; }
+                    dm.push_back((double)kf1.depth[idx1]);
+                }
+                if (dv[a].meas) {
+                    if (idx2 >= kf1.n_obs) { err_out = "keyframe 1 has no keypoint idx2 (Measurements.cc:432)"; return DEFTRI_E_ARG; }
+                    uv2.push_back(kf1.kp_uv[2 * (size_t)idx2]); uv2.push_back(kf1.kp_uv[2 * (size_t)idx2 + 1]);
+                    obs2.push_back(idx2);
+                    dm.push_back(0.0);                            // filled below from the image
+                } else {
+                    if (!kf2.depth) { err_out = "keyframe without a depth image needs depth[]"; return DEFTRI_E_ARG; }
+                    dm.push_back((double)kf2.depth[idx2]);
+                }
                 if (i >= n1 || inv[i] < 0) continue;             // slot i used as a position index
                 const int meshIndex = inv[i];
                 if (adj[meshIndex].empty()) continue;
@@ -282,6 +288,16 @@ extern "C" int deftri_measure_relative_map_errors(int32_t device, const deftri_m
                 pairMatches++;
             }
             const int64_t nr = (int64_t)ij.size() / 2, nd = (int64_t)dm.size() / 2;
+            if (!obs2.empty()) {                                  // every matched slot, in order
+                std::vector<double> d2(obs2.size());
+                std::vector<uint8_t> s2st(obs2.size());
+                const int rc = di->measure(kf2.id, (int32_t)obs2.size(), uv2.data(), 0, d2.data(), s2st.data(), err_out);
+                if (rc) return rc;
+                for (size_t k = 0; k < obs2.size(); k++) {
+                    if (s2st[k]) { err_out = depth_status_message(kf2.id, obs2[k], &uv2[2 * k], s2st[k]); return DEFTRI_E_ARG; }
+                    dm[2 * k + 1] = d2[k];
+                }
+            }
             Scratch sc;
             const int32_t *d_ij = sc.put(ij);
             const double *d_p1 = sc.put(v1), *d_p2 = sc.put(v2), *d_Rt = sc.put(std::vector<double>(Rt, Rt + 12));

@@ -122,6 +122,7 @@ struct deftri_ctx {
     // map-level graph (deftri_arap_build_graph)
     GraphResult graph;
     std::unique_ptr<GraphDevice> gdev;      // computeR on this context's device (graph_dev.hip)
+    DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
     // speculative lambda lanes (see Lane)
     int analytic_jac = 0;                   // deftri_arap_optimization: 0 g2o numeric (reference), 1 analytic
     bool prof_analytic = false;             // deftri_profile_trial linearizes like the last solve_lm
@@ -1091,6 +1092,7 @@ int deftri_ctx_create(int32_t device, deftri_ctx **out) {
         deftri_ctx_destroy(ctx);
         return DEFTRI_E_HIP;
     }
+    ctx->images.bind(device, ctx->st);
     LiveCtx::add(ctx);
     *out = ctx;
     return 0;
@@ -1103,6 +1105,7 @@ int deftri_ctx_destroy(deftri_ctx *ctx) {
     hipSetDevice(ctx->device);
     free_device(ctx);
     ctx->gdev.reset();
+    { std::string e; ctx->images.set(0, nullptr, e); }
     delete ctx->sp_tr;
     ctx->sp_tr = nullptr;
     if (ctx->comm) ncclCommDestroy(ctx->comm);
@@ -1500,6 +1503,8 @@ int64_t deftri_sizeof(int32_t which) {
         case 8: return (int64_t)sizeof(deftri_deformation_params);
         case 9: return (int64_t)sizeof(deftri_deformation_report);
         case 10: return (int64_t)sizeof(deftri_deformation_eval);
+        case 11: return (int64_t)sizeof(deftri_depth_image);
+        case 12: return (int64_t)sizeof(deftri_real_abs_errors);
         default: return -1;
     }
 }
@@ -2264,10 +2269,50 @@ int deftri_arap_build_graph(deftri_ctx *ctx, const deftri_map *map, double rep_w
                             float depth_error, const deftri_problem_desc **desc_out) {
     if (!ctx || !map || !desc_out) return DEFTRI_E_ARG;
     std::string err;
-    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx)))
-        return fail(ctx, DEFTRI_E_GRAPH, err);
+    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images))
+        return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     *desc_out = &ctx->graph.desc;
     return 0;
+}
+
+// ---- keyframe depth images (depth_image.hip) ----
+int deftri_set_depth_images(deftri_ctx *ctx, int32_t n, const deftri_depth_image *images) {
+    if (!ctx) return DEFTRI_E_ARG;
+    std::string err;
+    const int rc = ctx->images.set(n, images, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_depth_measure(deftri_ctx *ctx, int64_t kf_id, int32_t n, const float *uv, int32_t scaled, double *depth,
+                         uint8_t *status) {
+    if (!ctx) return DEFTRI_E_ARG;
+    std::string err;
+    const int rc = ctx->images.measure(kf_id, n, uv, scaled, depth, status, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_depth_image_stats(const deftri_ctx *ctx, int64_t *uploads, int64_t *samplings) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (uploads) *uploads = ctx->images.uploads;
+    if (samplings) *samplings = ctx->images.samplings;
+    return 0;
+}
+
+int deftri_measure_real_absolute_map_errors(deftri_ctx *ctx, const deftri_map *map, deftri_real_abs_errors *out) {
+    if (!ctx || !map || !out) return DEFTRI_E_ARG;
+    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
+    std::string err;
+    const int rc = measure_real_absolute(ctx->images, ctx->device, ctx->st, *map, out, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_measure_relative_map_errors_images(deftri_ctx *ctx, const deftri_map *map, deftri_rel_errors *out,
+                                              int32_t max_pairs, int32_t *n_pairs) {
+    if (!ctx || !map || !n_pairs || map->n_keyframes < 0 || (max_pairs > 0 && !out)) return DEFTRI_E_ARG;
+    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
+    std::string err;
+    const int rc = measure_relative(&ctx->images, ctx->device, ctx->st, *map, out, max_pairs, n_pairs, err);
+    return rc ? fail(ctx, rc, err.empty() ? "relative map errors failed" : err) : 0;
 }
 
 int deftri_graph_stats(const deftri_ctx *ctx, int64_t *memo_hits, int64_t *struct_hits, double *ms_last) {
@@ -2303,8 +2348,8 @@ int deftri_arap_optimization(deftri_ctx *ctx, deftri_map *map, double rep_weight
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
     };
     std::string err;
-    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx)))
-        return fail(ctx, DEFTRI_E_GRAPH, err);
+    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images))
+        return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     const double ms_graph = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     int rc = deftri_problem_upload(ctx, &ctx->graph.desc);

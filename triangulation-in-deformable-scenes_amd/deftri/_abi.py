@@ -137,6 +137,16 @@ class RelErrorsC(C.Structure):
                 ("global_t_error", f64), ("area", f64), ("valid_pairs", i64), ("n_matches", i64)]
 
 
+class DepthImageC(C.Structure):
+    _fields_ = [("kf_id", i64), ("rows", i32), ("cols", i32), ("pixels", P(f32)), ("image_depth_scale", f64),
+                ("ph", f32 * 4)]
+
+
+class RealAbsErrorsC(C.Structure):
+    _fields_ = [("average_movement", f64), ("average_error", f64), ("rmse", f64), ("average_up_to_scale_error", f64),
+                ("point_count", i64), ("n_points", i64), ("scale1", f64), ("scale2", f64)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

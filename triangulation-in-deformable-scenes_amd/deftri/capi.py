@@ -107,6 +107,13 @@ def load():
         "deftri_measure_relative_map_errors": (C.c_int, [C.c_int32, P(_abi.MapC), P(_abi.RelErrorsC), C.c_int32,
                                                          P(C.c_int32)]),
         "deftri_sim_normal_stream": (C.c_int, [C.c_int64, C.c_float, C.c_float, P(C.c_float)]),
+        "deftri_set_depth_images": (C.c_int, [C.c_void_p, C.c_int32, P(_abi.DepthImageC)]),
+        "deftri_depth_measure": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, P(C.c_float), C.c_int32, P(C.c_double),
+                                           P(C.c_uint8)]),
+        "deftri_depth_image_stats": (C.c_int, [C.c_void_p, P(C.c_int64), P(C.c_int64)]),
+        "deftri_measure_real_absolute_map_errors": (C.c_int, [C.c_void_p, P(_abi.MapC), P(_abi.RealAbsErrorsC)]),
+        "deftri_measure_relative_map_errors_images": (C.c_int, [C.c_void_p, P(_abi.MapC), P(_abi.RelErrorsC), C.c_int32,
+                                                                P(C.c_int32)]),
         "deftri_sim_two_view": (C.c_int, [C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                           P(C.c_float), P(C.c_float), C.c_float, C.c_int32, C.c_float, C.c_float,
                                           C.c_float, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
@@ -147,6 +154,8 @@ EXPORTED = [
     "deftri_debug_plan_solve_dist", "deftri_set_plan", "deftri_set_jacobian_storage", "deftri_get_plan_info",
     "deftri_debug_sp_product", "deftri_set_pair_window", "deftri_deformation_optimization", "deftri_global_insert",
     "deftri_debug_nelder_mead", "deftri_keyframe_order",
+    "deftri_set_depth_images", "deftri_depth_measure", "deftri_depth_image_stats",
+    "deftri_measure_real_absolute_map_errors", "deftri_measure_relative_map_errors_images",
 ]
 
 
@@ -170,6 +179,8 @@ class Context:
         self._prob = None
         self._solver = ("pcg", 0.0, 0)
         self.jacobian_mode = False       # deftri_set_jacobian_mode's default: g2o numeric Jacobians
+        self._images_sig = ()            # the depth image set on the context (register_depth_images)
+        self._images_digest = ()
 
     def set_jacobian_mode(self, analytic):
         """The Jacobians of deftri_arap_optimization / _deformation_optimization on this context."""
@@ -370,8 +381,77 @@ class Context:
         return {arr[i].name.decode(): {"launches": arr[i].launches, "ms": arr[i].ms, "flops": arr[i].flops,
                                        "bytes": arr[i].bytes} for i in range(n.value)}
 
+    # keyframe depth images -------------------------------------------------------------------
+    def set_depth_images(self, images):
+        """deftri_set_depth_images: `images` = [(kf id, float32 [rows, cols], image_depth_scale, ph[4])];
+        replaces the context's set ([] clears it)."""
+        arr = (_abi.DepthImageC * max(1, len(images)))()
+        keep = []
+        for n, (kid, im, scale, ph) in enumerate(images):
+            im = np.ascontiguousarray(im, np.float32)
+            keep.append(im)
+            arr[n].kf_id, arr[n].rows, arr[n].cols = int(kid), im.shape[0], im.shape[1]
+            arr[n].pixels = _abi.ptr(im, _abi.f32)
+            arr[n].image_depth_scale = float(scale)
+            arr[n].ph[:] = [float(v) for v in ph]
+        self._images_sig = self._images_digest = None      # unknown until register_depth_images sets them
+        self._check(self.lib.deftri_set_depth_images(self.h, len(images), arr))
+
+    def register_depth_images(self, m):
+        """The depth images of a Map's keyframes on the context, before a map-level call: sent only
+        when the set changed (the same arrays, or other arrays with the same content — the clones a
+        worker process receives)."""
+        images = getattr(m, "depth_images", None)                # sim.ArrayMap (simulated scenes) carries none
+        kfs = sorted(images() if images else [], key=lambda kf: kf.id)   # a clone iterates its keyframes in another order
+        sig =tuple((kf.id, kf.depth_image.ctypes.data, kf.depth_image.shape, float(kf.image_depth_scale),
+                     tuple(float(v) for v in kf.ph)) for kf in kfs)
+        if sig == self._images_sig:
+            return
+        import zlib
+        digest = tuple((s[0], zlib.crc32(kf.depth_image), zlib.adler32(kf.depth_image)) + s[2:] for s, kf in zip(sig, kfs))
+        if digest != self._images_digest:
+            self.set_depth_images([(kf.id, kf.depth_image, kf.image_depth_scale, kf.ph) for kf in kfs])
+        self._images_sig, self._images_digest = sig, digest
+        self._images_keep = [kf.depth_image for kf in kfs]      # the addresses in `sig` stay theirs
+
+    def depth_measure(self, kf_id, uv, scaled=True):
+        """KeyFrame::getDepthMeasure(x, y, scaled) of keyframe kf_id's image for the pixels uv [n, 2]:
+        (depth [n] float64, NaN where the status is not 0; status [n] uint8 — deftri.h)."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        n = len(uv)
+        depth = np.zeros(n, np.float64); status = np.zeros(n, np.uint8)
+        self._check(self.lib.deftri_depth_measure(self.h, int(kf_id), n, _abi.ptr(uv, _abi.f32), 1 if scaled else 0,
+                                                  _dp(depth), _abi.ptr(status, C.c_uint8)))
+        return depth, status
+
+    def depth_image_stats(self):
+        """(images copied to the context, keyframe samplings) over the context's life."""
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.deftri_depth_image_stats(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def measure_real_absolute(self, m):
+        """deftri_measure_real_absolute_map_errors (Measurements.cc:101-348); figures in mm."""
+        self.register_depth_images(m)
+        mc, keep = m.to_c()
+        out = _abi.RealAbsErrorsC()
+        self._check(self.lib.deftri_measure_real_absolute_map_errors(self.h, C.byref(mc), C.byref(out)))
+        return {k: getattr(out, k) for k, _ in _abi.RealAbsErrorsC._fields_}
+
+    def measure_relative_images(self, m):
+        """deftri_measure_relative_map_errors_images: one record per keyframe pair."""
+        self.register_depth_images(m)
+        mc, keep = m.to_c()
+        K = len(m.keyframes)
+        npair = max(1, K * (K - 1) // 2)
+        out = (_abi.RelErrorsC * npair)()
+        n = C.c_int32()
+        self._check(self.lib.deftri_measure_relative_map_errors_images(self.h, C.byref(mc), out, npair, C.byref(n)))
+        return [{k: getattr(out[i], k) for k, _ in _abi.RelErrorsC._fields_} for i in range(n.value)]
+
     # map-level API -------------------------------------------------------------------------
     def build_graph(self, m, rep_weight, arap_weight, depth_error):
+        self.register_depth_images(m)
         mc, keep = m.to_c()
         out = C.POINTER(_abi.ProblemDesc)()
         self._check(self.lib.deftri_arap_build_graph(self.h, C.byref(mc), float(rep_weight), float(arap_weight),
@@ -422,6 +502,7 @@ class Context:
         """analytic=False (default): g2o numeric ARAP/depth Jacobians, the reference's arithmetic."""
         prev = self.jacobian_mode
         self.set_jacobian_mode(analytic)
+        self.register_depth_images(m)
         mc, keep = m.to_c()
         upd = C.c_double(0.0)
         rep = _abi.Report()
@@ -465,6 +546,7 @@ class Context:
         rep = _abi.DeformationReport()
         rep.evals = C.cast(evals, C.POINTER(_abi.DeformationEval))
         rep.max_evals = max_evals
+        self.register_depth_images(m)
         mc, keep = m.to_c()
         prev = self.jacobian_mode
         self.set_jacobian_mode(False)                  # g2o numeric J (the reference's)

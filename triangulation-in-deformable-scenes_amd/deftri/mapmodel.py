@@ -113,7 +113,8 @@ class MapPoint:
 
 
 class KeyFrame:
-    def __init__(self, kid, pose, kb8, n_slots, inv_sigma2, keypoints=None, octaves=None, depth=None):
+    def __init__(self, kid, pose, kb8, n_slots, inv_sigma2, keypoints=None, octaves=None, depth=None, depth_image=None,
+                 image_depth_scale=1.0, ph=None):
         self.id = int(kid)
         self.pose = pose                              # SE3f, T_cw
         self.kb8 = np.asarray(kb8, dtype=np.float32)
@@ -123,6 +124,19 @@ class KeyFrame:
         self.depth = np.zeros(n_slots, np.float32) if depth is None else np.asarray(depth, np.float32)
         self.map_points = [None] * n_slots
         self.estimated_depth_scale = 1.0               # KeyFrame.h:198 default
+        # real images: depthIm_ (CV_32F, rows x cols), imageDepthScale_ and phcalibration_ (fx fy cx cy).
+        # With an image set the depth measurements come from it (getDepthMeasure(x, y, scaled)) and
+        # `depth` may be None; copies of the keyframe share the image array, as cv::Mat copies do
+        self.ph = np.array([1, 1, 0, 0], np.float32)
+        self.set_depth_image(depth_image, image_depth_scale, ph)
+
+    def set_depth_image(self, image, image_depth_scale=1.0, ph=None):
+        """Frame::setDepthIm + the image's scale and pinhole calibration."""
+        self.depth_image = None if image is None else np.ascontiguousarray(image, np.float32)
+        assert self.depth_image is None or self.depth_image.ndim == 2
+        self.image_depth_scale = float(image_depth_scale)
+        if ph is not None:
+            self.ph = np.asarray(ph, np.float32).reshape(4)
 
     @property
     def n_slots(self):
@@ -244,6 +258,8 @@ class Map:
                 if k == "map_points":
                     get = memo.get
                     d[k] = [None if m is None else (get(id(m)) or copy.deepcopy(m, memo)) for m in v]
+                elif k == "depth_image":
+                    d[k] = v                           # cv::Mat copy: the header is new, the data shared
                 elif isinstance(v, np.ndarray):
                     d[k] = v.copy()
                 elif isinstance(v, (int, float, str)):
@@ -292,7 +308,8 @@ class Map:
                     obs[i] = self.is_map_point_in_keyframe(mp.id, kf.id)
             uv = np.ascontiguousarray(kf.keypoints, np.float32)
             octv = np.ascontiguousarray(kf.octaves, np.int32)
-            dep = np.ascontiguousarray(kf.depth, np.float32)
+            # a keyframe with a depth image may have no per-index depths (deftri_keyframe.depth NULL)
+            dep = None if kf.depth is None else np.ascontiguousarray(kf.depth, np.float32)
             c.point_id, c.point_pos, c.obs_index = _abi.ptr(pid, _abi.i64), _abi.ptr(pos, _abi.f32), _abi.ptr(obs, _abi.i32)
             c.kp_uv, c.kp_octave, c.depth = _abi.ptr(uv, _abi.f32), _abi.ptr(octv, _abi.i32), _abi.ptr(dep, _abi.f32)
             c.n_obs = len(kf.keypoints)
@@ -312,6 +329,10 @@ class Map:
         m.globals = C.cast(glob, C.POINTER(_abi.GlobalEntryC))
         keep["globals"] = glob
         return m, keep
+
+    def depth_images(self):
+        """The keyframes that have a depth image."""
+        return [kf for kf in self.keyframes.values() if getattr(kf, "depth_image", None) is not None]
 
     def from_c(self, m, keep):
         """Write back positions (fp32), depth scales and the global T (reference :967-1007)."""

@@ -97,4 +97,17 @@ def measureRelativeMapErrors(pMap, device=0):
     """Modules/Utils/Measurements.cc:350-518 on the device: per keyframe pair (map order) the
     accumulated "Rel. error", "depthError" and "gloablTError" after that pair."""
     from . import capi
+    images = getattr(pMap, "depth_images", None)
+    if images and images():
+        # real images: the depth measurements of keyframes with a depth image come from the image
+        from .optimization import _ctx
+        return _ctx(device).measure_relative_images(pMap)
     return capi.measure_relative(pMap, device)
+
+
+def measureRealAbsoluteMapErrors(pMap, device=0):
+    """Modules/Utils/Measurements.cc:101-348 on the device, from the keyframes' depth images:
+    {"average_movement", "average_error", "rmse", "average_up_to_scale_error"} in mm (the
+    Experiment.txt figures), "point_count", and for tests "n_points", "scale1", "scale2"."""
+    from .optimization import _ctx
+    return _ctx(device).measure_real_absolute(pMap)

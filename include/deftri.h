@@ -570,6 +570,76 @@ int deftri_triangulate_nrslam(deftri_ctx *ctx, int32_t n, const float *uv1, cons
                               const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w,
                               float min_cos, float *x3d_1, float *x3d_2, uint8_t *valid);
 
+/* ---- every seed the reference defines (useTriangulationMethod, Geometry.cc:216-230) -----------
+   Triangulation.method and Triangulation.seed.location as enums.  The reference's `if` chains map the
+   strings: a method other than "Classic", "ORBSLAM", "DepthMeasurement" is NRSLAM; a location other
+   than "TwoPoints" / "FarPoints" is the in-rays seed (each point on its own ray).
+     NRSLAM  triangulateNRSLAM (:103-153): TwoPoints, FarPoints, in-rays.
+     CLASSIC triangulateClassic (:62-101): TwoPoints, in-rays; FarPoints falls into its else (in-rays).
+             n = svd.matrixV().col(1) of A = M^T (I - t t^T) is computed in closed form: v0 from the 2x2
+             A A^T, n = t x v0 (an fp32 SVD does not resolve col(1)).
+     DEPTH   triangulateDepth (:189-214) is defined only inside reconstructPoints, where the unit rays
+             go straight in.  In the simulated entry its inputs are CameraModel::unproject(x, d), which
+             returns an unset vector (CameraModel.h:128-135, unprojectWithZ commented out):
+             deftri_triangulate returns DEFTRI_E_ARG.
+     ORBSLAM triangulateORBSLAM (:155-186) never writes x3D_1 / x3D_2 and the callers read unset
+             memory: DEFTRI_E_ARG in both entries. */
+#define DEFTRI_TRI_CLASSIC 0
+#define DEFTRI_TRI_NRSLAM  1
+#define DEFTRI_TRI_ORBSLAM 2
+#define DEFTRI_TRI_DEPTH   3
+#define DEFTRI_LOC_INRAYS    0   /* any string other than the two below */
+#define DEFTRI_LOC_TWOPOINTS 1
+#define DEFTRI_LOC_FARPOINTS 2
+
+/* deftri_triangulate_nrslam for any defined (method, location): the same unprojection, isValidParallax
+   test, conventions and outputs; (NRSLAM, FARPOINTS) is bit-identical to it. */
+int deftri_triangulate(deftri_ctx *ctx, int32_t n, int32_t method, int32_t location, const float *uv1,
+                       const float *uv2, const float *kb8_1, const float *kb8_2, const float *T1w,
+                       const float *T2w, float min_cos, float *x3d_1, float *x3d_2, uint8_t *valid);
+
+/* MonocularMapInitializer::reconstructPoints (MonocularMapInitializer.cc:281-395) for n matched pixel
+   pairs (uv2 already gathered through vMatches_), the poses given.  Per correspondence: both world
+   points, cos_parallax (:324-326) and a status, the reference's tests in order, first failure wins:
+     0 kept;  1 a point not finite or isZero() (every |coefficient| <= 1e-5, :315);
+     2 z_1 < 0 or z_1 > depth_limit (:329);  3 checks and squared reprojection error in view 1 > 5.991
+     (:339);  4 the depth test in view 2 (:346);  5 the reprojection test in view 2 (:355).
+   The report restates :370-394 on the host: n_triangulated = 2 * kept, parallax_deg = the degrees of
+   the min(50, kept - 1)-th smallest kept cosine, accepted = that cosine in [0, 1] and n_triangulated >=
+   25 and parallax_deg > min_parallax (the reference passes Triangulation.minCos here, Mapping.cc:60).
+   Nothing kept, or the cosine outside [0, 1] (the reference returns before setting it): parallax_deg 0,
+   accepted 0.  n == 0 returns 0 with a zeroed report. */
+typedef struct deftri_reconstruct_params {
+    int32_t method, location;   /* DEFTRI_TRI_*, DEFTRI_LOC_* */
+    int32_t checks;             /* Triangulation.checks == "true" */
+    float depth_limit;          /* Triangulation.depthLimit */
+    float min_parallax;
+} deftri_reconstruct_params;
+typedef struct deftri_reconstruct_report {
+    int64_t n_triangulated, n_nonfinite, n_depth1, n_err1, n_depth2, n_err2;
+    float parallax_deg;
+    int32_t accepted;
+} deftri_reconstruct_report;
+int deftri_reconstruct_points(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2,
+                              const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w,
+                              const deftri_reconstruct_params *params, float *x3d_1, float *x3d_2,
+                              uint8_t *status, float *cos_parallax, deftri_reconstruct_report *report);
+
+/* The initial estimatedDepthScale_ of two real keyframes (Mapping.cc:183-254) for the n correspondences
+   reconstructPoints kept, from the context's depth images of kf_id_1 / kf_id_2.  keep[i] = 0 where
+   getDepthMeasure(x, y) <= 0 in either image or a pixel is outside (0.1, 1500) in x or y (the
+   reference's literals, :194-200); such a pair gets no MapPoints.  A kept pair whose parallax angle in
+   DEGREES exceeds min_cos — the reference compares degrees with Triangulation.minCos (:220), reproduced
+   as it stands — adds getDepthMeasure(x, y, false) / z_c to its keyframe's fp64 sum; scale = sum /
+   n_points.  The sums are reduced per workgroup on the device and added in workgroup order on the
+   host (no atomics: the same bits every run).  n_points == 0 leaves both scales NaN, the reference's
+   0 / 0.  A pixel whose sampler status is not 0 fails the call with DEFTRI_E_ARG (the message names the
+   keyframe id and the pixel) and leaves every output untouched. */
+int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, int32_t n, const float *uv1,
+                             const float *uv2, const float *x3d_1, const float *x3d_2, const float *kb8_1,
+                             const float *kb8_2, const float *T1w, const float *T2w, float min_cos,
+                             uint8_t *keep, double *scale_1, double *scale_2, int64_t *n_points);
+
 /* Build the flattened graph only (no solve): the arrays are owned by the context and stay
    valid until the next call on it.  Used by the parity tests to compare indexing. */
 /* MapPoint id of every point vertex of the last graph deftri_arap_build_graph built (n = its

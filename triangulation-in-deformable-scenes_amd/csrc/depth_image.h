@@ -35,6 +35,9 @@ class DepthImages {
     // the views of every keyframe of `map` (sampling the keyframes whose keypoints the cache does not
     // hold); valid until the next set() or views()
     int views(const deftri_map &map, std::vector<DepthView> &out, std::string &err);
+    // the resident image of a keyframe on a device context, for kernels that sample it themselves
+    // (k_init_depth_scales); false when the keyframe has no image or the context is host-only
+    bool device_image(int64_t kf_id, const float **pixels, int32_t *rows, int32_t *cols, double *scale);
     int64_t uploads = 0, samplings = 0;
 
  private:

@@ -131,6 +131,13 @@ DepthImages::Image *DepthImages::find(int64_t kf_id) {
     return nullptr;
 }
 
+bool DepthImages::device_image(int64_t kf_id, const float **pixels, int32_t *rows, int32_t *cols, double *scale) {
+    Image *im = find(kf_id);
+    if (!im || !im->dev) return false;
+    *pixels = im->dev; *rows = im->rows; *cols = im->cols; *scale = im->scale;
+    return true;
+}
+
 int DepthImages::set(int32_t n, const deftri_depth_image *images, std::string &err) {
     if (n < 0 || (n > 0 && !images)) { err = "bad depth image list"; return DEFTRI_E_ARG; }
     for (int32_t i = 0; i < n; i++) {

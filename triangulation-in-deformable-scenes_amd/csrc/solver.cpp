@@ -2133,6 +2133,222 @@ int deftri_triangulate_nrslam(deftri_ctx *ctx, int32_t n, const float *uv1, cons
     return 0;
 }
 
+// ---- every defined seed, reconstructPoints, the initial depth scales (triangulate.hip) ----
+}  // extern "C"
+namespace {
+// T1w, T2w, T21 = T2w * T1w.inverse(), T2w.inverse() (3x4 each), formed as deftri_triangulate_nrslam does
+void triangulation_poses(const float *T1w, const float *T2w, float Tp[48]) {
+    auto inverse = [](const float *T, float *Ti) {
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Ti[4 * i + j] = T[4 * j + i];
+        for (int i = 0; i < 3; i++) Ti[4 * i + 3] = -(Ti[4 * i] * T[3] + Ti[4 * i + 1] * T[7] + Ti[4 * i + 2] * T[11]);
+    };
+    float T1i[12];
+    std::memcpy(Tp, T1w, 12 * sizeof(float));
+    std::memcpy(Tp + 12, T2w, 12 * sizeof(float));
+    inverse(T1w, T1i);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++)
+            Tp[24 + 4 * i + j] = T2w[4 * i] * T1i[j] + T2w[4 * i + 1] * T1i[4 + j] + T2w[4 * i + 2] * T1i[8 + j];
+        Tp[24 + 4 * i + 3] = (T2w[4 * i] * T1i[3] + T2w[4 * i + 1] * T1i[7] + T2w[4 * i + 2] * T1i[11]) + T2w[4 * i + 3];
+    }
+    inverse(T2w, Tp + 36);
+}
+
+// "" when the reference defines the variant, else why it does not
+const char *undefined_seed(int32_t method, int32_t location, bool simulated) {
+    if (method != DEFTRI_TRI_CLASSIC && method != DEFTRI_TRI_NRSLAM && method != DEFTRI_TRI_ORBSLAM && method != DEFTRI_TRI_DEPTH)
+        return "unknown triangulation method";
+    if (location != DEFTRI_LOC_INRAYS && location != DEFTRI_LOC_TWOPOINTS && location != DEFTRI_LOC_FARPOINTS)
+        return "unknown seed location";
+    if (method == DEFTRI_TRI_ORBSLAM)
+        return "Triangulation.method ORBSLAM is undefined in the reference: triangulateORBSLAM (Geometry.cc:155-186) never "
+               "writes x3D_1 / x3D_2";
+    if (method == DEFTRI_TRI_DEPTH && simulated)
+        return "Triangulation.method DepthMeasurement is undefined in the simulated entry: its inputs are "
+               "CameraModel::unproject(x, d), an unset vector (CameraModel.h:128-135); it is defined in "
+               "deftri_reconstruct_points (Geometry.cc:189-214)";
+    return "";
+}
+
+// one device allocation carved into 256-byte aligned pieces
+struct DevArena {
+    char *base = nullptr;
+    size_t used = 0, cap = 0;
+    ~DevArena() { if (base) hipFree(base); }
+    static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
+    bool reserve(size_t bytes) { cap = bytes; return hipMalloc(&base, bytes ? bytes : 256) == hipSuccess; }
+    template <typename T> T *take(size_t count) {
+        T *p = (T *)(base + used);
+        used += pad(sizeof(T) * count);
+        return p;
+    }
+};
+
+// the inputs every triangulation kernel reads: the pixel pairs, both calibrations, the four poses
+struct TriInputs {
+    float *uv1, *uv2, *k1, *k2, *T;
+    static size_t bytes(size_t N) { return 2 * DevArena::pad(8 * N) + 2 * DevArena::pad(32) + DevArena::pad(48 * sizeof(float)); }
+    // Tp stays the caller's until the stream is synchronized
+    TriInputs(DevArena &A, size_t N, const float *h_uv1, const float *h_uv2, const float *kb8_1, const float *kb8_2,
+              const float *Tp, hipStream_t st)
+        : uv1(A.take<float>(2 * N)), uv2(A.take<float>(2 * N)), k1(A.take<float>(8)), k2(A.take<float>(8)), T(A.take<float>(48)) {
+        hipMemcpyAsync(uv1, h_uv1, 8 * N, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(uv2, h_uv2, 8 * N, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(k1, kb8_1, 32, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(k2, kb8_2, 32, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(T, Tp, 48 * sizeof(float), hipMemcpyHostToDevice, st);
+    }
+};
+}  // namespace
+extern "C" {
+
+int deftri_triangulate(deftri_ctx *ctx, int32_t n, int32_t method, int32_t location, const float *uv1, const float *uv2,
+                       const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w, float min_cos,
+                       float *x3d_1, float *x3d_2, uint8_t *valid) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !valid)) || !kb8_1 || !kb8_2 || !T1w || !T2w)
+        return fail(ctx, DEFTRI_E_ARG, "triangulate: null array or negative n");
+    const char *why = undefined_seed(method, location, true);
+    if (*why) return fail(ctx, DEFTRI_E_ARG, why);
+    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
+    if (n == 0) return 0;
+    hipSetDevice(ctx->device);
+    float Tp[48];
+    triangulation_poses(T1w, T2w, Tp);
+    const size_t N = (size_t)n;
+    DevArena A;
+    if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + DevArena::pad(N)))
+        return fail(ctx, DEFTRI_E_HIP, "triangulate: allocation failed");
+    const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
+    float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
+    uint8_t *d_v = A.take<uint8_t>(N);
+    if (!launch_triangulate(method, location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, min_cos, d_x1, d_x2, d_v, ctx->st)) {
+        hipStreamSynchronize(ctx->st);
+        return fail(ctx, DEFTRI_E_ARG, "triangulate: no kernel for this (method, location)");
+    }
+    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, ctx->st);
+    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, ctx->st);
+    hipMemcpyAsync(valid, d_v, N, hipMemcpyDeviceToHost, ctx->st);
+    const hipError_t e = hipStreamSynchronize(ctx->st);
+    if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("triangulate: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int deftri_reconstruct_points(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                              const float *kb8_2, const float *T1w, const float *T2w, const deftri_reconstruct_params *params,
+                              float *x3d_1, float *x3d_2, uint8_t *status, float *cos_parallax,
+                              deftri_reconstruct_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !status || !cos_parallax)) || !kb8_1 || !kb8_2 || !T1w ||
+        !T2w || !params || !report)
+        return fail(ctx, DEFTRI_E_ARG, "reconstruct_points: null array or negative n");
+    const char *why = undefined_seed(params->method, params->location, false);
+    if (*why) return fail(ctx, DEFTRI_E_ARG, why);
+    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
+    std::memset(report, 0, sizeof(*report));
+    if (n == 0) return 0;
+    hipSetDevice(ctx->device);
+    float Tp[48];
+    triangulation_poses(T1w, T2w, Tp);
+    const size_t N = (size_t)n;
+    DevArena A;
+    if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + DevArena::pad(N) + DevArena::pad(4 * N)))
+        return fail(ctx, DEFTRI_E_HIP, "reconstruct_points: allocation failed");
+    const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
+    float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
+    uint8_t *d_s = A.take<uint8_t>(N);
+    float *d_c = A.take<float>(N);
+    if (!launch_reconstruct_points(params->method, params->location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, params->depth_limit,
+                                   params->checks ? 1 : 0, d_x1, d_x2, d_s, d_c, ctx->st)) {
+        hipStreamSynchronize(ctx->st);
+        return fail(ctx, DEFTRI_E_ARG, "reconstruct_points: no kernel for this (method, location)");
+    }
+    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, ctx->st);
+    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, ctx->st);
+    hipMemcpyAsync(status, d_s, N, hipMemcpyDeviceToHost, ctx->st);
+    hipMemcpyAsync(cos_parallax, d_c, 4 * N, hipMemcpyDeviceToHost, ctx->st);
+    const hipError_t e = hipStreamSynchronize(ctx->st);
+    if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("reconstruct_points: ") + hipGetErrorString(e));
+    // the acceptance (:370-394) from the copied-back status and cosines
+    std::vector<float> par;
+    int64_t *counters[6] = {nullptr, &report->n_nonfinite, &report->n_depth1, &report->n_err1, &report->n_depth2,
+                            &report->n_err2};
+    for (size_t i = 0; i < N; i++) {
+        if (status[i] == 0) par.push_back(cos_parallax[i]);
+        else if (status[i] <= 5) ++*counters[status[i]];
+    }
+    report->n_triangulated = 2 * (int64_t)par.size();
+    if (par.empty()) return 0;
+    const size_t idx = std::min<size_t>(50, par.size() - 1);
+    std::nth_element(par.begin(), par.begin() + (std::ptrdiff_t)idx, par.end());      // sorted order's element idx
+    const float cosp = par[idx];
+    if (cosp < 0.0f || cosp > 1.0f) return 0;                 // "Parallax must be between 0 and 1": not accepted
+    const float radians = acosf(cosp);
+    const float degrees = (float)((double)radians * (180.0 / M_PI));
+    report->parallax_deg = degrees;
+    report->accepted = (report->n_triangulated >= 25 && degrees > params->min_parallax) ? 1 : 0;
+    return 0;
+}
+
+int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, int32_t n, const float *uv1, const float *uv2,
+                             const float *x3d_1, const float *x3d_2, const float *kb8_1, const float *kb8_2, const float *T1w,
+                             const float *T2w, float min_cos, uint8_t *keep, double *scale_1, double *scale_2,
+                             int64_t *n_points) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !keep)) || !kb8_1 || !kb8_2 || !T1w || !T2w || !scale_1 ||
+        !scale_2 || !n_points)
+        return fail(ctx, DEFTRI_E_ARG, "init_depth_scales: null array or negative n");
+    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
+    hipSetDevice(ctx->device);
+    DepthImageDev im[2];
+    const int64_t ids[2] = {kf_id_1, kf_id_2};
+    for (int c = 0; c < 2; c++)
+        if (!ctx->images.device_image(ids[c], &im[c].pixels, &im[c].rows, &im[c].cols, &im[c].scale))
+            return fail(ctx, DEFTRI_E_ARG, "Depth image is not initialized: keyframe " + std::to_string(ids[c]));
+    const size_t N = (size_t)n, nb = (N + 255) / 256;
+    double sum[3] = {0, 0, 0};
+    std::vector<uint8_t> h_keep(N), h_st(N);
+    if (n > 0) {
+        float Tp[48];
+        triangulation_poses(T1w, T2w, Tp);
+        DevArena A;
+        if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + 2 * DevArena::pad(N) + DevArena::pad(24 * nb)))
+            return fail(ctx, DEFTRI_E_HIP, "init_depth_scales: allocation failed");
+        const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
+        float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
+        uint8_t *d_keep = A.take<uint8_t>(N), *d_st = A.take<uint8_t>(N);
+        double *d_part = A.take<double>(3 * nb);
+        std::vector<double> part(3 * nb);
+        hipMemcpyAsync(d_x1, x3d_1, 12 * N, hipMemcpyHostToDevice, ctx->st);
+        hipMemcpyAsync(d_x2, x3d_2, 12 * N, hipMemcpyHostToDevice, ctx->st);
+        launch_init_depth_scales(n, in.uv1, in.uv2, d_x1, d_x2, in.k1, in.k2, in.T, min_cos, im[0], im[1], d_keep, d_st, d_part,
+                                 ctx->st);
+        hipMemcpyAsync(h_keep.data(), d_keep, N, hipMemcpyDeviceToHost, ctx->st);
+        hipMemcpyAsync(h_st.data(), d_st, N, hipMemcpyDeviceToHost, ctx->st);
+        hipMemcpyAsync(part.data(), d_part, 24 * nb, hipMemcpyDeviceToHost, ctx->st);
+        const hipError_t e = hipStreamSynchronize(ctx->st);
+        if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("init_depth_scales: ") + hipGetErrorString(e));
+        for (size_t i = 0; i < N; i++) {
+            if (!h_st[i]) continue;
+            const int c = (h_st[i] & 15) ? 0 : 1;
+            const float *px = (c ? uv2 : uv1) + 2 * i;
+            char buf[200];
+            std::snprintf(buf, sizeof(buf), "keyframe %lld correspondence %zu: pixel (%g, %g) %s", (long long)ids[c], i,
+                          (double)px[0], (double)px[1],
+                          ((c ? h_st[i] >> 4 : h_st[i] & 15) == 1) ? "is out of range of the depth image"
+                                                                   : "reads outside the depth image");
+            return fail(ctx, DEFTRI_E_ARG, buf);
+        }
+        for (size_t b = 0; b < nb; b++)                        // workgroup order
+            for (int q = 0; q < 3; q++) sum[q] += part[3 * b + q];
+        std::memcpy(keep, h_keep.data(), N);
+    }
+    *n_points = (int64_t)sum[2];
+    *scale_1 = sum[0] / sum[2];                                // n_points == 0: 0 / 0 = NaN, as the reference (:250-251)
+    *scale_2 = sum[1] / sum[2];
+    return 0;
+}
+
 int deftri_download(deftri_ctx *ctx, double *points, double *scales, double *tg) {
     if (!ctx || !ctx->have) return fail(ctx, DEFTRI_E_NOPROBLEM, "no problem uploaded");
     hipSetDevice(ctx->device);

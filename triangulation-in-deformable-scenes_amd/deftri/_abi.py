@@ -147,6 +147,22 @@ class RealAbsErrorsC(C.Structure):
                 ("point_count", i64), ("n_points", i64), ("scale1", f64), ("scale2", f64)]
 
 
+DEFTRI_TRI_CLASSIC, DEFTRI_TRI_NRSLAM, DEFTRI_TRI_ORBSLAM, DEFTRI_TRI_DEPTH = 0, 1, 2, 3
+DEFTRI_LOC_INRAYS, DEFTRI_LOC_TWOPOINTS, DEFTRI_LOC_FARPOINTS = 0, 1, 2
+
+
+class ReconstructParams(C.Structure):
+    _fields_ = [("method", i32), ("location", i32), ("checks", i32), ("depth_limit", f32), ("min_parallax", f32)]
+
+
+class ReconstructReport(C.Structure):
+    _fields_ = [("n_triangulated", i64), ("n_nonfinite", i64), ("n_depth1", i64), ("n_err1", i64), ("n_depth2", i64),
+                ("n_err2", i64), ("parallax_deg", f32), ("accepted", i32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -60,6 +60,17 @@ def load():
         "deftri_triangulate_nrslam": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float),
                                                 P(C.c_float), P(C.c_float), P(C.c_float), C.c_float, P(C.c_float),
                                                 P(C.c_float), P(C.c_uint8)]),
+        "deftri_triangulate": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
+                                         P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), C.c_float, P(C.c_float),
+                                         P(C.c_float), P(C.c_uint8)]),
+        "deftri_reconstruct_points": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float),
+                                                P(C.c_float), P(C.c_float), P(C.c_float), P(_abi.ReconstructParams),
+                                                P(C.c_float), P(C.c_float), P(C.c_uint8), P(C.c_float),
+                                                P(_abi.ReconstructReport)]),
+        "deftri_init_depth_scales": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, P(C.c_float), P(C.c_float),
+                                               P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                               P(C.c_float), C.c_float, P(C.c_uint8), P(C.c_double), P(C.c_double),
+                                               P(C.c_int64)]),
         "deftri_download": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double)]),
         "deftri_reset_state": (C.c_int, [C.c_void_p]),
         "deftri_eval_chi2": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -156,7 +167,27 @@ EXPORTED = [
     "deftri_debug_nelder_mead", "deftri_keyframe_order",
     "deftri_set_depth_images", "deftri_depth_measure", "deftri_depth_image_stats",
     "deftri_measure_real_absolute_map_errors", "deftri_measure_relative_map_errors_images",
+    "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
 ]
+
+
+def trian_method_code(method):
+    """Triangulation.method as useTriangulationMethod's `if` chain reads it (Geometry.cc:220-228): any
+    string other than the three named ones is NRSLAM."""
+    return {"Classic": _abi.DEFTRI_TRI_CLASSIC, "ORBSLAM": _abi.DEFTRI_TRI_ORBSLAM,
+            "DepthMeasurement": _abi.DEFTRI_TRI_DEPTH}.get(method, _abi.DEFTRI_TRI_NRSLAM)
+
+
+def trian_location_code(location):
+    """Triangulation.seed.location as the triangulate* functions read it: any string other than
+    "TwoPoints" / "FarPoints" is the in-rays seed."""
+    return {"TwoPoints": _abi.DEFTRI_LOC_TWOPOINTS, "FarPoints": _abi.DEFTRI_LOC_FARPOINTS}.get(location, _abi.DEFTRI_LOC_INRAYS)
+
+
+def _pose34(T):
+    """Sophus::SE3f::matrix3x4() of an SE3f (R, t): float32 [3, 4]."""
+    return np.ascontiguousarray(np.concatenate([np.asarray(T.R, np.float32), np.asarray(T.t, np.float32)[:, None]], 1),
+                                np.float32)
 
 
 def _dp(a):
@@ -496,6 +527,66 @@ class Context:
                                                       float(min_cos), fp(x1), fp(x2),
                                                       v.ctypes.data_as(C.POINTER(C.c_uint8))))
         return x1, x2, v.astype(bool)
+
+    def triangulate(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, min_cos=0.9998, method="NRSLAM", location="FarPoints"):
+        """triangulate_nrslam for any (Triangulation.method, Triangulation.seed.location) the reference
+        defines (deftri_triangulate); the strings map as the reference's `if` chains do.  "ORBSLAM" and
+        "DepthMeasurement" raise DeftriError (DEFTRI_E_ARG): undefined in the reference (deftri.h)."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
+        n = len(uv1)
+        assert len(uv2) == n
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32); v = np.zeros(n, np.uint8)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self.lib.deftri_triangulate(self.h, n, trian_method_code(method), trian_location_code(location), fp(uv1),
+                                                fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb), float(min_cos), fp(x1), fp(x2),
+                                                v.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return x1, x2, v.astype(bool)
+
+    def reconstruct_points(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, method="NRSLAM", location="FarPoints", depth_limit=0.0,
+                           checks=False, min_parallax=0.0):
+        """MonocularMapInitializer::reconstructPoints for matched pixel pairs on the device
+        (deftri_reconstruct_points).  Returns (x3d_1 [n,3], x3d_2 [n,3], status [n] uint8, cos_parallax
+        [n] float32, report dict)."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
+        n = len(uv1)
+        assert len(uv2) == n
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        prm = _abi.ReconstructParams(method=trian_method_code(method), location=trian_location_code(location),
+                                     checks=1 if checks else 0, depth_limit=float(depth_limit),
+                                     min_parallax=float(min_parallax))
+        rep = _abi.ReconstructReport()
+        x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32)
+        st = np.zeros(n, np.uint8); cosp = np.zeros(n, np.float32)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self.lib.deftri_reconstruct_points(self.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb),
+                                                       C.byref(prm), fp(x1), fp(x2), st.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                       fp(cosp), C.byref(rep)))
+        return x1, x2, st, cosp, rep.as_dict()
+
+    def init_depth_scales(self, kf_id_1, kf_id_2, uv1, uv2, x3d_1, x3d_2, kb8_1, kb8_2, T1w, T2w, min_cos=0.9998,
+                          out=None):
+        """The initial estimatedDepthScale_ of two keyframes whose depth images are on the context
+        (deftri_init_depth_scales, Mapping.cc:183-254).  Returns (keep [n] bool, scale_1, scale_2,
+        n_points); the scales are NaN when n_points == 0.  `out`: a (keep uint8 [n], scales float64 [2],
+        n_points int64 [1]) triple to write into instead of new arrays."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
+        x1, x2 = f(x3d_1).reshape(-1, 3), f(x3d_2).reshape(-1, 3)
+        n = len(uv1)
+        assert len(uv2) == n and len(x1) == n and len(x2) == n
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        keep, sc, npts = out if out is not None else (np.zeros(n, np.uint8), np.zeros(2, np.float64), np.zeros(1, np.int64))
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        s1 = C.cast(sc.ctypes.data, C.POINTER(C.c_double))
+        s2 = C.cast(sc.ctypes.data + 8, C.POINTER(C.c_double))
+        self._check(self.lib.deftri_init_depth_scales(self.h, int(kf_id_1), int(kf_id_2), n, fp(uv1), fp(uv2), fp(x1), fp(x2),
+                                                      fp(k1), fp(k2), fp(Ta), fp(Tb), float(min_cos),
+                                                      keep.ctypes.data_as(C.POINTER(C.c_uint8)), s1, s2,
+                                                      npts.ctypes.data_as(C.POINTER(C.c_int64))))
+        return keep.astype(bool), float(sc[0]), float(sc[1]), int(npts[0])
 
     def arap_optimization(self, m, rep_weight, global_weight, arap_weight, alpha, beta, depth_error,
                           n_iterations, want_update=True, analytic=False):

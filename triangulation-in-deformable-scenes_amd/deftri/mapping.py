@@ -1,0 +1,210 @@
+"""The map producer for two real keyframes: MonocularMapInitializer::reconstructPoints
+(Modules/Mapping/MonocularMapInitializer.cc:281-395) and the map construction with the initial depth
+scales of Mapping::monocularMapInitialization (Modules/Mapping/Mapping.cc:171-254).
+
+  reconstruct_points()            host restatement of reconstructPoints for matched pixel pairs (fp32 as the
+                                  reference, or fp64 for parity bands); the device version is
+                                  capi.Context.reconstruct_points (k_reconstruct_points)
+  init_depth_scales()             host restatement of the depth filter and estimatedDepthScale_ sums
+                                  (Mapping.cc:183-254); the device version is Context.init_depth_scales
+  monocular_map_initialization()  the two device steps, then the Map as Mapping.cc:171-254 builds it
+
+The pose hypothesis (essential matrix and RANSAC, MonocularMapInitializer.cc:90-279) is out of scope:
+the poses are inputs.  Two quirks of the reference are kept as they stand: the current keyframe's
+MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
+the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
+reconstructPoints, which receives minCos as fMinParallax, :60).
+"""
+import numpy as np
+
+from . import sim
+from .mapmodel import Map, MapPoint
+
+CHI2_2DOF = 5.991          # the reference's literal (a double)
+
+
+def _kb8_unproject(kb8, uv, dt):
+    """KannalaBrandt8::unproject (KannalaBrandt8.cc:51-83) in dtype dt."""
+    if dt == np.float32:
+        return sim.kb8_unproject(np.asarray(kb8, np.float32), uv)
+    k = np.asarray(kb8, np.float32).astype(dt)
+    uv = np.asarray(uv, np.float32).astype(dt)
+    px = (uv[:, 0] - k[2]) / k[0]
+    py = (uv[:, 1] - k[3]) / k[1]
+    theta_d = np.sqrt(px * px + py * py)
+    theta = theta_d.copy()
+    for _ in range(10):
+        t2 = theta * theta; t4 = t2 * t2; t6 = t4 * t2; t8 = t4 * t4
+        fix = (theta * (1 + k[4] * t2 + k[5] * t4 + k[6] * t6 + k[7] * t8) - theta_d) / \
+              (1 + 3 * k[4] * t2 + 5 * k[5] * t4 + 7 * k[6] * t6 + 9 * k[7] * t8)
+        theta = theta - fix
+    with np.errstate(invalid="ignore", divide="ignore"):
+        s = np.sin(theta) / theta_d
+    return np.stack([s * px, s * py, np.cos(theta)], 1)
+
+
+def _kb8_project(kb8, pc, dt):
+    """KannalaBrandt8::project (KannalaBrandt8.cc:32-49) in dtype dt."""
+    if dt == np.float32:
+        return sim.kb8_project(np.asarray(kb8, np.float32), pc)
+    k = np.asarray(kb8, np.float32).astype(dt)
+    theta = np.arctan2(np.sqrt(pc[:, 0] * pc[:, 0] + pc[:, 1] * pc[:, 1]), pc[:, 2])
+    psi = np.arctan2(pc[:, 1], pc[:, 0])
+    t2 = theta * theta; t3 = theta * t2; t5 = t3 * t2; t7 = t5 * t2; t9 = t7 * t2
+    r = theta + k[4] * t3 + k[5] * t5 + k[6] * t7 + k[7] * t9
+    return np.stack([k[0] * r * np.cos(psi) + k[2], k[1] * r * np.sin(psi) + k[3]], 1)
+
+
+def world_ray_cosine(r1, r2, T1w, T2w, dt=np.float32):
+    """cosRayParallax of (T1w.inverse().rotationMatrix() * r1).normalized() and the same for view 2
+    (MonocularMapInitializer.cc:324-326, Mapping.cc:214-216)."""
+    R1, R2 = np.asarray(T1w.R, dt), np.asarray(T2w.R, dt)
+    ray1, ray2 = r1 @ R1, r2 @ R2                       # rows of R^T r
+    ray1 = ray1 / np.linalg.norm(ray1, axis=1, keepdims=True)
+    ray2 = ray2 / np.linalg.norm(ray2, axis=1, keepdims=True)
+    return (ray1 * ray2).sum(1) / (np.linalg.norm(ray1, axis=1) * np.linalg.norm(ray2, axis=1))
+
+
+def acceptance(status, cos_parallax, min_parallax):
+    """reconstructPoints' tail (:370-394) from the per-correspondence status and cosines: the report
+    of deftri_reconstruct_points."""
+    status = np.asarray(status)
+    kept = np.sort(np.asarray(cos_parallax, np.float32)[status == 0])
+    rep = {"n_triangulated": 2 * len(kept), "n_nonfinite": int((status == 1).sum()), "n_depth1": int((status == 2).sum()),
+           "n_err1": int((status == 3).sum()), "n_depth2": int((status == 4).sum()), "n_err2": int((status == 5).sum()),
+           "parallax_deg": 0.0, "accepted": 0}
+    if len(kept) == 0:
+        return rep
+    c = kept[min(50, len(kept) - 1)]
+    if c < 0 or c > 1:
+        return rep
+    degrees = np.float32(float(np.arccos(np.float32(c))) * (180.0 / np.pi))
+    rep["parallax_deg"] = float(degrees)
+    rep["accepted"] = int(rep["n_triangulated"] >= 25 and degrees > np.float32(min_parallax))
+    return rep
+
+
+def reconstruct_points(uv1, uv2, kb8_1, kb8_2, T1w, T2w, method="NRSLAM", location="FarPoints", depth_limit=0.0,
+                       checks=False, min_parallax=0.0, dtype=np.float32):
+    """reconstructPoints' loop (:303-367) for matched pixel pairs (uv2 gathered through vMatches_), in
+    `dtype`.  Returns a dict: x3d_1, x3d_2 [n,3], status [n] uint8 (0 kept, 1 not finite / isZero, 2
+    depth in view 1, 3 reprojection in view 1, 4 depth in view 2, 5 reprojection in view 2; first failure
+    wins), cos_parallax [n], report (acceptance()), and the deciding quantities z1, z2, err1, err2."""
+    dt = np.dtype(dtype)
+    uv1 = np.asarray(uv1, np.float32).reshape(-1, 2); uv2 = np.asarray(uv2, np.float32).reshape(-1, 2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r1 = _kb8_unproject(kb8_1, uv1, dt); r2 = _kb8_unproject(kb8_2, uv2, dt)
+        r1 = r1 / np.linalg.norm(r1, axis=1, keepdims=True)
+        r2 = r2 / np.linalg.norm(r2, axis=1, keepdims=True)
+        x1, x2 = sim.triangulate_pair(r1, r2, T1w, T2w, method, location, dtype=dt)
+        R1, t1, R2, t2 = (np.asarray(a, dt) for a in (T1w.R, T1w.t, T2w.R, T2w.t))
+        c1, c2 = x1 @ R1.T + t1, x2 @ R2.T + t2
+        cosp = world_ray_cosine(r1, r2, T1w, T2w, dt)
+        e1 = ((uv1.astype(dt) - _kb8_project(kb8_1, c1, dt)) ** 2).sum(1)
+        e2 = ((uv2.astype(dt) - _kb8_project(kb8_2, c2, dt)) ** 2).sum(1)
+        lim = dt.type(depth_limit)
+        bad = ~(np.isfinite(x1).all(1) & np.isfinite(x2).all(1)) | (np.abs(x1) <= 1e-5).all(1) | (np.abs(x2) <= 1e-5).all(1)
+        tests = [bad, (c1[:, 2] < 0) | (c1[:, 2] > lim), bool(checks) & (e1.astype(np.float64) > CHI2_2DOF),
+                 (c2[:, 2] < 0) | (c2[:, 2] > lim), bool(checks) & (e2.astype(np.float64) > CHI2_2DOF)]
+    status = np.zeros(len(uv1), np.uint8)
+    for code in (5, 4, 3, 2, 1):                         # the earliest failing test wins
+        status[tests[code - 1]] = code
+    return {"x3d_1": x1, "x3d_2": x2, "status": status, "cos_parallax": cosp,
+            "report": acceptance(status, cosp, min_parallax), "z1": c1[:, 2], "z2": c2[:, 2], "err1": e1, "err2": e2}
+
+
+def _host_sampler():
+    """getDepthMeasure through the library's host function (a host-only context)."""
+    from . import capi
+    ctx = capi.Context(-1)
+
+    def sample(kf, uv, scaled):
+        ctx.set_depth_images([(kf.id, kf.depth_image, kf.image_depth_scale, kf.ph)])
+        return ctx.depth_measure(kf.id, uv, scaled)
+    return sample
+
+
+def camera_z_f32(T, x):
+    """(T * x).z in float32, one rounding per operation in the order of the device's xform()."""
+    R, t = np.asarray(T.R, np.float32), np.asarray(T.t, np.float32)
+    x = np.asarray(x, np.float32)
+    return ((R[2, 0] * x[:, 0] + R[2, 1] * x[:, 1]) + R[2, 2] * x[:, 2]) + t[2]
+
+
+def init_depth_scales(kf_ref, kf_cur, uv1, uv2, x3d_1, x3d_2, min_cos, sampler=None):
+    """The depth filter and the initial estimatedDepthScale_ of both keyframes (Mapping.cc:183-254) for
+    the correspondences reconstructPoints kept, on the host with a sequential fp64 sum.  sampler(kf, uv,
+    scaled) -> (depth float64 [n], status uint8 [n]) is getDepthMeasure (default: the library's host
+    function).  Returns (keep [n] bool, scale_1, scale_2, n_points); a pixel with a non-zero sampler
+    status raises ValueError; n_points == 0 gives NaN scales (the reference's 0 / 0)."""
+    sampler = sampler or _host_sampler()
+    uv1 = np.asarray(uv1, np.float32).reshape(-1, 2); uv2 = np.asarray(uv2, np.float32).reshape(-1, 2)
+    d1, s1 = sampler(kf_ref, uv1, True); d2, s2 = sampler(kf_cur, uv2, True)
+    for kf, uv, st in ((kf_ref, uv1, s1), (kf_cur, uv2, s2)):
+        if np.any(st):
+            i = int(np.flatnonzero(st)[0])
+            raise ValueError(f"keyframe {kf.id} correspondence {i}: pixel ({uv[i, 0]:g}, {uv[i, 1]:g}) has depth status {st[i]}")
+    d1u, _ = sampler(kf_ref, uv1, False); d2u, _ = sampler(kf_cur, uv2, False)
+    inside = lambda uv: ~((uv[:, 0].astype(np.float64) <= 0.1) | (uv[:, 0] >= 1500) | (uv[:, 1].astype(np.float64) <= 0.1) |
+                          (uv[:, 1] >= 1500))
+    keep = ~((d1 <= 0.0) | (d2 <= 0.0)) & inside(uv1) & inside(uv2)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r1 = sim.kb8_unproject(kf_ref.kb8, uv1); r2 = sim.kb8_unproject(kf_cur.kb8, uv2)
+        r1 = r1 / np.linalg.norm(r1, axis=1, keepdims=True)
+        r2 = r2 / np.linalg.norm(r2, axis=1, keepdims=True)
+        cosp = world_ray_cosine(r1, r2, kf_ref.pose, kf_cur.pose).astype(np.float32)
+        degrees = (np.arccos(cosp).astype(np.float32).astype(np.float64) * (180.0 / np.pi)).astype(np.float32)
+    use = keep & (degrees > np.float32(min_cos))          # degrees against minCos, as the reference (:220)
+    z1 = camera_z_f32(kf_ref.pose, x3d_1).astype(np.float64)
+    z2 = camera_z_f32(kf_cur.pose, x3d_2).astype(np.float64)
+    scale1 = scale2 = 0.0
+    n_points = 0
+    for i in np.flatnonzero(use):
+        scale1 += d1u[i] / z1[i]
+        scale2 += d2u[i] / z2[i]
+        n_points += 1
+    with np.errstate(invalid="ignore", divide="ignore"):
+        scale1, scale2 = np.float64(scale1) / np.float64(n_points), np.float64(scale2) / np.float64(n_points)
+    return keep, float(scale1), float(scale2), n_points
+
+
+def monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings):
+    """Two real keyframes (poses, keypoints, depth images) and vMatches (matches[i] = the current
+    keyframe's keypoint matched to the reference keyframe's keypoint i, < 0 for none) to the Map
+    arapOptimization expects, as Mapping.cc:171-254: reconstructPoints and the depth-scale step on the
+    device of `ctx`, then both keyframes inserted, one MapPoint pair per kept correspondence with the
+    observations (ref, i) and (cur, matches[i]), both slots at index i (the reference's slot quirk,
+    :208-209), and estimated_depth_scale on both keyframes.  Settings: trian_method, trian_location,
+    depth_limit, trian_checks, min_cos (also reconstructPoints' fMinParallax, Mapping.cc:60).
+    Returns (Map, report); the Map is None when reconstructPoints does not accept the pair (:164-166)."""
+    matches = np.asarray(matches, np.int64)
+    idx = np.flatnonzero(matches >= 0)
+    uv1 = np.ascontiguousarray(kf_ref.keypoints[idx], np.float32)
+    uv2 = np.ascontiguousarray(kf_cur.keypoints[matches[idx]], np.float32)
+    x1, x2, status, _cosp, report = ctx.reconstruct_points(
+        uv1, uv2, kf_ref.kb8, kf_cur.kb8, kf_ref.pose, kf_cur.pose, method=settings.trian_method,
+        location=settings.trian_location, depth_limit=settings.depth_limit, checks=settings.trian_checks,
+        min_parallax=settings.min_cos)
+    if not report["accepted"]:
+        return None, report
+    m = Map()
+    m.insert_keyframe(kf_ref)
+    m.insert_keyframe(kf_cur)
+    ctx.register_depth_images(m)
+    tri = np.flatnonzero(status == 0)
+    keep, scale1, scale2, n_points = ctx.init_depth_scales(kf_ref.id, kf_cur.id, uv1[tri], uv2[tri], x1[tri], x2[tri],
+                                                           kf_ref.kb8, kf_cur.kb8, kf_ref.pose, kf_cur.pose, settings.min_cos)
+    next_id = 0
+    for k in tri[keep]:
+        i = int(idx[k])
+        mp1, mp2 = MapPoint(x1[k], next_id), MapPoint(x2[k], next_id + 1)
+        next_id += 2
+        m.insert_map_point(mp1); m.insert_map_point(mp2)
+        m.add_observation(kf_ref.id, mp1.id, i)
+        m.add_observation(kf_cur.id, mp2.id, int(matches[i]))
+        kf_ref.map_points[i] = mp1
+        kf_cur.map_points[i] = mp2
+    kf_ref.estimated_depth_scale = scale1
+    kf_cur.estimated_depth_scale = scale2
+    report = dict(report, n_scale_points=n_points, n_map_points=next_id)
+    return m, report

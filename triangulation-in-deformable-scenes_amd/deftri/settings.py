@@ -24,7 +24,7 @@ NUMERIC = {
     "Optimization.nlopt.rep.lowerBound": "nlopt_rep_lb", "Optimization.nlopt.rep.upperBound": "nlopt_rep_ub",
     "Optimization.nlopt.global.lowerBound": "nlopt_global_lb", "Optimization.nlopt.global.upperBound": "nlopt_global_ub",
     "Optimization.nlopt.arap.lowerBound": "nlopt_arap_lb", "Optimization.nlopt.arap.upperBound": "nlopt_arap_ub",
-    "Triangulation.minCos": "min_cos",
+    "Triangulation.minCos": "min_cos", "Triangulation.depthLimit": "depth_limit",
 }
 STRINGS = {
     "Optimization.selection": "selection", "Optimization.weightsSelection": "weights_selection",
@@ -61,6 +61,8 @@ class Settings:
                 setattr(self, attr, 0.0)
         for key, attr in STRINGS.items():
             setattr(self, attr, kv.get(key, ""))
+        # Triangulation.checks: true only for the string "true" (Settings.cc:101-108)
+        self.trian_checks = kv.get("Triangulation.checks", "") == "true"
         self.n_scales = int(self.n_scales)
         self.n_optimizations = int(self.n_optimizations)
         self.n_iterations = int(self.n_iterations)

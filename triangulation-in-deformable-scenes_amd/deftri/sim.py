@@ -9,9 +9,10 @@ Recipe, per reference file:
   depth       SLAM::getSimulatedDepthMeasurements SLAM.cc:321-338 (d = z_c * scale + N(0, err/1000))
   keypoints   SLAM::createKeyPoints SLAM.cc:281-319 (KB8 projection + N(0, RepError), rounded to
               `decimals`), octave 0
-  MapPoints   Mapping::triangulateSimulatedMapPoints Mapping.cc:280-349 with
-              triangulateNRSLAM(..., "FarPoints") Geometry.cc:103-153 and isValidParallax
-              Mapping.cc:351-364 (fp32 math)
+  MapPoints   Mapping::triangulateSimulatedMapPoints Mapping.cc:280-349 with the seed of
+              Triangulation.method / seed.location (useTriangulationMethod Geometry.cc:216-230; default
+              triangulateNRSLAM(..., "FarPoints") :103-153) and isValidParallax Mapping.cc:351-364
+              (fp32 math)
   sigma table Frame.cc:61-75 (nScales, scale factor)
 Noise streams: the keypoint and depth noise and the camera poses come from deftri_sim_two_view
 (csrc/sim_host.cpp): libstdc++'s std::default_random_engine (minstd_rand0, seed 1) and
@@ -131,14 +132,129 @@ def triangulate_nrslam_far(xn1, xn2, T1w, T2w):
     return (Ti * p3d1.astype(np.float32)), (Ti * p3d2.astype(np.float32))
 
 
-def triangulate_simulated(kb8_1, kb8_2, uv1, uv2, T1w, T2w, min_cos=0.9998):
-    """Mapping::triangulateSimulatedMapPoints (Mapping.cc:280-349; NRSLAM, FarPoints) with
-    isValidParallax (:351-366), vectorised fp32 host restatement.  The device version is
-    deftri_triangulate_nrslam.  Returns (x3d_1, x3d_2, valid)."""
+UNDEFINED_ORBSLAM = ("Triangulation.method ORBSLAM is undefined in the reference: triangulateORBSLAM "
+                     "(Geometry.cc:155-186) never writes x3D_1 / x3D_2")
+UNDEFINED_SIM_DEPTH = ("Triangulation.method DepthMeasurement is undefined in the simulated entry: its inputs are "
+                       "CameraModel::unproject(x, d), an unset vector (CameraModel.h:128-135)")
+
+
+def seed_method(method):
+    """useTriangulationMethod's `if` chain (Geometry.cc:220-228): an unknown string is NRSLAM."""
+    return method if method in ("Classic", "ORBSLAM", "DepthMeasurement") else "NRSLAM"
+
+
+def seed_location(method, location):
+    """The seed location a triangulate* function takes for the string: anything but "TwoPoints" /
+    "FarPoints" is "InRays", and triangulateClassic has no FarPoints branch (its else is InRays)."""
+    loc = location if location in ("TwoPoints", "FarPoints") else "InRays"
+    return "InRays" if (seed_method(method) == "Classic" and loc == "FarPoints") else loc
+
+
+def _rows(a, b):
+    return (a * b).sum(1)
+
+
+def _unit(a):
+    return a / np.linalg.norm(a, axis=1, keepdims=True)
+
+
+def classic_normal(m0, m1, t21, svd=False):
+    """triangulateClassic's n = svd.matrixV().col(1) of A = M^T (I - t t^T) (Geometry.cc:69-77), per
+    row.  Closed form (the device's): A t = 0, so col(2) = +-t and col(1) = t x v0 with v0 the major
+    right-singular vector, A^T u for the major eigenvector u of the 2x2 A A^T.  svd=True takes numpy's
+    SVD instead (the fp64 cross-check; the sign of n is free)."""
+    dt = m0.dtype
+    t = t21 / np.linalg.norm(t21)
+    c0, c1 = _unit(m0), _unit(m1)
+    a0 = c0 - _rows(c0, t)[:, None] * t
+    a1 = c1 - _rows(c1, t)[:, None] * t
+    if svd:
+        A = np.stack([a0, a1], 1)
+        return np.linalg.svd(A, full_matrices=True)[2][:, 1, :].astype(dt)
+    g00, g01, g11 = _rows(a0, a0), _rows(a0, a1), _rows(a1, a1)
+    hd = dt.type(0.5) * (g00 - g11)
+    lam = dt.type(0.5) * (g00 + g11) + np.sqrt(hd * hd + g01 * g01)
+    first = g00 >= g11
+    ux = np.where(first, lam - g11, g01)
+    uy = np.where(first, g01, lam - g00)
+    ux = np.where((ux == 0) & (uy == 0), dt.type(1), ux)
+    v0 = _unit(ux[:, None] * a0 + uy[:, None] * a1)
+    return _unit(np.cross(t[None, :], v0)).astype(dt)
+
+
+def triangulate_pair(xn1, xn2, T1w, T2w, method="NRSLAM", location="FarPoints", dtype=np.float32, classic_svd=False):
+    """useTriangulationMethod (Geometry.cc:216-230) for rows of ray pairs, in `dtype`: triangulateNRSLAM
+    (:103-153; TwoPoints, FarPoints, InRays), triangulateClassic (:62-101; TwoPoints, InRays, the normal
+    by classic_normal) and triangulateDepth (:189-214; the three locations).  The strings map as the
+    reference's `if` chains do.  Returns the world points (x3d_1, x3d_2)."""
+    meth, loc = seed_method(method), seed_location(method, location)
+    if meth == "ORBSLAM":
+        raise ValueError(UNDEFINED_ORBSLAM)
+    dt = np.dtype(dtype)
+    xn1, xn2 = np.asarray(xn1, dt), np.asarray(xn2, dt)
+    R1, t1, R2, t2 = (np.asarray(a, dt) for a in (T1w.R, T1w.t, T2w.R, T2w.t))
+    R1i, t1i = R1.T, -(R1.T @ t1)
+    R21, t21 = R2 @ R1i, R2 @ t1i + t2
+    R2i, t2i = R2.T, -(R2.T @ t2)
+    if meth == "NRSLAM":
+        f0, f1 = _unit(xn1), _unit(xn2)
+        Rf0 = f0 @ R21.T
+        p = np.cross(Rf0, f1); q = np.cross(Rf0, t21[None, :]); r = np.cross(f1, t21[None, :])
+        pn, qn, rn = (np.linalg.norm(a, axis=1) for a in (p, q, r))
+        point0 = (rn / pn)[:, None] * Rf0
+        point1 = (qn / pn)[:, None] * f1
+        x1 = (qn / (qn + rn))[:, None] * (t21 + (rn / pn)[:, None] * (Rf0 + f1))
+        if loc == "TwoPoints":
+            p1, p2 = x1, x1
+        elif loc == "FarPoints":
+            point0 = t21 + point0
+            p1, p2 = point0 + (point0 - x1), point1 + (point1 - x1)
+        else:
+            p1, p2 = t21 + point0, point1
+    elif meth == "Classic":
+        m0, m1 = xn1 @ R21.T, xn2
+        n = classic_normal(m0, m1, t21, svd=classic_svd)
+        m0_ = m0 - _rows(m0, n)[:, None] * n
+        m1_ = m1 - _rows(m1, n)[:, None] * n
+        z = np.cross(m1_, m0_)
+        zz = _rows(z, z)
+        lam0 = _rows(z, np.cross(t21[None, :], m1_)) / zz
+        lam1 = _rows(z, np.cross(t21[None, :], m0_)) / zz
+        if loc == "TwoPoints":
+            p1 = t21 + lam0[:, None] * m0_
+            p2 = p1
+        else:
+            p1, p2 = t21 + lam0[:, None] * m0, lam1[:, None] * m1
+    else:
+        point0, point1 = xn1 @ R21.T + t21, xn2
+        x1 = (point0 + point1) / dt.type(2)
+        if loc == "TwoPoints":
+            p1, p2 = x1, x1
+        elif loc == "FarPoints":
+            p1, p2 = point0 + (point0 - x1), point1 + (point1 - x1)
+        else:
+            p1, p2 = point0, point1
+    return (p1 @ R2i.T + t2i).astype(dt), (p2 @ R2i.T + t2i).astype(dt)
+
+
+def triangulate_simulated(kb8_1, kb8_2, uv1, uv2, T1w, T2w, min_cos=0.9998, method="NRSLAM", location="FarPoints"):
+    """Mapping::triangulateSimulatedMapPoints (Mapping.cc:280-349) with isValidParallax (:351-366),
+    vectorised fp32 host restatement, for the Triangulation.method / seed.location the reference
+    defines there (NRSLAM and Classic; ORBSLAM and DepthMeasurement raise ValueError).  The device
+    version is deftri_triangulate (deftri_triangulate_nrslam for the default NRSLAM, FarPoints).
+    Returns (x3d_1, x3d_2, valid)."""
+    meth, loc = seed_method(method), seed_location(method, location)
+    if meth == "ORBSLAM":
+        raise ValueError(UNDEFINED_ORBSLAM)
+    if meth == "DepthMeasurement":
+        raise ValueError(UNDEFINED_SIM_DEPTH)
     xn1 = kb8_unproject(kb8_1, uv1); xn2 = kb8_unproject(kb8_2, uv2)
     xn1 = xn1 / np.linalg.norm(xn1, axis=1, keepdims=True)
     xn2 = xn2 / np.linalg.norm(xn2, axis=1, keepdims=True)
-    x3d1, x3d2 = triangulate_nrslam_far(xn1, xn2, T1w, T2w)
+    if (meth, loc) == ("NRSLAM", "FarPoints"):
+        x3d1, x3d2 = triangulate_nrslam_far(xn1, xn2, T1w, T2w)
+    else:
+        x3d1, x3d2 = triangulate_pair(xn1, xn2, T1w, T2w, meth, loc)
     z1 = (T1w * x3d1)[:, 2]; z2 = (T2w * x3d2)[:, 2]
     ray1 = xn1 @ T1w.inverse().R.T; ray2 = xn2 @ T2w.inverse().R.T
     ray1 /= np.linalg.norm(ray1, axis=1, keepdims=True); ray2 /= np.linalg.norm(ray2, axis=1, keepdims=True)
@@ -150,7 +266,8 @@ def triangulate_simulated(kb8_1, kb8_2, uv1, uv2, T1w, T2w, min_cos=0.9998):
 def simulate_two_view(n=120, seed=0, orig=None, moved=None, c1=(-0.10, 0.02, 0.12),
                       c2=(0.14, 0.01, 0.06), kb8=SIM_KB8, rep_error=1.0, decimals=1,
                       depth_error=3.0, depth_scales=(0.4, 1.7), min_cos=0.9998, n_scales=8,
-                      scale_factor=1.2, rigid=0.0025, gaussian=0.0025, scale_scene=False, compact=False):
+                      scale_factor=1.2, rigid=0.0025, gaussian=0.0025, scale_scene=False, compact=False,
+                      trian_method="NRSLAM", trian_location="FarPoints"):
     """The reference's Execution/simulation.cc flow up to deformationOptimization.
 
     scale_scene: for large n the cloud extents grow by sqrt(n/120) (generate_points); this also
@@ -160,6 +277,8 @@ def simulate_two_view(n=120, seed=0, orig=None, moved=None, c1=(-0.10, 0.02, 0.1
       (the reference leaves null slots, which triggers its slot/position index quirk; see
       SURVEY Appendix B.2 — a compacted scene is the same as running the reference on the
       filtered point files).
+    trian_method, trian_location: Triangulation.method / Triangulation.seed.location (Settings.trian_method /
+      .trian_location) — the seed triangulateSimulatedMapPoints puts into the map (triangulate_simulated).
     Returns (Map, ground_truth dict)."""
     if orig is None:
         sc = np.sqrt(n / 120.0) if scale_scene else 1.0
@@ -181,13 +300,14 @@ def simulate_two_view(n=120, seed=0, orig=None, moved=None, c1=(-0.10, 0.02, 0.1
     m = Map()
     m.insert_keyframe(kf0)
     m.insert_keyframe(kf1)
-    x3d1, x3d2, valid = triangulate_simulated(kb8, kb8, uv1, uv2, T1w, T2w, min_cos)
+    x3d1, x3d2, valid = triangulate_simulated(kb8, kb8, uv1, uv2, T1w, T2w, min_cos, trian_method, trian_location)
     if compact and not valid.all():
         keep = np.where(valid)[0]
         return simulate_two_view(n=len(keep), seed=seed, orig=orig[keep], moved=moved[keep], c1=c1, c2=c2,
                                  kb8=kb8, rep_error=rep_error, decimals=decimals, depth_error=depth_error,
                                  depth_scales=depth_scales, min_cos=min_cos, n_scales=n_scales,
-                                 scale_factor=scale_factor, compact=True)
+                                 scale_factor=scale_factor, compact=True, trian_method=trian_method,
+                                 trian_location=trian_location)
     next_id = 0
     for i in range(n):
         if not valid[i]:

@@ -398,7 +398,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
 /* sizeof() of the ABI structs for binding checks: 0 deftri_problem_desc, 1 deftri_lm_params,
    2 deftri_report, 3 deftri_keyframe, 4 deftri_map, 5 deftri_ba_desc, 6 deftri_pixels_error,
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
-   10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors. */
+   10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
+   14 deftri_feature_grid (13 is unassigned and answers -1, like every other index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -639,6 +640,68 @@ int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, 
                              const float *uv2, const float *x3d_1, const float *x3d_2, const float *kb8_1,
                              const float *kb8_2, const float *T1w, const float *T2w, float min_cos,
                              uint8_t *keep, double *scale_1, double *scale_2, int64_t *n_points);
+
+/* ---- from keypoints to correspondences: the two steps in front of reconstructPoints ----------- */
+/* The feature grid of a Frame (Frame.cc:213-250).  Without Camera.k1 the bounds are 0, 0, Camera.cols,
+   Camera.rows (:222-227).  scale_factor: FeatureExtractor.fScaleFactor, n_scales: .nScales
+   (vScaleFactor_[0] = 1, [i] = [i-1] * fScaleFactor in float, :65-70). */
+typedef struct deftri_feature_grid {   /* Frame.cc:213-250 */
+    int32_t cols, rows;                /* FeatureGrid.nGridCols / nGridRows */
+    float min_col, min_row, max_col, max_row;
+    int32_t n_scales; float scale_factor;
+} deftri_feature_grid;
+
+/* searchForInitializaion(refFrame, currFrame, th, windowSizeFactor, vMatches)
+   (Modules/Matching/DescriptorMatching.cc:39-99).  Frame 1 is the reference frame, frame 2 the current
+   one: uv [n*2] keypoints, octave [n], desc [n*32] the 256-bit descriptors.  matches[i] = the current
+   keypoint matched to reference keypoint i, or -1; best_dist / second_dist (each may be NULL) the two
+   smallest Hamming distances among the candidates of i, 255 where there is none (the reference's start
+   values; also for a reference keypoint of octave > 0, which is not searched); *n_matches the
+   reference's return value.  Restated as it stands:
+     - only reference keypoints of octave <= 0 are searched (:56); radius = windowSizeFactor * 1 *
+       getScaleFactor(octave); candidates are getFeaturesInArea(x, y, radius, octave - 1, octave + 1)
+       (Frame.cc:288-323): the cell range from four posInGrid calls that fall back to 0 / size - 1 when
+       they fail, then octave in range and |dx| < radius && |dy| < radius, strict, in float;
+     - posInGrid (Frame.cc:277-286) rounds (half away from zero) to a cell index and a current keypoint is
+       in the grid only if its own posInGrid succeeds (:204-210): one in the last half cell on the right
+       or at the bottom (x >= 1428.75 on 1440 columns and 64 cells) is in no cell, never a candidate;
+     - best and second start at 255, so a distance of 255 or 256 never becomes the best; accepted when
+       bestDist <= th && (float)bestDist < float(secondBestDist) * 0.9 — a tie for best rejects;
+     - nothing makes the matches one-to-one.
+   The result does not depend on the order the candidates are visited in; the device (cell lists as a
+   CSR, one 64-lane wave per reference keypoint) equals the sequential host loop exactly.  A host-only
+   context runs that loop.  n1 == 0 or n2 == 0 returns 0 with every entry -1 and *n_matches 0.
+   DEFTRI_E_ARG with a message: cols or rows <= 0 (or more than 2^24 cells), max <= min, n_scales < 1, an
+   octave outside [0, n_scales) (the reference would index vScaleFactor_ out of range), a null required
+   pointer. */
+int deftri_match_for_initialization(deftri_ctx *ctx, const deftri_feature_grid *grid,
+        int32_t n1, const float *uv1, const int32_t *octave1, const uint8_t *desc1,   /* n1 x 32 */
+        int32_t n2, const float *uv2, const int32_t *octave2, const uint8_t *desc2,
+        int32_t th, float window_size_factor,
+        int32_t *matches /* n1, -1 = none */, int32_t *best_dist, int32_t *second_dist /* may be NULL */,
+        int32_t *n_matches);
+
+/* The vTriangulated mask MonocularMapInitializer::initialize builds with Triangulation.checks
+   (MonocularMapInitializer.cc:93-104) for n matched pixel pairs.  findEssentialWithRANSAC (:119-178)
+   builds the same E = [t]x R of T12 = T1w * T2w^-1 (computeEssentialMatrixFromPose, Geometry.cc:239-256)
+   in each of its 16 iterations (computeE is commented out), so its result is one
+   computeScoreAndInliers (:206-223): per match, in float, r = unproject(uv).normalized() of both views,
+   r1_hat = (E r1).normalized(), err = |float(pi/2) - acos(r1_hat . r2.normalized())|, inlier = err <
+   epipolar_th (Epipolar.th).  *score = the inliers; a score of 0 leaves vBestInliers empty in the
+   reference: nothing is triangulated.  err may be NULL.  T1w, T2w: row-major 3x4.  n < 8 returns
+   DEFTRI_E_ARG: cv::kmeans refuses fewer samples than its 8 clusters and the reference throws.  A
+   host-only context runs the sequential loop of the same functions. */
+int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2,
+        const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w,
+        float epipolar_th, uint8_t *inlier, float *err /* may be NULL */, int32_t *score);
+
+/* TEST ONLY: the cell lists of n keypoints as deftri_match_for_initialization builds them for the current
+   frame (the device's CSR on a device context, Frame::distributeFeatures' grid on a host-only one):
+   cell_start [cols*rows + 1], the keys of cell (col, row) at cell_keys[cell_start[col*rows + row] ..
+   cell_start[col*rows + row + 1]); cell_keys [n], of which the first cell_start[cols*rows] are written.
+   The order inside a cell is not defined on the device. */
+int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n, const float *uv,
+        int32_t *cell_start, int32_t *cell_keys);
 
 /* Build the flattened graph only (no solve): the arrays are owned by the context and stay
    valid until the next call on it.  Used by the parity tests to compare indexing. */

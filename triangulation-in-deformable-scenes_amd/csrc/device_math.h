@@ -189,6 +189,64 @@ __device__ __forceinline__ void kb8_project_jac(const float *k, const float p[3]
     J[5] = -k[1] * fd * p[1] / (r2 + z2);
 }
 
+// ---- fp32 3-vectors and KannalaBrandt8::unproject (host and device) --------------------------
+// The reference's Eigen / Sophus float code, one rounding per operation (triangulate.hip's kernels and
+// matching.hip's epipolar test, whose host loop runs the same functions).  Every function switches
+// contraction off itself: an operation keeps its own setting when it is inlined, and a product from one
+// of these would otherwise fuse with a sum from another.
+struct V3 { float x, y, z; };
+__host__ __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
+__host__ __device__ __forceinline__ V3 add(V3 a, V3 b) {
+#pragma clang fp contract(off)
+    return v3(a.x + b.x, a.y + b.y, a.z + b.z);
+}
+__host__ __device__ __forceinline__ V3 sub(V3 a, V3 b) {
+#pragma clang fp contract(off)
+    return v3(a.x - b.x, a.y - b.y, a.z - b.z);
+}
+__host__ __device__ __forceinline__ V3 scl(float s, V3 a) {
+#pragma clang fp contract(off)
+    return v3(s * a.x, s * a.y, s * a.z);
+}
+__host__ __device__ __forceinline__ float dot(V3 a, V3 b) {
+#pragma clang fp contract(off)
+    return a.x * b.x + a.y * b.y + a.z * b.z;
+}
+__host__ __device__ __forceinline__ float nrm(V3 a) {
+#pragma clang fp contract(off)
+    return sqrtf(dot(a, a));
+}
+__host__ __device__ __forceinline__ V3 cross(V3 a, V3 b) {
+#pragma clang fp contract(off)
+    return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+__host__ __device__ __forceinline__ V3 normalized(V3 a) {
+#pragma clang fp contract(off)
+    const float n = nrm(a);
+    return v3(a.x / n, a.y / n, a.z / n);
+}
+
+// KannalaBrandt8::unproject (KannalaBrandt8.cc:51-83): Newton on theta, 10 steps, stop at |fix| < 1e-6
+__host__ __device__ __forceinline__ V3 kb8_unproject(const float *k, float u, float v) {
+#pragma clang fp contract(off)
+    const float px = (u - k[2]) / k[0], py = (v - k[3]) / k[1];
+    const float theta_d = sqrtf(px * px + py * py);
+    float th = 0.0f;
+    if (theta_d > 1e-8f) {
+        float theta = theta_d;
+        for (int j = 0; j < 10; j++) {
+            const float t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
+            const float k0t2 = k[4] * t2, k1t4 = k[5] * t4, k2t6 = k[6] * t6, k3t8 = k[7] * t8;
+            const float fix = (theta * (1 + k0t2 + k1t4 + k2t6 + k3t8) - theta_d) /
+                              (1 + 3 * k0t2 + 5 * k1t4 + 7 * k2t6 + 9 * k3t8);
+            theta = theta - fix;
+            if (fabsf(fix) < 1e-6f) break;
+        }
+        th = theta;
+    }
+    return v3(sinf(th) * px / theta_d, sinf(th) * py / theta_d, cosf(th));
+}
+
 // ---- keyframe depth image lookup (host and device) ------------------------------------------
 // KeyFrame::getDepthMeasure(x, y, scaled) (KeyFrame.cc:181-202) over Interpolate (Geometry.cc:
 // 607-620), fp32 without contraction as the reference's build.  The status is decided before any

@@ -1,0 +1,500 @@
+// matching.hip — from two frames' keypoints to the correspondences reconstructPoints takes.
+//
+// searchForInitializaion (reference Modules/Matching/DescriptorMatching.cc:39-99): for every reference
+// keypoint of octave <= 0, the current frame's keypoints in a window of its feature grid
+// (Frame::getFeaturesInArea, Frame.cc:288-323, over Frame::posInGrid, :277-286), the two smallest Hamming
+// distances among them (both start at 255), and the acceptance bestDist <= th && (float)bestDist <
+// float(secondBestDist) * 0.9.  (best, second) are the two smallest of a multiset, so the order the
+// candidates are visited in does not change them, and an accepted best is strictly below the second:
+// its index is unique.  The device therefore reduces in any order and equals the sequential loop.
+//   k_grid_cells / k_grid_scan / k_grid_fill   the current frame's cell lists as a CSR
+//   k_match_init                               one 64-lane wave per reference keypoint
+//   k_count_matches                            nMatches
+// posInGrid rounds to the nearest cell index, so a keypoint in the last half cell of the image gets
+// index == size, is in no cell (Frame.cc:204-210) and is never a candidate: kept.
+//
+// The epipolar mask of MonocularMapInitializer::initialize with Triangulation.checks
+// (MonocularMapInitializer.cc:93-104): findEssentialWithRANSAC (:119-178) scores the same E, built from
+// the poses (:160-163), in every iteration, so its result is one computeScoreAndInliers (:206-223):
+//   k_epipolar_inliers                         one thread per match, the score per workgroup
+//
+// Float arithmetic without contraction on both sides; the host loops below are the sequential
+// restatements a host-only context runs and the kernels are tested against.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "dev_arena.h"
+#include "device_math.h"
+#include "matching.h"
+
+namespace deftri {
+
+namespace dev {
+// Frame::initializeGrid / computeImageBoundaries (Frame.cc:213-227)
+struct GridGeom {
+    int cols, rows;
+    float min_col, min_row, width_inv, height_inv;
+};
+struct Kb8 { float k[8]; };
+struct Mat3 { float m[9]; };
+
+inline GridGeom geometry(const deftri_feature_grid &g) {
+    GridGeom G;
+    G.cols = g.cols; G.rows = g.rows;
+    G.min_col = g.min_col; G.min_row = g.min_row;
+    G.width_inv = (float)g.cols / (float)(g.max_col - g.min_col);
+    G.height_inv = (float)g.rows / (float)(g.max_row - g.min_row);
+    return G;
+}
+
+// Frame::posInGrid (Frame.cc:277-286).  The reference converts the rounded float to int before it
+// tests the range; a value no int holds (or a NaN) is outside the grid here as well.
+__host__ __device__ __forceinline__ bool pos_in_grid(const GridGeom &G, float x, float y, int &col, int &row) {
+    const float fc = roundf((x - G.min_col) * G.width_inv);
+    const float fr = roundf((y - G.min_row) * G.height_inv);
+    const bool ok = fc >= 0.0f && fc < (float)G.cols && fr >= 0.0f && fr < (float)G.rows;
+    col = ok ? (int)fc : 0;
+    row = ok ? (int)fr : 0;
+    return ok;
+}
+
+// the cell range of Frame::getFeaturesInArea (Frame.cc:296-307): each of the four calls falls back when
+// it fails, also when it fails through its other coordinate
+__host__ __device__ __forceinline__ void cell_range(const GridGeom &G, float x, float y, float radius, int &cmin, int &rmin,
+                                                    int &cmax, int &rmax) {
+    int dummy;
+    if (!pos_in_grid(G, x - radius, y, cmin, dummy)) cmin = 0;
+    if (!pos_in_grid(G, x, y - radius, dummy, rmin)) rmin = 0;
+    if (!pos_in_grid(G, x + radius, y, cmax, dummy)) cmax = G.cols - 1;
+    if (!pos_in_grid(G, x, y + radius, dummy, rmax)) rmax = G.rows - 1;
+}
+
+// DescriptorMatching.cc:92, the literal expression
+__host__ __device__ __forceinline__ bool accept_match(int best, int second, int th) {
+    return best <= th && (double)(float)best < (double)(float)second * 0.9;
+}
+
+// Eigen's normalized(): the vector itself when its squared norm is not positive
+__host__ __device__ __forceinline__ V3 eigen_normalized(V3 a) {
+    const float z = dot(a, a);
+    if (!(z > 0.0f)) return a;
+    const float n = sqrtf(z);
+    return v3(a.x / n, a.y / n, a.z / n);
+}
+
+// computeScoreAndInliers (:206-223) for one match: |float(pi/2) - acos(r1_hat . r2.normalized())|
+__host__ __device__ __forceinline__ float epipolar_error(const Kb8 &k1, const Kb8 &k2, const Mat3 &E, float u1, float v1, float u2,
+                                                         float v2) {
+    const V3 r1 = normalized(kb8_unproject(k1.k, u1, v1)), r2 = normalized(kb8_unproject(k2.k, u2, v2));   // :79-80
+    const V3 Er = v3(E.m[0] * r1.x + E.m[1] * r1.y + E.m[2] * r1.z, E.m[3] * r1.x + E.m[4] * r1.y + E.m[5] * r1.z,
+                     E.m[6] * r1.x + E.m[7] * r1.y + E.m[8] * r1.z);
+    const V3 r1_hat = eigen_normalized(Er), r2n = eigen_normalized(r2);
+    const float d = r1_hat.x * r2n.x + r1_hat.y * r2n.y + r1_hat.z * r2n.z;
+    return fabsf((float)(M_PI / 2) - acosf(d));
+}
+
+// the cell of every keypoint (c * rows + r, -1 outside the grid) and the cells' sizes
+__global__ void k_grid_cells(int n, const float *__restrict__ uv, GridGeom G, int *__restrict__ cell, int *__restrict__ count) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    int c, r;
+    const bool in = pos_in_grid(G, uv[2 * i], uv[2 * i + 1], c, r);
+    const int id = in ? c * G.rows + r : -1;
+    cell[i] = id;
+    if (in) atomicAdd(&count[id], 1);
+}
+
+// exclusive scan of the cell sizes by one workgroup: start [ncell + 1], cursor [ncell] = start
+__global__ void __launch_bounds__(256) k_grid_scan(int ncell, const int *__restrict__ count, int *__restrict__ start,
+                                                   int *__restrict__ cursor) {
+    __shared__ int sums[256];
+    const long long chunk = ((long long)ncell + 255) / 256;
+    const long long lo = min((long long)threadIdx.x * chunk, (long long)ncell), hi = min(lo + chunk, (long long)ncell);
+    int s = 0;
+    for (long long c = lo; c < hi; c++) s += count[c];
+    sums[threadIdx.x] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int t = 0; t < 256; t++) { const int v = sums[t]; sums[t] = run; run += v; }
+        start[ncell] = run;
+    }
+    __syncthreads();
+    int run = sums[threadIdx.x];
+    for (long long c = lo; c < hi; c++) { start[c] = run; cursor[c] = run; run += count[c]; }
+}
+
+__global__ void k_grid_fill(int n, const int *__restrict__ cell, int *__restrict__ cursor, int *__restrict__ keys) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const int id = cell[i];
+    if (id >= 0) keys[atomicAdd(&cursor[id], 1)] = i;
+}
+
+// (best, second, index) of two candidate sets joined: the two smallest distances of the union, the
+// lower index among equal bests.  Identity (255, 255, -1).
+__device__ __forceinline__ void join_best(int &b, int &s, int &idx, int b2, int s2, int idx2) {
+    const int lo = min(b, b2), hi = max(b, b2);
+    if (b2 < b || (b2 == b && idx2 >= 0 && (idx < 0 || idx2 < idx))) idx = idx2;
+    s = min(hi, min(s, s2));
+    b = lo;
+}
+
+// One wave per reference keypoint (4 per workgroup).  `radius`: windowSizeFactor * 1 * getScaleFactor(0),
+// the only octave searched (:56).  A column of the cell range is one run of cell_keys (cells c * rows +
+// rmin .. rmax are adjacent); the lanes stride over it.
+__global__ void __launch_bounds__(256)
+k_match_init(int n1, const float *__restrict__ uv1, const int *__restrict__ octave1, const uint4 *__restrict__ desc1,
+             const float *__restrict__ uv2, const int *__restrict__ octave2, const uint4 *__restrict__ desc2, GridGeom G,
+             const int *__restrict__ cell_start, const int *__restrict__ cell_keys, float radius, int th,
+             int *__restrict__ matches, int *__restrict__ best_out, int *__restrict__ second_out) {
+    const int lane = threadIdx.x & 63;
+    const int i = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (i >= n1) return;
+    const int oct = octave1[i];
+    int b = 255, s = 255, idx = -1;
+    if (oct <= 0) {                                                    // :56
+        const float x = uv1[2 * i], y = uv1[2 * i + 1];
+        const int min_level = oct - 1, max_level = oct + 1;            // :72
+        int cmin, rmin, cmax, rmax;
+        cell_range(G, x, y, radius, cmin, rmin, cmax, rmax);
+        const uint4 a0 = desc1[2 * (size_t)i], a1 = desc1[2 * (size_t)i + 1];
+        for (int c = cmin; c <= cmax; c++) {
+            if (rmin > rmax) break;
+            const int k0 = cell_start[c * G.rows + rmin], k1 = cell_start[c * G.rows + rmax + 1];
+            for (int k = k0 + lane; k < k1; k += 64) {
+                const int j = cell_keys[k];
+                const int o = octave2[j];
+                if (o < min_level || o > max_level) continue;                       // Frame.cc:315
+                const float dx = uv2[2 * j] - x, dy = uv2[2 * j + 1] - y;
+                if (!(fabsf(dx) < radius && fabsf(dy) < radius)) continue;          // :317
+                const uint4 c0 = desc2[2 * (size_t)j], c1 = desc2[2 * (size_t)j + 1];
+                const unsigned long long w0 = ((unsigned long long)(a0.y ^ c0.y) << 32) | (a0.x ^ c0.x);
+                const unsigned long long w1 = ((unsigned long long)(a0.w ^ c0.w) << 32) | (a0.z ^ c0.z);
+                const unsigned long long w2 = ((unsigned long long)(a1.y ^ c1.y) << 32) | (a1.x ^ c1.x);
+                const unsigned long long w3 = ((unsigned long long)(a1.w ^ c1.w) << 32) | (a1.z ^ c1.z);
+                const int d = __popcll(w0) + __popcll(w1) + __popcll(w2) + __popcll(w3);
+                // DescriptorMatching.cc:82-89; a distance of 255 or 256 changes nothing
+                if (d < b) { s = b; b = d; idx = j; }
+                else {
+                    if (d < s) s = d;
+                    if (d == b && d < 255 && j < idx) idx = j;
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const int b2 = __shfl_xor(b, off, 64), s2 = __shfl_xor(s, off, 64), i2 = __shfl_xor(idx, off, 64);
+            join_best(b, s, idx, b2, s2, i2);
+        }
+    }
+    if (lane == 0) {
+        matches[i] = (oct <= 0 && accept_match(b, s, th)) ? idx : -1;   // :92-95
+        best_out[i] = b;
+        second_out[i] = s;
+    }
+}
+
+__global__ void k_count_matches(int n, const int *__restrict__ matches, int *__restrict__ total) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const unsigned long long m = __ballot(i < n && matches[i] >= 0);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(total, __popcll(m));
+}
+
+// part [gridDim.x]: the inliers of each workgroup (a ballot per wave, then the four waves); the host
+// adds them in workgroup order
+__global__ void __launch_bounds__(256)
+k_epipolar_inliers(int n, const float *__restrict__ uv1, const float *__restrict__ uv2, Kb8 k1, Kb8 k2, Mat3 E, float th,
+                   uint8_t *__restrict__ inlier, float *__restrict__ err, int *__restrict__ part) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    bool in = false;
+    if (i < n) {
+        const float e = epipolar_error(k1, k2, E, uv1[2 * i], uv1[2 * i + 1], uv2[2 * i], uv2[2 * i + 1]);
+        in = e < th;                                                   // :211
+        inlier[i] = in ? 1 : 0;
+        err[i] = e;
+    }
+    __shared__ int red[4];
+    const unsigned long long m = __ballot(in);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = __popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+}  // namespace dev
+
+using namespace dev;
+
+namespace {
+int hip_fail(std::string &err, const char *what, hipError_t e) {
+    err = std::string(what) + ": " + hipGetErrorString(e);
+    return DEFTRI_E_HIP;
+}
+
+// "" for a grid Frame could have built, else what is wrong with it
+std::string grid_error(const deftri_feature_grid &g) {
+    if (g.cols <= 0 || g.rows <= 0) return "FeatureGrid.nGridCols / nGridRows must be positive";
+    if ((int64_t)g.cols * g.rows > ((int64_t)1 << 24)) return "feature grid of more than 2^24 cells";
+    if (!(g.max_col > g.min_col) || !(g.max_row > g.min_row)) return "feature grid bounds: max <= min";
+    if (g.n_scales < 1) return "FeatureExtractor.nScales < 1";
+    return "";
+}
+
+// the reference reads vScaleFactor_[octave] of the keypoint (DescriptorMatching.cc:69)
+bool octaves_ok(const deftri_feature_grid &g, int32_t n, const int32_t *octave, const char *which, std::string &err) {
+    for (int32_t i = 0; i < n; i++)
+        if (octave[i] < 0 || octave[i] >= g.n_scales) {
+            err = std::string("match_for_initialization: ") + which + " keypoint " + std::to_string(i) + " has octave " +
+                  std::to_string(octave[i]) + ", outside [0, nScales = " + std::to_string(g.n_scales) + ")";
+            return false;
+        }
+    return true;
+}
+
+// getScaleFactor(octave) of Frame's table (Frame.cc:65-70): a running float product
+float scale_factor(const deftri_feature_grid &g, int octave) {
+    float s = 1.0f;
+    for (int i = 1; i <= octave; i++) s = s * g.scale_factor;
+    return s;
+}
+
+// cell_start / cell_keys of `uv` on the device (the arrays stay in A); ncell = cols * rows
+void launch_grid(const GridGeom &G, int n, const float *d_uv, int *d_cell, int *d_count, int *d_start, int *d_cursor,
+                 int *d_keys, hipStream_t st) {
+    const int ncell = G.cols * G.rows;
+    hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)ncell, st);
+    hipLaunchKernelGGL(dev::k_grid_cells, dim3((n + 255) / 256), dim3(256), 0, st, n, d_uv, G, d_cell, d_count);
+    hipLaunchKernelGGL(dev::k_grid_scan, dim3(1), dim3(256), 0, st, ncell, d_count, d_start, d_cursor);
+    hipLaunchKernelGGL(dev::k_grid_fill, dim3((n + 255) / 256), dim3(256), 0, st, n, d_cell, d_cursor, d_keys);
+}
+
+// Frame::distributeFeatures' grid (Frame.cc:204-210) on the host: grid[c * rows + r] in keypoint order
+std::vector<std::vector<int32_t>> host_grid(const GridGeom &G, int32_t n, const float *uv) {
+    std::vector<std::vector<int32_t>> grid((size_t)G.cols * G.rows);
+    for (int32_t i = 0; i < n; i++) {
+        int c, r;
+        if (pos_in_grid(G, uv[2 * i], uv[2 * i + 1], c, r)) grid[(size_t)c * G.rows + r].push_back(i);
+    }
+    return grid;
+}
+
+// HammingDistance (DescriptorMatching.cc:21-36) over 8 32-bit words
+int hamming(const uint8_t *a, const uint8_t *b) {
+    int dist = 0;
+    for (int w = 0; w < 8; w++) {
+        uint32_t x, y;
+        std::memcpy(&x, a + 4 * w, 4);
+        std::memcpy(&y, b + 4 * w, 4);
+        dist += __builtin_popcount(x ^ y);
+    }
+    return dist;
+}
+}  // namespace
+
+int feature_grid_cells(int device, hipStream_t st, const deftri_feature_grid &grid, int32_t n, const float *uv,
+                       int32_t *cell_start, int32_t *cell_keys, std::string &err) {
+    const std::string why = grid_error(grid);
+    if (!why.empty()) {
+        err = "feature_grid_cells: " + why;
+        return DEFTRI_E_ARG;
+    }
+    const GridGeom G = geometry(grid);
+    const size_t ncell = (size_t)G.cols * G.rows, N = (size_t)n;
+    if (device < 0 || n == 0) {
+        const auto cells = host_grid(G, n, uv);
+        int32_t run = 0;
+        for (size_t c = 0; c < ncell; c++) {
+            cell_start[c] = run;
+            for (int32_t k : cells[c]) cell_keys[run++] = k;
+        }
+        cell_start[ncell] = run;
+        return 0;
+    }
+    hipSetDevice(device);
+    DevArena A;
+    if (!A.reserve(DevArena::pad(8 * N) + 2 * DevArena::pad(4 * N) + 2 * DevArena::pad(4 * ncell) + DevArena::pad(4 * (ncell + 1)))) {
+        err = "feature_grid_cells: allocation failed";
+        return DEFTRI_E_HIP;
+    }
+    float *d_uv = A.take<float>(2 * N);
+    int *d_cell = A.take<int>(N), *d_keys = A.take<int>(N), *d_count = A.take<int>(ncell), *d_cursor = A.take<int>(ncell);
+    int *d_start = A.take<int>(ncell + 1);
+    hipMemcpyAsync(d_uv, uv, 8 * N, hipMemcpyHostToDevice, st);
+    launch_grid(G, n, d_uv, d_cell, d_count, d_start, d_cursor, d_keys, st);
+    hipMemcpyAsync(cell_start, d_start, 4 * (ncell + 1), hipMemcpyDeviceToHost, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(err, "feature_grid_cells", e);
+    // only the filled part of cell_keys is defined
+    const hipError_t e2 = hipMemcpy(cell_keys, d_keys, 4 * (size_t)cell_start[ncell], hipMemcpyDeviceToHost);
+    if (e2 != hipSuccess) return hip_fail(err, "feature_grid_cells", e2);
+    return 0;
+}
+
+int match_for_initialization(int device, hipStream_t st, const deftri_feature_grid &grid, int32_t n1, const float *uv1,
+                             const int32_t *octave1, const uint8_t *desc1, int32_t n2, const float *uv2,
+                             const int32_t *octave2, const uint8_t *desc2, int32_t th, float window_size_factor,
+                             int32_t *matches, int32_t *best_dist, int32_t *second_dist, int32_t *n_matches,
+                             std::string &err) {
+    const std::string why = grid_error(grid);
+    if (!why.empty()) {
+        err = "match_for_initialization: " + why;
+        return DEFTRI_E_ARG;
+    }
+    if (!octaves_ok(grid, n1, octave1, "reference", err) || !octaves_ok(grid, n2, octave2, "current", err)) return DEFTRI_E_ARG;
+    const GridGeom G = geometry(grid);
+    const float radius = window_size_factor * 1 * scale_factor(grid, 0);   // :69, octave 0 (the only one searched)
+    *n_matches = 0;
+    if (n1 == 0 || n2 == 0) {
+        for (int32_t i = 0; i < n1; i++) {
+            matches[i] = -1;
+            if (best_dist) best_dist[i] = 255;
+            if (second_dist) second_dist[i] = 255;
+        }
+        return 0;
+    }
+    if (device < 0) {
+        const auto cells = host_grid(G, n2, uv2);
+        std::vector<int32_t> to_check;
+        int nm = 0;
+        for (int32_t i = 0; i < n1; i++) {
+            matches[i] = -1;                                           // :40
+            if (best_dist) best_dist[i] = 255;
+            if (second_dist) second_dist[i] = 255;
+            if (octave1[i] > 0) continue;                              // :56
+            const float x = uv1[2 * i], y = uv1[2 * i + 1];
+            const int last_octave = octave1[i];
+            const float rad = window_size_factor * 1 * scale_factor(grid, last_octave);
+            // getFeaturesInArea(x, y, rad, last_octave - 1, last_octave + 1) (Frame.cc:288-323)
+            to_check.clear();
+            int cmin, rmin, cmax, rmax;
+            cell_range(G, x, y, rad, cmin, rmin, cmax, rmax);
+            for (int c = cmin; c <= cmax; c++)
+                for (int r = rmin; r <= rmax; r++)
+                    for (int32_t key : cells[(size_t)c * G.rows + r]) {
+                        const int o = octave2[key];
+                        if (o >= last_octave - 1 && o <= last_octave + 1) {
+                            const float px = uv2[2 * key] - x, py = uv2[2 * key + 1] - y;
+                            if (fabsf(px) < rad && fabsf(py) < rad) to_check.push_back(key);
+                        }
+                    }
+            int best = 255, second = 255;                              // :76-90
+            int32_t best_idx = -1;
+            for (int32_t j : to_check) {
+                const int dist = hamming(desc1 + 32 * (size_t)i, desc2 + 32 * (size_t)j);
+                if (dist < best) {
+                    second = best;
+                    best = dist;
+                    best_idx = j;
+                } else if (dist < second) {
+                    second = dist;
+                }
+            }
+            if (accept_match(best, second, th)) {                      // :92-95
+                matches[i] = best_idx;
+                nm++;
+            }
+            if (best_dist) best_dist[i] = best;
+            if (second_dist) second_dist[i] = second;
+        }
+        *n_matches = nm;
+        return 0;
+    }
+    hipSetDevice(device);
+    const size_t N1 = (size_t)n1, N2 = (size_t)n2, ncell = (size_t)G.cols * G.rows;
+    DevArena A;
+    const size_t bytes = DevArena::pad(8 * N1) + DevArena::pad(4 * N1) + DevArena::pad(32 * N1) + DevArena::pad(8 * N2) + DevArena::pad(4 * N2) +
+                         DevArena::pad(32 * N2) + 2 * DevArena::pad(4 * N2) + 2 * DevArena::pad(4 * ncell) + DevArena::pad(4 * (ncell + 1)) +
+                         3 * DevArena::pad(4 * N1) + DevArena::pad(4);
+    if (!A.reserve(bytes)) {
+        err = "match_for_initialization: allocation failed";
+        return DEFTRI_E_HIP;
+    }
+    float *d_uv1 = A.take<float>(2 * N1);
+    int *d_oct1 = A.take<int>(N1);
+    uint4 *d_desc1 = A.take<uint4>(2 * N1);
+    float *d_uv2 = A.take<float>(2 * N2);
+    int *d_oct2 = A.take<int>(N2);
+    uint4 *d_desc2 = A.take<uint4>(2 * N2);
+    int *d_cell = A.take<int>(N2), *d_keys = A.take<int>(N2), *d_count = A.take<int>(ncell), *d_cursor = A.take<int>(ncell);
+    int *d_start = A.take<int>(ncell + 1);
+    int *d_match = A.take<int>(N1), *d_best = A.take<int>(N1), *d_second = A.take<int>(N1), *d_total = A.take<int>(1);
+    hipMemcpyAsync(d_uv1, uv1, 8 * N1, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_oct1, octave1, 4 * N1, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_desc1, desc1, 32 * N1, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_uv2, uv2, 8 * N2, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_oct2, octave2, 4 * N2, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_desc2, desc2, 32 * N2, hipMemcpyHostToDevice, st);
+    hipMemsetAsync(d_total, 0, sizeof(int), st);
+    launch_grid(G, n2, d_uv2, d_cell, d_count, d_start, d_cursor, d_keys, st);
+    hipLaunchKernelGGL(dev::k_match_init, dim3((n1 + 3) / 4), dim3(256), 0, st, n1, d_uv1, d_oct1, d_desc1, d_uv2, d_oct2,
+                       d_desc2, G, d_start, d_keys, radius, th, d_match, d_best, d_second);
+    hipLaunchKernelGGL(dev::k_count_matches, dim3((n1 + 255) / 256), dim3(256), 0, st, n1, d_match, d_total);
+    int total = 0;
+    hipMemcpyAsync(matches, d_match, 4 * N1, hipMemcpyDeviceToHost, st);
+    if (best_dist) hipMemcpyAsync(best_dist, d_best, 4 * N1, hipMemcpyDeviceToHost, st);
+    if (second_dist) hipMemcpyAsync(second_dist, d_second, 4 * N1, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&total, d_total, sizeof(int), hipMemcpyDeviceToHost, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(err, "match_for_initialization", e);
+    *n_matches = total;
+    return 0;
+}
+
+int epipolar_inliers(int device, hipStream_t st, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                     const float *kb8_2, const float *T1w, const float *T2w, float epipolar_th, uint8_t *inlier, float *err_out,
+                     int32_t *score, std::string &err) {
+    // T12 = T1w * T2w.inverse() (:162) and E = [t]x R (Geometry.cc:239-256), in float; poses row-major 3x4
+    float T2i[12], R[9], t[3];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T2i[4 * i + j] = T2w[4 * j + i];
+    for (int i = 0; i < 3; i++) T2i[4 * i + 3] = -(T2i[4 * i] * T2w[3] + T2i[4 * i + 1] * T2w[7] + T2i[4 * i + 2] * T2w[11]);
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) R[3 * i + j] = T1w[4 * i] * T2i[j] + T1w[4 * i + 1] * T2i[4 + j] + T1w[4 * i + 2] * T2i[8 + j];
+        t[i] = (T1w[4 * i] * T2i[3] + T1w[4 * i + 1] * T2i[7] + T1w[4 * i + 2] * T2i[11]) + T1w[4 * i + 3];
+    }
+    const float tx[9] = {0.0f, -t[2], t[1], t[2], 0.0f, -t[0], -t[1], t[0], 0.0f};
+    Mat3 E;
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) E.m[3 * i + j] = tx[3 * i] * R[j] + tx[3 * i + 1] * R[3 + j] + tx[3 * i + 2] * R[6 + j];
+    Kb8 k1, k2;
+    std::memcpy(k1.k, kb8_1, sizeof(k1.k));
+    std::memcpy(k2.k, kb8_2, sizeof(k2.k));
+    if (device < 0) {
+        int sc = 0;
+        for (int32_t i = 0; i < n; i++) {
+            const float e = epipolar_error(k1, k2, E, uv1[2 * i], uv1[2 * i + 1], uv2[2 * i], uv2[2 * i + 1]);
+            inlier[i] = e < epipolar_th ? 1 : 0;
+            if (inlier[i]) sc++;
+            if (err_out) err_out[i] = e;
+        }
+        *score = sc;
+        return 0;
+    }
+    hipSetDevice(device);
+    const size_t N = (size_t)n, nb = (N + 255) / 256;
+    DevArena A;
+    if (!A.reserve(2 * DevArena::pad(8 * N) + DevArena::pad(N) + DevArena::pad(4 * N) + DevArena::pad(4 * nb))) {
+        err = "epipolar_inliers: allocation failed";
+        return DEFTRI_E_HIP;
+    }
+    float *d_uv1 = A.take<float>(2 * N), *d_uv2 = A.take<float>(2 * N);
+    uint8_t *d_in = A.take<uint8_t>(N);
+    float *d_err = A.take<float>(N);
+    int *d_part = A.take<int>(nb);
+    std::vector<int> part(nb);
+    hipMemcpyAsync(d_uv1, uv1, 8 * N, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(d_uv2, uv2, 8 * N, hipMemcpyHostToDevice, st);
+    hipLaunchKernelGGL(dev::k_epipolar_inliers, dim3((unsigned)nb), dim3(256), 0, st, n, d_uv1, d_uv2, k1, k2, E, epipolar_th,
+                       d_in, d_err, d_part);
+    hipMemcpyAsync(inlier, d_in, N, hipMemcpyDeviceToHost, st);
+    if (err_out) hipMemcpyAsync(err_out, d_err, 4 * N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(part.data(), d_part, 4 * nb, hipMemcpyDeviceToHost, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return hip_fail(err, "epipolar_inliers", e);
+    int sc = 0;
+    for (size_t b = 0; b < nb; b++) sc += part[b];                     // workgroup order
+    *score = sc;
+    return 0;
+}
+
+}  // namespace deftri

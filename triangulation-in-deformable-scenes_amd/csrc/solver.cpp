@@ -27,8 +27,10 @@
 #include <memory>
 
 #include "../../include/deftri.h"
+#include "dev_arena.h"
 #include "graph_builder.h"
 #include "kernels.h"
+#include "matching.h"
 #include "pcg.h"
 #include "spcg.h"
 #include "exit_guard.h"
@@ -1505,6 +1507,7 @@ int64_t deftri_sizeof(int32_t which) {
         case 10: return (int64_t)sizeof(deftri_deformation_eval);
         case 11: return (int64_t)sizeof(deftri_depth_image);
         case 12: return (int64_t)sizeof(deftri_real_abs_errors);
+        case 14: return (int64_t)sizeof(deftri_feature_grid);
         default: return -1;
     }
 }
@@ -2170,20 +2173,6 @@ const char *undefined_seed(int32_t method, int32_t location, bool simulated) {
     return "";
 }
 
-// one device allocation carved into 256-byte aligned pieces
-struct DevArena {
-    char *base = nullptr;
-    size_t used = 0, cap = 0;
-    ~DevArena() { if (base) hipFree(base); }
-    static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
-    bool reserve(size_t bytes) { cap = bytes; return hipMalloc(&base, bytes ? bytes : 256) == hipSuccess; }
-    template <typename T> T *take(size_t count) {
-        T *p = (T *)(base + used);
-        used += pad(sizeof(T) * count);
-        return p;
-    }
-};
-
 // the inputs every triangulation kernel reads: the pixel pairs, both calibrations, the four poses
 struct TriInputs {
     float *uv1, *uv2, *k1, *k2, *T;
@@ -2347,6 +2336,46 @@ int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, 
     *scale_1 = sum[0] / sum[2];                                // n_points == 0: 0 / 0 = NaN, as the reference (:250-251)
     *scale_2 = sum[1] / sum[2];
     return 0;
+}
+
+// ---- searchForInitializaion and the epipolar inlier mask (matching.hip) ----
+int deftri_match_for_initialization(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n1, const float *uv1,
+                                    const int32_t *octave1, const uint8_t *desc1, int32_t n2, const float *uv2,
+                                    const int32_t *octave2, const uint8_t *desc2, int32_t th, float window_size_factor,
+                                    int32_t *matches, int32_t *best_dist, int32_t *second_dist, int32_t *n_matches) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!grid || !n_matches || n1 < 0 || n2 < 0 || (n1 > 0 && (!uv1 || !octave1 || !desc1 || !matches)) ||
+        (n2 > 0 && (!uv2 || !octave2 || !desc2)))
+        return fail(ctx, DEFTRI_E_ARG, "match_for_initialization: null array or negative size");
+    std::string err;
+    const int rc = match_for_initialization(ctx->device, ctx->st, *grid, n1, uv1, octave1, desc1, n2, uv2, octave2, desc2, th,
+                                            window_size_factor, matches, best_dist, second_dist, n_matches, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                            const float *kb8_2, const float *T1w, const float *T2w, float epipolar_th, uint8_t *inlier,
+                            float *err, int32_t *score) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!uv1 || !uv2 || !kb8_1 || !kb8_2 || !T1w || !T2w || !inlier || !score)
+        return fail(ctx, DEFTRI_E_ARG, "epipolar_inliers: null array");
+    if (n < 8)
+        return fail(ctx, DEFTRI_E_ARG, "epipolar_inliers: fewer than 8 matches: cv::kmeans refuses fewer samples than its 8 "
+                                       "clusters (MonocularMapInitializer.cc:130) and the reference throws");
+    std::string msg;
+    const int rc = epipolar_inliers(ctx->device, ctx->st, n, uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th, inlier, err, score,
+                                    msg);
+    return rc ? fail(ctx, rc, msg) : 0;
+}
+
+int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n, const float *uv,
+                                    int32_t *cell_start, int32_t *cell_keys) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!grid || n < 0 || !cell_start || (n > 0 && (!uv || !cell_keys)))
+        return fail(ctx, DEFTRI_E_ARG, "feature_grid_cells: null array or negative n");
+    std::string err;
+    const int rc = feature_grid_cells(ctx->device, ctx->st, *grid, n, uv, cell_start, cell_keys, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
 int deftri_download(deftri_ctx *ctx, double *points, double *scales, double *tg) {

@@ -25,15 +25,7 @@ namespace deftri {
 namespace dev {
 
 #pragma clang fp contract(off)
-struct V3 { float x, y, z; };
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 add(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
-__device__ __forceinline__ V3 sub(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
-__device__ __forceinline__ V3 scl(float s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ float nrm(V3 a) { return sqrtf(dot(a, a)); }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-__device__ __forceinline__ V3 normalized(V3 a) { const float n = nrm(a); return v3(a.x / n, a.y / n, a.z / n); }
+// V3 and its arithmetic, kb8_unproject: device_math.h
 // T = [R | t] row-major 3x4
 __device__ __forceinline__ V3 rot(const float *T, V3 p) {
     return v3(T[0] * p.x + T[1] * p.y + T[2] * p.z, T[4] * p.x + T[5] * p.y + T[6] * p.z,
@@ -44,26 +36,6 @@ __device__ __forceinline__ V3 rotT(const float *T, V3 p) {     // R^T p
               T[2] * p.x + T[6] * p.y + T[10] * p.z);
 }
 __device__ __forceinline__ V3 xform(const float *T, V3 p) { return add(rot(T, p), v3(T[3], T[7], T[11])); }
-
-// KannalaBrandt8::unproject (KannalaBrandt8.cc:51-83)
-__device__ __forceinline__ V3 kb8_unproject(const float *k, float u, float v) {
-    const float px = (u - k[2]) / k[0], py = (v - k[3]) / k[1];
-    const float theta_d = sqrtf(px * px + py * py);
-    float th = 0.0f;
-    if (theta_d > 1e-8f) {
-        float theta = theta_d;
-        for (int j = 0; j < 10; j++) {
-            const float t2 = theta * theta, t4 = t2 * t2, t6 = t4 * t2, t8 = t4 * t4;
-            const float k0t2 = k[4] * t2, k1t4 = k[5] * t4, k2t6 = k[6] * t6, k3t8 = k[7] * t8;
-            const float fix = (theta * (1 + k0t2 + k1t4 + k2t6 + k3t8) - theta_d) /
-                              (1 + 3 * k0t2 + 5 * k1t4 + 7 * k2t6 + 9 * k3t8);
-            theta = theta - fix;
-            if (fabsf(fix) < 1e-6f) break;
-        }
-        th = theta;
-    }
-    return v3(sinf(th) * px / theta_d, sinf(th) * py / theta_d, cosf(th));
-}
 
 // Tp: T1w, T2w, T21 = T2w T1w^-1, T2w^-1 (3x4 each, formed on the host as Sophus does)
 __global__ void k_triangulate_nrslam(int n, const float *__restrict__ uv1, const float *__restrict__ uv2,

@@ -9,5 +9,7 @@ Layout:
   capi.py         libdeftri.so binding (HIP kernels behind a C-ABI)
   optimization.py reference-API mirror: arapOptimization, deformationOptimization, ...
   settings.py     Settings YAML subset (the solver's keys)
+  mapping.py      the map producer for two real keyframes (monocularMapInitialization)
+  matching.py     host restatements of searchForInitializaion and the epipolar inlier mask
 """
 __all__ = ["_abi", "problem", "mapmodel", "sim", "capi"]

@@ -163,6 +163,11 @@ class ReconstructReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class FeatureGrid(C.Structure):
+    _fields_ = [("cols", i32), ("rows", i32), ("min_col", f32), ("min_row", f32), ("max_col", f32), ("max_row", f32),
+                ("n_scales", i32), ("scale_factor", f32)]
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -71,6 +71,15 @@ def load():
                                                P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                                P(C.c_float), C.c_float, P(C.c_uint8), P(C.c_double), P(C.c_double),
                                                P(C.c_int64)]),
+        "deftri_match_for_initialization": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
+                                                      P(C.c_uint8), C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_uint8),
+                                                      C.c_int32, C.c_float, P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                                      P(C.c_int32)]),
+        "deftri_epipolar_inliers": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                              P(C.c_float), P(C.c_float), C.c_float, P(C.c_uint8), P(C.c_float),
+                                              P(C.c_int32)]),
+        "deftri_debug_feature_grid_cells": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
+                                                      P(C.c_int32)]),
         "deftri_download": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double)]),
         "deftri_reset_state": (C.c_int, [C.c_void_p]),
         "deftri_eval_chi2": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -168,6 +177,7 @@ EXPORTED = [
     "deftri_set_depth_images", "deftri_depth_measure", "deftri_depth_image_stats",
     "deftri_measure_real_absolute_map_errors", "deftri_measure_relative_map_errors_images",
     "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
+    "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
 ]
 
 
@@ -587,6 +597,60 @@ class Context:
                                                       keep.ctypes.data_as(C.POINTER(C.c_uint8)), s1, s2,
                                                       npts.ctypes.data_as(C.POINTER(C.c_int64))))
         return keep.astype(bool), float(sc[0]), float(sc[1]), int(npts[0])
+
+    @staticmethod
+    def _feature_grid(grid):
+        """A deftri_feature_grid from an _abi.FeatureGrid or a dict of its fields (matching.feature_grid)."""
+        return grid if isinstance(grid, _abi.FeatureGrid) else _abi.FeatureGrid(**grid)
+
+    def match_for_initialization(self, grid, uv1, octave1, desc1, uv2, octave2, desc2, th, window_size_factor):
+        """searchForInitializaion (DescriptorMatching.cc:39-99) of reference keypoints 1 against current
+        keypoints 2 on this context: the device, or the sequential host loop on a host-only one
+        (deftri_match_for_initialization).  desc: uint8 [n, 32].  Returns (matches int32 [n1] with -1 for
+        none, best_dist int32 [n1], second_dist int32 [n1], n_matches)."""
+        f = lambda a: np.ascontiguousarray(a, np.float32).reshape(-1, 2)
+        uv1, uv2 = f(uv1), f(uv2)
+        o1, o2 = np.ascontiguousarray(octave1, np.int32).ravel(), np.ascontiguousarray(octave2, np.int32).ravel()
+        d1, d2 = (np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in (desc1, desc2))
+        n1, n2 = len(uv1), len(uv2)
+        assert len(o1) == n1 and len(d1) == n1 and len(o2) == n2 and len(d2) == n2
+        g = self._feature_grid(grid)
+        matches = np.zeros(n1, np.int32); best = np.zeros(n1, np.int32); second = np.zeros(n1, np.int32)
+        nm = C.c_int32(0)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        bp = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint8))
+        self._check(self.lib.deftri_match_for_initialization(self.h, C.byref(g), n1, fp(uv1), ip(o1), bp(d1), n2, fp(uv2),
+                                                             ip(o2), bp(d2), int(th), float(window_size_factor), ip(matches),
+                                                             ip(best), ip(second), C.byref(nm)))
+        return matches, best, second, int(nm.value)
+
+    def epipolar_inliers(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th):
+        """The inlier mask of MonocularMapInitializer::initialize with Triangulation.checks for matched
+        pixel pairs (deftri_epipolar_inliers).  Returns (inlier bool [n], err float32 [n], score)."""
+        f = lambda a: np.ascontiguousarray(a, np.float32)
+        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
+        n = len(uv1)
+        assert len(uv2) == n
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        inl = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
+        score = C.c_int32(0)
+        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+        self._check(self.lib.deftri_epipolar_inliers(self.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb),
+                                                     float(epipolar_th), inl.ctypes.data_as(C.POINTER(C.c_uint8)), fp(err),
+                                                     C.byref(score)))
+        return inl.astype(bool), err, int(score.value)
+
+    def debug_feature_grid_cells(self, grid, uv):
+        """TEST ONLY: the cell lists of keypoints `uv` as the match builds them (deftri_debug_feature_grid_cells).
+        Returns (cell_start int32 [cols*rows + 1], cell_keys int32 [keys in the grid])."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        g = self._feature_grid(grid)
+        start = np.zeros(max(g.cols * g.rows, 0) + 1, np.int32); keys = np.zeros(len(uv), np.int32)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._check(self.lib.deftri_debug_feature_grid_cells(self.h, C.byref(g), len(uv), uv.ctypes.data_as(C.POINTER(C.c_float)),
+                                                             ip(start), ip(keys)))
+        return start, keys[:start[-1]]
 
     def arap_optimization(self, m, rep_weight, global_weight, arap_weight, alpha, beta, depth_error,
                           n_iterations, want_update=True, analytic=False):

@@ -114,7 +114,7 @@ class MapPoint:
 
 class KeyFrame:
     def __init__(self, kid, pose, kb8, n_slots, inv_sigma2, keypoints=None, octaves=None, depth=None, depth_image=None,
-                 image_depth_scale=1.0, ph=None):
+                 image_depth_scale=1.0, ph=None, descriptors=None):
         self.id = int(kid)
         self.pose = pose                              # SE3f, T_cw
         self.kb8 = np.asarray(kb8, dtype=np.float32)
@@ -129,6 +129,8 @@ class KeyFrame:
         # `depth` may be None; copies of the keyframe share the image array, as cv::Mat copies do
         self.ph = np.array([1, 1, 0, 0], np.float32)
         self.set_depth_image(depth_image, image_depth_scale, ph)
+        # Frame::descriptors_: one 256-bit ORB descriptor per keypoint, uint8 [n_slots, 32] (matching only)
+        self.descriptors = None if descriptors is None else np.ascontiguousarray(descriptors, np.uint8).reshape(n_slots, 32)
 
     def set_depth_image(self, image, image_depth_scale=1.0, ph=None):
         """Frame::setDepthIm + the image's scale and pinhole calibration."""

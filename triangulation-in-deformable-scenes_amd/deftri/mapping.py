@@ -1,6 +1,7 @@
-"""The map producer for two real keyframes: MonocularMapInitializer::reconstructPoints
-(Modules/Mapping/MonocularMapInitializer.cc:281-395) and the map construction with the initial depth
-scales of Mapping::monocularMapInitialization (Modules/Mapping/Mapping.cc:171-254).
+"""The map producer for two real keyframes, Mapping::monocularMapInitialization (Modules/Mapping/
+Mapping.cc:131-254): searchForInitializaion and the minMatches gate (:144-156), the epipolar inlier mask of
+MonocularMapInitializer::initialize (MonocularMapInitializer.cc:53-112), reconstructPoints (:281-395) and
+the map construction with the initial depth scales (Mapping.cc:171-254).
 
   reconstruct_points()            host restatement of reconstructPoints for matched pixel pairs (fp32 as the
                                   reference, or fp64 for parity bands); the device version is
@@ -8,16 +9,22 @@ scales of Mapping::monocularMapInitialization (Modules/Mapping/Mapping.cc:171-25
   init_depth_scales()             host restatement of the depth filter and estimatedDepthScale_ sums
                                   (Mapping.cc:183-254); the device version is Context.init_depth_scales
   monocular_map_initialization()  the two device steps, then the Map as Mapping.cc:171-254 builds it
+  monocular_map_initialization_from_features()
+                                  the same from keypoints, octaves and descriptors: the match and the inlier
+                                  mask on the device (matching.py holds their host restatements), then
+                                  monocular_map_initialization
 
-The pose hypothesis (essential matrix and RANSAC, MonocularMapInitializer.cc:90-279) is out of scope:
-the poses are inputs.  Two quirks of the reference are kept as they stand: the current keyframe's
+The poses are inputs, as they are to the reference's RANSAC, which builds E from them in every iteration
+(MonocularMapInitializer.cc:160-163).  Still out of scope: estimating E from the samples (computeE,
+reconstructCameras), FAST and ORB extraction, and the matchers the reference never calls (guidedMatching,
+searchWithProjection, searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
 MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
 the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
 reconstructPoints, which receives minCos as fMinParallax, :60).
 """
 import numpy as np
 
-from . import sim
+from . import matching, sim
 from .mapmodel import Map, MapPoint
 
 CHI2_2DOF = 5.991          # the reference's literal (a double)
@@ -208,3 +215,36 @@ def monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings):
     kf_cur.estimated_depth_scale = scale2
     report = dict(report, n_scale_points=n_points, n_map_points=next_id)
     return m, report
+
+
+def monocular_map_initialization_from_features(ctx, kf_ref, kf_cur, settings):
+    """Mapping::monocularMapInitialization (Mapping.cc:131-254) from two keyframes' keypoints, octaves and
+    descriptors (KeyFrame.descriptors, uint8 [n, 32]), poses and depth images, on the device of `ctx`:
+      searchForInitializaion(ref, cur, Matching.initialization, Matching.initialization.radius) (:144);
+      fewer than Triangulation.minMatches matches: (None, report) (:151-156);
+      with Triangulation.checks the epipolar inlier mask under Epipolar.th (MonocularMapInitializer.cc:93-104)
+      — fewer than 8 matches raise, as cv::kmeans does there; a score of 0 leaves nothing to triangulate:
+      (None, report);
+      then monocular_map_initialization on the surviving matches.
+    Settings with Camera.k1 (OpenCV undistortion of keys and bounds) raise ValueError.  report["n_matches"]
+    is the match count; with checks report["n_inliers"] the score."""
+    grid = matching.feature_grid(settings)
+    if kf_ref.descriptors is None or kf_cur.descriptors is None:
+        raise ValueError("both keyframes need descriptors")
+    matches, _best, _second, n_matches = ctx.match_for_initialization(
+        grid, kf_ref.keypoints, kf_ref.octaves, kf_ref.descriptors, kf_cur.keypoints, kf_cur.octaves, kf_cur.descriptors,
+        settings.matching_init_th, settings.matching_init_radius)
+    report = {"n_matches": n_matches, "accepted": 0}
+    if n_matches < np.float32(settings.min_matches):          # :151, getMinMatches() is a float
+        return None, report
+    matches = matches.astype(np.int64)
+    if settings.trian_checks:
+        idx = np.flatnonzero(matches >= 0)
+        inlier, _err, score = ctx.epipolar_inliers(kf_ref.keypoints[idx], kf_cur.keypoints[matches[idx]], kf_ref.kb8,
+                                                   kf_cur.kb8, kf_ref.pose, kf_cur.pose, settings.epipolar_th)
+        report["n_inliers"] = score
+        if score == 0:                                        # vBestInliers stays empty: nTriangulated == 0
+            return None, report
+        matches[idx[~inlier]] = -1
+    m, rep = monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings)
+    return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})

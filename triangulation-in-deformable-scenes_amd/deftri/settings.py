@@ -25,6 +25,10 @@ NUMERIC = {
     "Optimization.nlopt.global.lowerBound": "nlopt_global_lb", "Optimization.nlopt.global.upperBound": "nlopt_global_ub",
     "Optimization.nlopt.arap.lowerBound": "nlopt_arap_lb", "Optimization.nlopt.arap.upperBound": "nlopt_arap_ub",
     "Triangulation.minCos": "min_cos", "Triangulation.depthLimit": "depth_limit",
+    "FeatureGrid.nGridCols": "grid_cols", "FeatureGrid.nGridRows": "grid_rows",
+    "FeatureExtractor.nFeatures": "n_features", "Epipolar.th": "epipolar_th",
+    "Matching.initialization": "matching_init_th", "Matching.initialization.radius": "matching_init_radius",
+    "Triangulation.minMatches": "min_matches",
 }
 STRINGS = {
     "Optimization.selection": "selection", "Optimization.weightsSelection": "weights_selection",
@@ -63,7 +67,11 @@ class Settings:
             setattr(self, attr, kv.get(key, ""))
         # Triangulation.checks: true only for the string "true" (Settings.cc:101-108)
         self.trian_checks = kv.get("Triangulation.checks", "") == "true"
+        # Camera.k1 present: the reference undistorts keys and image bounds with OpenCV (Settings.cc:54-66)
+        self.has_distortion = "Camera.k1" in kv
         self.n_scales = int(self.n_scales)
+        for attr in ("grid_cols", "grid_rows", "n_features", "matching_init_th"):     # ints in Settings.h
+            setattr(self, attr, int(getattr(self, attr)))
         self.n_optimizations = int(self.n_optimizations)
         self.n_iterations = int(self.n_iterations)
 

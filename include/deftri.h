@@ -594,7 +594,7 @@ int deftri_triangulate_nrslam(deftri_ctx *ctx, int32_t n, const float *uv1, cons
 #define DEFTRI_LOC_FARPOINTS 2
 
 /* deftri_triangulate_nrslam for any defined (method, location): the same unprojection, isValidParallax
-   test, conventions and outputs; (NRSLAM, FARPOINTS) is bit-identical to it. */
+   test, conventions and outputs; deftri_triangulate_nrslam is its (NRSLAM, FARPOINTS). */
 int deftri_triangulate(deftri_ctx *ctx, int32_t n, int32_t method, int32_t location, const float *uv1,
                        const float *uv2, const float *kb8_1, const float *kb8_2, const float *T1w,
                        const float *T2w, float min_cos, float *x3d_1, float *x3d_2, uint8_t *valid);

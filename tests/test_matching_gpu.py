@@ -119,6 +119,20 @@ def test_epipolar_inliers_on_device(gpu_ctx, n):
     assert gpu_ctx.epipolar_inliers(uv1, uv2, k1, k2, T1w, T2w, 0.0)[2] == 0
 
 
+@gpu
+@pytest.mark.parametrize("k", [8, 255, 256])
+def test_epipolar_inliers_prefix_is_bit_identical(gpu_ctx, k):
+    """Every match is one thread's work, independent of n: a call on the first k (8 is the entry's minimum)
+    equals rows [:k] of the call on all 257, across the 256-thread block and the 256-byte padding of the
+    call's device arena pieces."""
+    uv1, uv2, k1, k2, T1w, T2w, _ = ts.scene(257, nans=0)
+    inl, err, _ = gpu_ctx.epipolar_inliers(uv1, uv2, k1, k2, T1w, T2w, EPI_TH)
+    pinl, perr, pscore = gpu_ctx.epipolar_inliers(uv1[:k], uv2[:k], k1, k2, T1w, T2w, EPI_TH)
+    np.testing.assert_array_equal(pinl, inl[:k])
+    np.testing.assert_array_equal(perr.view(np.uint32), err[:k].view(np.uint32))
+    assert pscore == int(inl[:k].sum())
+
+
 # ---- end to end: two keyframes over 64 x 64 depth images, synthetic descriptors ----
 N_REAL = 200
 YAML_TAIL = ("\nCamera.cols: 64\nCamera.rows: 64\nFeatureGrid.nGridCols: 8\nFeatureGrid.nGridRows: 8\n"

@@ -19,7 +19,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT
 from deftri import _abi, capi, mapping, sim
-from deftri.mapmodel import KeyFrame, Map
+from deftri.mapmodel import KeyFrame, Map, SE3f
 from deftri.settings import Settings
 import depth_image_ref as ref
 import triangulation_scene as ts
@@ -42,19 +42,56 @@ def sim_keyframes():
     return out
 
 
+def _same_bits(got, want):
+    for a, b in zip(got, want):
+        assert a.dtype == b.dtype and a.shape == b.shape
+        np.testing.assert_array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
 @gpu
 @pytest.mark.parametrize("n", [120, 257])
-def test_nrslam_far_points_is_bit_identical(gpu_ctx, sim_keyframes, n):
-    """257 = one full 256-thread block and one thread of the next."""
-    kf0, kf1 = sim_keyframes[n]
-    args = (kf0.keypoints, kf1.keypoints, kf0.kb8, kf1.kb8, kf0.pose, kf1.pose)
-    old = gpu_ctx.triangulate_nrslam(*args)
-    new = gpu_ctx.triangulate(*args, method="NRSLAM", location="FarPoints")
-    assert old[2].sum() > 0.9 * n
-    for a, b in zip(old, new):
-        np.testing.assert_array_equal(a, b)
-    for a, b in zip(old, gpu_ctx.triangulate(*args, method="not a method")):     # an unknown method is NRSLAM
-        np.testing.assert_array_equal(a, b)
+def test_nrslam_far_points_is_bit_identical(gpu_ctx, n):
+    """257 = one full 256-thread block and one thread of the next.
+
+    tests/golden/triangulate_nrslam_far.npz holds what deftri_triangulate_nrslam returned on an MI355X at
+    commit 8a97c29, the last one where it ran a kernel of its own (k_triangulate_nrslam), for the two
+    scenes simulate_two_view(n, seed=3), with the exact fp32 inputs it was given.  The C entry, its
+    Python wrapper and (NRSLAM, FarPoints) of deftri_triangulate must all return those bits."""
+    g = np.load(GOLDEN / "triangulate_nrslam_far.npz")
+    uv1, uv2, k1, k2, Ta, Tb = (g[f"{key}_{n}"] for key in ("uv1", "uv2", "kb8_1", "kb8_2", "T1w", "T2w"))
+    want = (g[f"x3d_1_{n}"], g[f"x3d_2_{n}"], g[f"valid_{n}"])
+    assert all(a.dtype == np.float32 for a in (uv1, uv2, k1, k2, Ta, Tb)) and uv1.shape == (n, 2)
+    assert want[2].sum() > 0.9 * n
+    T1w, T2w = SE3f(Ta[:, :3], Ta[:, 3]), SE3f(Tb[:, :3], Tb[:, 3])
+    np.testing.assert_array_equal(capi._pose34(T1w), Ta)
+    args = (uv1, uv2, k1, k2, T1w, T2w)
+    _same_bits(gpu_ctx.triangulate_nrslam(*args), want)
+    _same_bits(gpu_ctx.triangulate(*args, method="NRSLAM", location="FarPoints"), want)
+    _same_bits(gpu_ctx.triangulate(*args, method="not a method"), want)        # an unknown method is NRSLAM
+    # the C entry itself
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32); v = np.zeros(n, np.uint8)
+    rc = gpu_ctx.lib.deftri_triangulate_nrslam(gpu_ctx.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb), 0.9998, fp(x1),
+                                               fp(x2), v.ctypes.data_as(C.POINTER(C.c_uint8)))
+    assert rc == 0
+    _same_bits((x1, x2, v.astype(bool)), want)
+
+
+@gpu
+@pytest.mark.parametrize("k", [1, 255, 256])
+def test_prefix_of_correspondences_is_bit_identical(gpu_ctx, sim_keyframes, k):
+    """Every correspondence is one thread's work, independent of n: a call on the first k equals rows [:k]
+    of the call on all 257.  k straddles the 256-thread block and the 256-byte padding of the uint8 piece
+    of the call's device arena: pieces that overlap or are mis-sized break this."""
+    kf0, kf1 = sim_keyframes[257]
+    rest = (kf0.kb8, kf1.kb8, kf0.pose, kf1.pose)
+    uv1, uv2 = np.asarray(kf0.keypoints, np.float32), np.asarray(kf1.keypoints, np.float32)
+    full = gpu_ctx.triangulate(uv1, uv2, *rest)
+    _same_bits(gpu_ctx.triangulate(uv1[:k], uv2[:k], *rest), [a[:k] for a in full])
+    kw = dict(depth_limit=1e3, checks=True)
+    full = gpu_ctx.reconstruct_points(uv1, uv2, *rest, **kw)[:4]
+    assert (full[2] == 0).any()                               # the points and cosines compared are real ones
+    _same_bits(gpu_ctx.reconstruct_points(uv1[:k], uv2[:k], *rest, **kw)[:4], [a[:k] for a in full])
 
 
 @gpu

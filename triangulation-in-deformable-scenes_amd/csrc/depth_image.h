@@ -21,6 +21,13 @@ struct DepthView {
     const float *ph = nullptr;       // the image's pinhole calibration fx fy cx cy
 };
 
+// a keyframe's depth image resident on the device (DepthImages::device_image)
+struct DepthImageDev {
+    const float *pixels = nullptr;
+    int rows = 0, cols = 0;
+    double scale = 1;
+};
+
 class DepthImages {
  public:
     DepthImages() = default;

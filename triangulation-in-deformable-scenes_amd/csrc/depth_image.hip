@@ -15,9 +15,11 @@
 
 #include "../../include/deftri.h"
 #include "depth_image.h"
+#include "dev_arena.h"
 #include "device_math.h"
 #include "kernels.h"
 #include "measure_scratch.h"
+#include "pose_host.h"
 
 namespace deftri {
 namespace dev {
@@ -181,11 +183,13 @@ int DepthImages::sample(Image &im, int32_t n, const float *uv, int scaled, doubl
         return 0;
     }
     if (hipSetDevice(dev_) != hipSuccess) { err = "hipSetDevice"; return DEFTRI_E_HIP; }
-    Scratch sc;
-    const float *d_uv = sc.put(std::vector<float>(uv, uv + 2 * (size_t)n));
-    double *d_depth = sc.alloc((size_t)n);
-    unsigned char *d_st = (unsigned char *)sc.alloc(((size_t)n + 7) / 8);
-    if (!d_uv || !d_depth || !d_st) { err = "depth sampling: allocation failed"; return DEFTRI_E_HIP; }
+    DevArena A;
+    float *d_uv;
+    double *d_depth;
+    uint8_t *d_st;
+    A.add(&d_uv, 2 * (size_t)n); A.add(&d_depth, (size_t)n); A.add(&d_st, (size_t)n);
+    if (!A.commit()) { err = "depth sampling: allocation failed"; return DEFTRI_E_HIP; }
+    hipMemcpy(d_uv, uv, sizeof(float) * 2 * (size_t)n, hipMemcpyHostToDevice);
     hipLaunchKernelGGL(dev::k_depth_sample, dim3(nblk(n, 256)), dim3(256), 0, st_, (int)n, im.dev, im.rows, im.cols, im.scale,
                        d_uv, scaled, d_depth, d_st);
     if (hipMemcpyAsync(depth, d_depth, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st_) != hipSuccess ||
@@ -246,11 +250,8 @@ namespace {
 // float) and invR * (-t) by the quaternion-vector product; rows of R (9), t (3)
 void se3f_inverse_rows(const float q[4], const float t[3], float out[12]) {
     const float x = -q[0], y = -q[1], z = -q[2], w = q[3];
-    const float tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
-    const float txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    const float R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx,
-                        txz - twy, tyz + twx, 1 - (txx + tyy)};
-    for (int i = 0; i < 9; i++) out[i] = R[i];
+    const float conj[4] = {x, y, z, w};
+    quat_to_rotation(conj, out);
     const float v[3] = {-t[0], -t[1], -t[2]};
     float uv[3] = {y * v[2] - z * v[1], z * v[0] - x * v[2], x * v[1] - y * v[0]};
     for (float &u : uv) u += u;
@@ -324,11 +325,13 @@ int measure_real_absolute(DepthImages &di, int device, hipStream_t st, const def
                 for (int i = 0; i < 3; i++) cams[28 + 7 * c + 4 + i] = t[i];
             }
             n_points += n;
-            Scratch sc;
-            const float *d_uv = sc.put(uv), *d_pw = sc.put(pw), *d_cams = sc.put(cams);
-            const double *d_d = sc.put(d);
-            double *terms = sc.alloc(7 * (size_t)n), *part = sc.alloc(256), *dout = sc.alloc(8);
-            if (!d_uv || !d_pw || !d_cams || !d_d || !terms || !part || !dout) { err = "allocation failed"; return DEFTRI_E_HIP; }
+            DevArena A;
+            float *d_uv, *d_pw, *d_cams;
+            double *d_d, *terms, *part, *dout;
+            A.add(&d_uv, uv.size()); A.add(&d_pw, pw.size()); A.add(&d_cams, cams.size()); A.add(&d_d, d.size());
+            A.add(&terms, 7 * (size_t)n); A.add(&part, 256); A.add(&dout, 8);
+            if (!A.commit()) { err = "allocation failed"; return DEFTRI_E_HIP; }
+            upload(d_uv, uv); upload(d_pw, pw); upload(d_cams, cams); upload(d_d, d);
             double s[7] = {0, 0, 0, 0, 0, 0, 0};
             if (n > 0) {
                 hipLaunchKernelGGL(dev::k_real_abs_terms, dim3(nblk(n, 256)), dim3(256), 0, st, (int)n, d_uv, d_d, d_pw, d_cams, terms);

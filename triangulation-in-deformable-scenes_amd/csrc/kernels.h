@@ -251,32 +251,6 @@ void launch_diag_entries(const DevPlan &L, double *diagv, hipStream_t st);
 void launch_absmax(int64_t n, const double *a, double *part, int nparts, double *out, hipStream_t st);
 void launch_int_to_double(int n, const int *a, double *out, hipStream_t st);
 void launch_maxdiag(const DevPlan &L, double *part, int nparts, double *out, hipStream_t st);
-// calculatePixelsStandDev partial sums (metrics.hip): 8 doubles per 256-match block
-void launch_pixel_partials(int nblk, const int32_t *blk_first, const int32_t *blk_last, const int32_t *blk_pair,
-                           const int32_t *pair_cams, const float *cams, const float *pts, const float *obs,
-                           double *part, hipStream_t st);
-// Mapping::triangulateSimulatedMapPoints, NRSLAM / FarPoints (triangulate.hip)
-void launch_triangulate_nrslam(int n, const float *uv1, const float *uv2, const float *kb1, const float *kb2,
-                               const float *Tp, float min_cos, float *x1, float *x2, uint8_t *valid, hipStream_t st);
-// the same producer for any defined (method, location) (DEFTRI_TRI_*, DEFTRI_LOC_*; k_triangulate), and
-// MonocularMapInitializer::reconstructPoints' loop body (k_reconstruct_points).  false: the reference
-// defines no such variant (nothing launched)
-bool launch_triangulate(int method, int loc, int n, const float *uv1, const float *uv2, const float *kb1, const float *kb2,
-                        const float *Tp, float min_cos, float *x1, float *x2, uint8_t *valid, hipStream_t st);
-bool launch_reconstruct_points(int method, int loc, int n, const float *uv1, const float *uv2, const float *kb1,
-                               const float *kb2, const float *Tp, float depth_limit, int checks, float *x1, float *x2,
-                               uint8_t *status, float *cosp, hipStream_t st);
-// a keyframe's depth image resident on the device (DepthImages::device_image)
-struct DepthImageDev {
-    const float *pixels = nullptr;
-    int rows = 0, cols = 0;
-    double scale = 1;
-};
-// the initial depth scales (Mapping.cc:183-254, k_init_depth_scales): keep [n], pix_status [n], part
-// [3 * ceil(n / 256)] = per workgroup sum 1, sum 2, count
-void launch_init_depth_scales(int n, const float *uv1, const float *uv2, const float *x3d1, const float *x3d2,
-                              const float *kb1, const float *kb2, const float *Tp, float min_cos, const DepthImageDev &im1,
-                              const DepthImageDev &im2, uint8_t *keep, uint8_t *pix_status, double *part, hipStream_t st);
 void launch_hmul(const DevPlan &L, const int64_t *brow_dof, const int64_t *bcol_dof, const double *x, double *y,
                  int64_t n, hipStream_t st);
 

@@ -28,6 +28,7 @@
 #include "dev_arena.h"
 #include "device_math.h"
 #include "matching.h"
+#include "pose_host.h"
 
 namespace deftri {
 
@@ -313,13 +314,14 @@ int feature_grid_cells(int device, hipStream_t st, const deftri_feature_grid &gr
     }
     hipSetDevice(device);
     DevArena A;
-    if (!A.reserve(DevArena::pad(8 * N) + 2 * DevArena::pad(4 * N) + 2 * DevArena::pad(4 * ncell) + DevArena::pad(4 * (ncell + 1)))) {
+    float *d_uv;
+    int *d_cell, *d_keys, *d_count, *d_cursor, *d_start;
+    A.add(&d_uv, 2 * N);
+    A.add(&d_cell, N); A.add(&d_keys, N); A.add(&d_count, ncell); A.add(&d_cursor, ncell); A.add(&d_start, ncell + 1);
+    if (!A.commit()) {
         err = "feature_grid_cells: allocation failed";
         return DEFTRI_E_HIP;
     }
-    float *d_uv = A.take<float>(2 * N);
-    int *d_cell = A.take<int>(N), *d_keys = A.take<int>(N), *d_count = A.take<int>(ncell), *d_cursor = A.take<int>(ncell);
-    int *d_start = A.take<int>(ncell + 1);
     hipMemcpyAsync(d_uv, uv, 8 * N, hipMemcpyHostToDevice, st);
     launch_grid(G, n, d_uv, d_cell, d_count, d_start, d_cursor, d_keys, st);
     hipMemcpyAsync(cell_start, d_start, 4 * (ncell + 1), hipMemcpyDeviceToHost, st);
@@ -403,22 +405,17 @@ int match_for_initialization(int device, hipStream_t st, const deftri_feature_gr
     hipSetDevice(device);
     const size_t N1 = (size_t)n1, N2 = (size_t)n2, ncell = (size_t)G.cols * G.rows;
     DevArena A;
-    const size_t bytes = DevArena::pad(8 * N1) + DevArena::pad(4 * N1) + DevArena::pad(32 * N1) + DevArena::pad(8 * N2) + DevArena::pad(4 * N2) +
-                         DevArena::pad(32 * N2) + 2 * DevArena::pad(4 * N2) + 2 * DevArena::pad(4 * ncell) + DevArena::pad(4 * (ncell + 1)) +
-                         3 * DevArena::pad(4 * N1) + DevArena::pad(4);
-    if (!A.reserve(bytes)) {
+    float *d_uv1, *d_uv2;
+    int *d_oct1, *d_oct2, *d_cell, *d_keys, *d_count, *d_cursor, *d_start, *d_match, *d_best, *d_second, *d_total;
+    uint4 *d_desc1, *d_desc2;
+    A.add(&d_uv1, 2 * N1); A.add(&d_oct1, N1); A.add(&d_desc1, 2 * N1);
+    A.add(&d_uv2, 2 * N2); A.add(&d_oct2, N2); A.add(&d_desc2, 2 * N2);
+    A.add(&d_cell, N2); A.add(&d_keys, N2); A.add(&d_count, ncell); A.add(&d_cursor, ncell); A.add(&d_start, ncell + 1);
+    A.add(&d_match, N1); A.add(&d_best, N1); A.add(&d_second, N1); A.add(&d_total, 1);
+    if (!A.commit()) {
         err = "match_for_initialization: allocation failed";
         return DEFTRI_E_HIP;
     }
-    float *d_uv1 = A.take<float>(2 * N1);
-    int *d_oct1 = A.take<int>(N1);
-    uint4 *d_desc1 = A.take<uint4>(2 * N1);
-    float *d_uv2 = A.take<float>(2 * N2);
-    int *d_oct2 = A.take<int>(N2);
-    uint4 *d_desc2 = A.take<uint4>(2 * N2);
-    int *d_cell = A.take<int>(N2), *d_keys = A.take<int>(N2), *d_count = A.take<int>(ncell), *d_cursor = A.take<int>(ncell);
-    int *d_start = A.take<int>(ncell + 1);
-    int *d_match = A.take<int>(N1), *d_best = A.take<int>(N1), *d_second = A.take<int>(N1), *d_total = A.take<int>(1);
     hipMemcpyAsync(d_uv1, uv1, 8 * N1, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(d_oct1, octave1, 4 * N1, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(d_desc1, desc1, 32 * N1, hipMemcpyHostToDevice, st);
@@ -445,17 +442,14 @@ int epipolar_inliers(int device, hipStream_t st, int32_t n, const float *uv1, co
                      const float *kb8_2, const float *T1w, const float *T2w, float epipolar_th, uint8_t *inlier, float *err_out,
                      int32_t *score, std::string &err) {
     // T12 = T1w * T2w.inverse() (:162) and E = [t]x R (Geometry.cc:239-256), in float; poses row-major 3x4
-    float T2i[12], R[9], t[3];
-    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) T2i[4 * i + j] = T2w[4 * j + i];
-    for (int i = 0; i < 3; i++) T2i[4 * i + 3] = -(T2i[4 * i] * T2w[3] + T2i[4 * i + 1] * T2w[7] + T2i[4 * i + 2] * T2w[11]);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) R[3 * i + j] = T1w[4 * i] * T2i[j] + T1w[4 * i + 1] * T2i[4 + j] + T1w[4 * i + 2] * T2i[8 + j];
-        t[i] = (T1w[4 * i] * T2i[3] + T1w[4 * i + 1] * T2i[7] + T1w[4 * i + 2] * T2i[11]) + T1w[4 * i + 3];
-    }
+    float T2i[12], T12[12];
+    pose34_inverse(T2w, T2i);
+    pose34_product(T1w, T2i, T12);
+    const float t[3] = {T12[3], T12[7], T12[11]};
     const float tx[9] = {0.0f, -t[2], t[1], t[2], 0.0f, -t[0], -t[1], t[0], 0.0f};
     Mat3 E;
     for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) E.m[3 * i + j] = tx[3 * i] * R[j] + tx[3 * i + 1] * R[3 + j] + tx[3 * i + 2] * R[6 + j];
+        for (int j = 0; j < 3; j++) E.m[3 * i + j] = tx[3 * i] * T12[j] + tx[3 * i + 1] * T12[4 + j] + tx[3 * i + 2] * T12[8 + j];
     Kb8 k1, k2;
     std::memcpy(k1.k, kb8_1, sizeof(k1.k));
     std::memcpy(k2.k, kb8_2, sizeof(k2.k));
@@ -473,14 +467,14 @@ int epipolar_inliers(int device, hipStream_t st, int32_t n, const float *uv1, co
     hipSetDevice(device);
     const size_t N = (size_t)n, nb = (N + 255) / 256;
     DevArena A;
-    if (!A.reserve(2 * DevArena::pad(8 * N) + DevArena::pad(N) + DevArena::pad(4 * N) + DevArena::pad(4 * nb))) {
+    float *d_uv1, *d_uv2, *d_err;
+    uint8_t *d_in;
+    int *d_part;
+    A.add(&d_uv1, 2 * N); A.add(&d_uv2, 2 * N); A.add(&d_in, N); A.add(&d_err, N); A.add(&d_part, nb);
+    if (!A.commit()) {
         err = "epipolar_inliers: allocation failed";
         return DEFTRI_E_HIP;
     }
-    float *d_uv1 = A.take<float>(2 * N), *d_uv2 = A.take<float>(2 * N);
-    uint8_t *d_in = A.take<uint8_t>(N);
-    float *d_err = A.take<float>(N);
-    int *d_part = A.take<int>(nb);
     std::vector<int> part(nb);
     hipMemcpyAsync(d_uv1, uv1, 8 * N, hipMemcpyHostToDevice, st);
     hipMemcpyAsync(d_uv2, uv2, 8 * N, hipMemcpyHostToDevice, st);

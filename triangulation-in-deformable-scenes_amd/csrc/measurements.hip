@@ -17,8 +17,10 @@
 #include "../../include/deftri.h"
 #include "graph_builder.h"
 #include "depth_image.h"
+#include "dev_arena.h"
 #include "kernels.h"
 #include "measure_scratch.h"
+#include "pose_host.h"
 
 namespace deftri {
 namespace dev {
@@ -94,18 +96,6 @@ __global__ void k_depth_terms(int n, const float *__restrict__ pw, const double 
 
 }  // namespace dev
 
-namespace {
-
-void quat_to_R(const double *q, double *R) {     // unit quaternion (x y z w) -> row-major R
-    const double x = q[0], y = q[1], z = q[2], w = q[3];
-    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
-    const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-
-}  // namespace
 }  // namespace deftri
 
 using namespace deftri;
@@ -145,11 +135,14 @@ extern "C" int deftri_measure_sim_absolute_map_errors(int32_t device, const deft
         }
     }
     if (hipSetDevice(device) != hipSuccess) return DEFTRI_E_NODEVICE;
-    Scratch sc;
+    DevArena A;
     hipStream_t st = nullptr;
-    const float *d1 = sc.put(o1), *d2 = sc.put(o2), *dg = sc.put(og), *dm = sc.put(mv);
-    double *terms = sc.alloc(5 * (size_t)pairs), *part = sc.alloc(256), *dout = sc.alloc(8);
-    if (!d1 || !d2 || !dg || !dm || !terms || !part || !dout) return DEFTRI_E_HIP;
+    float *d1, *d2, *dg, *dm;
+    double *terms, *part, *dout;
+    A.add(&d1, o1.size()); A.add(&d2, o2.size()); A.add(&dg, og.size()); A.add(&dm, mv.size());
+    A.add(&terms, 5 * (size_t)pairs); A.add(&part, 256); A.add(&dout, 8);
+    if (!A.commit()) return DEFTRI_E_HIP;
+    upload(d1, o1); upload(d2, o2); upload(dg, og); upload(dm, mv);
     if (pairs > 0)
         hipLaunchKernelGGL(dev::k_abs_terms, dim3(nblk(pairs, 256)), dim3(256), 0, st, (int)pairs, d1, d2, dg, dm, terms);
     double s[5] = {0, 0, 0, 0, 0};
@@ -202,14 +195,11 @@ int deftri::measure_relative(DepthImages *di, int device, hipStream_t st, const 
                     break;
                 }
             // Rs_global = so3().matrix() and Ts in fp32, cast to double
-            double Rt[12];
+            std::vector<double> Rt(12);
             {
-                float q[4] = {(float)tq[0], (float)tq[1], (float)tq[2], (float)tq[3]};
-                float x = q[0], y = q[1], z = q[2], w = q[3];
-                float tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
-                float txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-                float R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx,
-                              txz - twy, tyz + twx, 1 - (txx + tyy)};
+                const float q[4] = {(float)tq[0], (float)tq[1], (float)tq[2], (float)tq[3]};
+                float R[9];
+                quat_to_rotation(q, R);
                 for (int i = 0; i < 9; i++) Rt[i] = (double)R[i];
                 for (int i = 0; i < 3; i++) Rt[9 + i] = (double)(float)tq[4 + i];
             }
@@ -236,7 +226,7 @@ int deftri::measure_relative(DepthImages *di, int device, hipStream_t st, const 
                 for (int i = 0; i < 4; i++) { qn[i] = ks[c]->pose[i]; n += qn[i] * qn[i]; }
                 n = std::sqrt(n);
                 for (int i = 0; i < 4; i++) qn[i] /= n;
-                quat_to_R(qn, &cam[12 * c]);
+                quat_to_rotation(qn, &cam[12 * c]);
                 for (int i = 0; i < 3; i++) cam[12 * c + 9 + i] = ks[c]->pose[4 + i];
             }
             std::vector<float> dpw;
@@ -298,14 +288,16 @@ int deftri::measure_relative(DepthImages *di, int device, hipStream_t st, const 
                     dm[2 * k + 1] = d2[k];
                 }
             }
-            Scratch sc;
-            const int32_t *d_ij = sc.put(ij);
-            const double *d_p1 = sc.put(v1), *d_p2 = sc.put(v2), *d_Rt = sc.put(std::vector<double>(Rt, Rt + 12));
-            const float *d_pw = sc.put(dpw);
-            const double *d_dm = sc.put(dm), *d_cam = sc.put(cam);
-            double *rel = sc.alloc(2 * (size_t)nr), *dep = sc.alloc((size_t)nd), *part = sc.alloc(256), *dout = sc.alloc(4);
-            if (!d_ij || !d_p1 || !d_p2 || !d_Rt || !d_pw || !d_dm || !d_cam || !rel || !dep || !part || !dout)
-                return DEFTRI_E_HIP;
+            DevArena A;
+            int32_t *d_ij;
+            double *d_p1, *d_p2, *d_Rt, *d_dm, *d_cam, *rel, *dep, *part, *dout;
+            float *d_pw;
+            A.add(&d_ij, ij.size()); A.add(&d_p1, v1.size()); A.add(&d_p2, v2.size()); A.add(&d_Rt, Rt.size());
+            A.add(&d_pw, dpw.size()); A.add(&d_dm, dm.size()); A.add(&d_cam, cam.size());
+            A.add(&rel, 2 * (size_t)nr); A.add(&dep, (size_t)nd); A.add(&part, 256); A.add(&dout, 4);
+            if (!A.commit()) return DEFTRI_E_HIP;
+            upload(d_ij, ij); upload(d_p1, v1); upload(d_p2, v2); upload(d_Rt, Rt);
+            upload(d_pw, dpw); upload(d_dm, dm); upload(d_cam, cam);
             if (nr > 0)
                 hipLaunchKernelGGL(dev::k_rel_terms, dim3(nblk(nr, 256)), dim3(256), 0, st, (int)nr, d_ij, d_p1, d_p2, d_Rt, rel);
             if (nd > 0)

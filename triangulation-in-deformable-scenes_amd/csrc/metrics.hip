@@ -5,11 +5,17 @@
 // |obs - uv| and its square in u and v for both cameras (:440-452).  One thread per match computes
 // the two error vectors; each workgroup reduces its 256 matches in a fixed tree order into one
 // partial of 8 doubles (sum |e| and sum e^2, u and v, camera 1 then 2); the host adds the partials
-// of each pair in order and replays the reference's per-pair formulas (deftri_pixels_stand_dev).
+// of each pair in order and replays the reference's per-pair formulas (pixels_stand_dev).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "dev_arena.h"
 #include "device_math.h"
-#include "kernels.h"
+#include "metrics.h"
+#include "pose_host.h"
 
 namespace deftri {
 namespace dev {
@@ -60,12 +66,89 @@ __global__ void __launch_bounds__(256) k_pix_partial(const int32_t *__restrict__
 
 }  // namespace dev
 
-void launch_pixel_partials(int nblk, const int32_t *blk_first, const int32_t *blk_last, const int32_t *blk_pair,
-                           const int32_t *pair_cams, const float *cams, const float *pts, const float *obs,
-                           double *part, hipStream_t st) {
-    if (nblk > 0)
-        hipLaunchKernelGGL(dev::k_pix_partial, dim3(nblk), dim3(256), 0, st, blk_first, blk_last, blk_pair, pair_cams,
-                           cams, pts, obs, part);
+int pixels_stand_dev(int device, hipStream_t st, const deftri_map &map, deftri_pixels_error *out, std::string &err) {
+    if (device < 0) { err = "host-only context"; return DEFTRI_E_NODEVICE; }
+    hipSetDevice(device);
+    const int K = map.n_keyframes;
+    // per keyframe: R (fp32, Eigen toRotationMatrix of the fp32 unit quaternion), t, kb8
+    std::vector<float> cams(20 * (size_t)std::max(K, 1));
+    for (int k = 0; k < K; k++) {
+        const deftri_keyframe &kf = map.keyframes[k];
+        const float q[4] = {(float)kf.pose[0], (float)kf.pose[1], (float)kf.pose[2], (float)kf.pose[3]};
+        float *c = &cams[20 * (size_t)k];
+        quat_to_rotation(q, c);
+        for (int i = 0; i < 3; i++) c[9 + i] = (float)kf.pose[4 + i];
+        for (int i = 0; i < 8; i++) c[12 + i] = kf.kb8[i];
+    }
+    // matches of each pair in the reference's loop order (:386-416)
+    std::vector<float> pts, obs;
+    std::vector<int32_t> pair_cams, pair_first{0};
+    for (int a = 0; a < K; a++)
+        for (int b = a + 1; b < K; b++) {
+            const deftri_keyframe &k1 = map.keyframes[b], &k2 = map.keyframes[a];
+            pair_cams.push_back(b); pair_cams.push_back(a);
+            const int n = std::min(k1.n_slots, k2.n_slots);
+            for (int i = 0; i < n; i++) {
+                if (k1.point_id[i] < 0 || k2.point_id[i] < 0) continue;
+                const int o1 = k1.obs_index[i], o2 = k2.obs_index[i];
+                if (o1 < 0 || o2 < 0) continue;
+                if (o1 >= k1.n_obs || o2 >= k2.n_obs) { err = "observation index out of range"; return DEFTRI_E_ARG; }
+                for (int q = 0; q < 3; q++) pts.push_back(k1.point_pos[3 * (int64_t)i + q]);
+                for (int q = 0; q < 3; q++) pts.push_back(k2.point_pos[3 * (int64_t)i + q]);
+                obs.push_back(k1.kp_uv[2 * (int64_t)o1]); obs.push_back(k1.kp_uv[2 * (int64_t)o1 + 1]);
+                obs.push_back(k2.kp_uv[2 * (int64_t)o2]); obs.push_back(k2.kp_uv[2 * (int64_t)o2 + 1]);
+            }
+            pair_first.push_back((int32_t)(pts.size() / 6));
+        }
+    const int npair = (int)pair_cams.size() / 2;
+    // 256-match blocks that never straddle pairs: first match, end, pair
+    std::vector<int32_t> bf, bl, bp;
+    for (int p = 0; p < npair; p++)
+        for (int32_t s = pair_first[p]; s < pair_first[p + 1]; s += 256) {
+            bf.push_back(s); bl.push_back(std::min(s + 256, pair_first[p + 1])); bp.push_back(p);
+        }
+    const int nblk = (int)bf.size();
+    std::vector<double> part(8 * (size_t)std::max(nblk, 1), 0.0);
+    if (nblk > 0) {
+        DevArena A;
+        double *d_part;
+        float *d_cams, *d_pts, *d_obs;
+        int32_t *d_bf, *d_bl, *d_bp, *d_pc;
+        A.add(&d_part, part.size()); A.add(&d_cams, cams.size()); A.add(&d_pts, pts.size()); A.add(&d_obs, obs.size());
+        A.add(&d_bf, bf.size()); A.add(&d_bl, bl.size()); A.add(&d_bp, bp.size()); A.add(&d_pc, pair_cams.size());
+        if (!A.commit()) { err = "pixels_stand_dev: allocation failed"; return DEFTRI_E_HIP; }
+        hipMemcpyAsync(d_cams, cams.data(), 4 * cams.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_pts, pts.data(), 4 * pts.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_obs, obs.data(), 4 * obs.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_bf, bf.data(), 4 * bf.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_bl, bl.data(), 4 * bl.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_bp, bp.data(), 4 * bp.size(), hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_pc, pair_cams.data(), 4 * pair_cams.size(), hipMemcpyHostToDevice, st);
+        hipLaunchKernelGGL(dev::k_pix_partial, dim3(nblk), dim3(256), 0, st, d_bf, d_bl, d_bp, d_pc, d_cams, d_pts, d_obs, d_part);
+        hipMemcpyAsync(part.data(), d_part, 8 * part.size(), hipMemcpyDeviceToHost, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) { err = std::string("pixels_stand_dev: ") + hipGetErrorString(e); return DEFTRI_E_HIP; }
+    }
+    // the reference's per-pair formulas (:454-485); meanUV and nMatches carry over pairs
+    double mUV1[2] = {0, 0}, mUV2[2] = {0, 0};
+    double mC1 = 0, mC2 = 0, dC1 = 0, dC2 = 0;
+    size_t nMatches = 0;
+    for (int p = 0, blk = 0; p < npair; p++) {
+        double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (; blk < nblk && bp[blk] == p; blk++)
+            for (int q = 0; q < 8; q++) sum[q] += part[8 * (size_t)blk + q];
+        nMatches += (size_t)(pair_first[p + 1] - pair_first[p]);
+        const double nm = (double)nMatches;
+        for (int q = 0; q < 2; q++) { mUV1[q] += sum[q]; mUV2[q] += sum[4 + q]; }
+        for (int q = 0; q < 2; q++) { mUV1[q] /= nm; mUV2[q] /= nm; }
+        mC1 = (mUV1[0] + mUV1[1]) / 2.0;
+        mC2 = (mUV2[0] + mUV2[1]) / 2.0;
+        dC1 = (std::sqrt(sum[2] / nm) + std::sqrt(sum[3] / nm)) / 2.0;
+        dC2 = (std::sqrt(sum[6] / nm) + std::sqrt(sum[7] / nm)) / 2.0;
+    }
+    out->avgc1 = mC1; out->avgc2 = mC2; out->avg = (mC1 + mC2) / 2.0;
+    out->desvc1 = dC1; out->desvc2 = dC2; out->desv = (dC1 + dC2) / 2.0;
+    return 0;
 }
 
 }  // namespace deftri

@@ -27,14 +27,16 @@
 #include <memory>
 
 #include "../../include/deftri.h"
-#include "dev_arena.h"
 #include "graph_builder.h"
 #include "kernels.h"
 #include "matching.h"
+#include "metrics.h"
 #include "pcg.h"
+#include "pose_host.h"
 #include "spcg.h"
 #include "exit_guard.h"
 #include "symbolic.h"
+#include "triangulate.h"
 
 using namespace deftri;
 
@@ -70,17 +72,6 @@ static void quat_norm(double *q) {      // SE3Quat::normalizeRotation
     if (q[3] < 0) { q[0] = -q[0]; q[1] = -q[1]; q[2] = -q[2]; q[3] = -q[3]; }
     double n = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     for (int k = 0; k < 4; k++) q[k] /= n;
-}
-
-static void quat_mat(const double *q, double *R) {
-    double x = q[0], y = q[1], z = q[2], w = q[3];
-    double tx = 2 * x, ty = 2 * y, tz = 2 * z;
-    double twx = tx * w, twy = ty * w, twz = tz * w;
-    double txx = tx * x, txy = ty * x, txz = tz * x;
-    double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
 }
 
 }  // namespace
@@ -392,7 +383,7 @@ int refresh_values(deftri_ctx *ctx, const HostProblem &h) {
         return v.empty() ? hipSuccess : hipMemcpy(dst, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice);
     };
     std::vector<double> camR(9 * (size_t)std::max(P.C, 1));
-    for (int c = 0; c < P.C; c++) quat_mat(&h.cam_pose[7 * c], &camR[9 * c]);
+    for (int c = 0; c < P.C; c++) quat_to_rotation(&h.cam_pose[7 * c], &camR[9 * c]);
     HIPOK(put(P.points, h.points)); HIPOK(put(P.scales, h.scales)); HIPOK(put(P.tg, h.tg));
     HIPOK(put(ctx->init_state[0], h.points)); HIPOK(put(ctx->init_state[1], h.scales));
     HIPOK(put(ctx->init_state[2], h.tg));
@@ -502,7 +493,7 @@ int upload_device(deftri_ctx *ctx, const HostProblem &h) {
     if ((rc = dalloc(ctx, &P.tg_bak, 7 * (int64_t)P.Q))) return rc;
     PUT(P.cam_kb8, h.cam_kb8); PUT(P.cam_pose, h.cam_pose);
     std::vector<double> camR(9 * (size_t)std::max(P.C, 1));
-    for (int c = 0; c < P.C; c++) quat_mat(&h.cam_pose[7 * c], &camR[9 * c]);
+    for (int c = 0; c < P.C; c++) quat_to_rotation(&h.cam_pose[7 * c], &camR[9 * c]);
     PUT(P.cam_R, camR);
     PUT(P.rep_point, h.rep_point); PUT(P.rep_cam, h.rep_cam); PUT(P.rep_obs, h.rep_obs); PUT(P.rep_info, h.rep_info);
     PUT(P.dep_point, h.dep_point); PUT(P.dep_scale, h.dep_scale); PUT(P.dep_cam, h.dep_cam);
@@ -1999,197 +1990,26 @@ int deftri_solve_lm(deftri_ctx *ctx, const deftri_lm_params *prm, deftri_report 
     return 0;
 }
 
+// ---- calculatePixelsStandDev (metrics.hip) ----
 int deftri_pixels_stand_dev(deftri_ctx *ctx, const deftri_map *map, deftri_pixels_error *out) {
     if (!ctx || !map || !out || map->n_keyframes < 0 || (map->n_keyframes > 0 && !map->keyframes)) return DEFTRI_E_ARG;
-    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
-    hipSetDevice(ctx->device);
-    const int K = map->n_keyframes;
-    // per keyframe: R (fp32, Eigen toRotationMatrix of the fp32 unit quaternion), t, kb8
-    std::vector<float> cams(20 * (size_t)std::max(K, 1));
-    for (int k = 0; k < K; k++) {
-        const deftri_keyframe &kf = map->keyframes[k];
-        float x = (float)kf.pose[0], y = (float)kf.pose[1], z = (float)kf.pose[2], w = (float)kf.pose[3];
-        float tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
-        float txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
-        float *c = &cams[20 * (size_t)k];
-        c[0] = 1 - (tyy + tzz); c[1] = txy - twz;       c[2] = txz + twy;
-        c[3] = txy + twz;       c[4] = 1 - (txx + tzz); c[5] = tyz - twx;
-        c[6] = txz - twy;       c[7] = tyz + twx;       c[8] = 1 - (txx + tyy);
-        for (int q = 0; q < 3; q++) c[9 + q] = (float)kf.pose[4 + q];
-        for (int q = 0; q < 8; q++) c[12 + q] = kf.kb8[q];
-    }
-    // matches of each pair in the reference's loop order (:386-416)
-    std::vector<float> pts, obs;
-    std::vector<int32_t> pair_cams, pair_first{0};
-    for (int a = 0; a < K; a++)
-        for (int b = a + 1; b < K; b++) {
-            const deftri_keyframe &k1 = map->keyframes[b], &k2 = map->keyframes[a];
-            pair_cams.push_back(b); pair_cams.push_back(a);
-            const int n = std::min(k1.n_slots, k2.n_slots);
-            for (int i = 0; i < n; i++) {
-                if (k1.point_id[i] < 0 || k2.point_id[i] < 0) continue;
-                const int o1 = k1.obs_index[i], o2 = k2.obs_index[i];
-                if (o1 < 0 || o2 < 0) continue;
-                if (o1 >= k1.n_obs || o2 >= k2.n_obs) return fail(ctx, DEFTRI_E_ARG, "observation index out of range");
-                for (int q = 0; q < 3; q++) pts.push_back(k1.point_pos[3 * (int64_t)i + q]);
-                for (int q = 0; q < 3; q++) pts.push_back(k2.point_pos[3 * (int64_t)i + q]);
-                obs.push_back(k1.kp_uv[2 * (int64_t)o1]); obs.push_back(k1.kp_uv[2 * (int64_t)o1 + 1]);
-                obs.push_back(k2.kp_uv[2 * (int64_t)o2]); obs.push_back(k2.kp_uv[2 * (int64_t)o2 + 1]);
-            }
-            pair_first.push_back((int32_t)(pts.size() / 6));
-        }
-    const int npair = (int)pair_cams.size() / 2;
-    std::vector<int32_t> bf, bl, bp;
-    for (int p = 0; p < npair; p++)
-        for (int32_t s = pair_first[p]; s < pair_first[p + 1]; s += 256) {
-            bf.push_back(s); bl.push_back(std::min(s + 256, pair_first[p + 1])); bp.push_back(p);
-        }
-    const int nblk = (int)bf.size();
-    std::vector<double> part(8 * (size_t)std::max(nblk, 1), 0.0);
-    if (nblk > 0) {
-        // scratch buffers of this call (one allocation, freed before returning)
-        const size_t nb_i = 3 * (size_t)nblk + 2 * (size_t)npair, nb_f = cams.size() + pts.size() + obs.size();
-        const size_t bytes = 8 * part.size() + 4 * nb_f + 4 * nb_i + 64;
-        char *dbuf = nullptr;
-        HIPOK(hipMalloc(&dbuf, bytes));
-        double *d_part = (double *)dbuf;
-        float *d_cams = (float *)(d_part + part.size());
-        float *d_pts = d_cams + cams.size(), *d_obs = d_pts + pts.size();
-        int32_t *d_bf = (int32_t *)(d_obs + obs.size()), *d_bl = d_bf + nblk, *d_bp = d_bl + nblk, *d_pc = d_bp + nblk;
-        hipMemcpyAsync(d_cams, cams.data(), 4 * cams.size(), hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_pts, pts.data(), 4 * pts.size(), hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_obs, obs.data(), 4 * obs.size(), hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_bf, bf.data(), 4 * (size_t)nblk, hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_bl, bl.data(), 4 * (size_t)nblk, hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_bp, bp.data(), 4 * (size_t)nblk, hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_pc, pair_cams.data(), 4 * pair_cams.size(), hipMemcpyHostToDevice, ctx->st);
-        launch_pixel_partials(nblk, d_bf, d_bl, d_bp, d_pc, d_cams, d_pts, d_obs, d_part, ctx->st);
-        hipMemcpyAsync(part.data(), d_part, 8 * part.size(), hipMemcpyDeviceToHost, ctx->st);
-        hipError_t e = hipStreamSynchronize(ctx->st);
-        hipFree(dbuf);
-        if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("pixels_stand_dev: ") + hipGetErrorString(e));
-    }
-    // the reference's per-pair formulas (:454-485); meanUV and nMatches carry over pairs
-    double mUV1[2] = {0, 0}, mUV2[2] = {0, 0};
-    double mC1 = 0, mC2 = 0, dC1 = 0, dC2 = 0;
-    size_t nMatches = 0;
-    for (int p = 0, blk = 0; p < npair; p++) {
-        double sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (; blk < nblk && bp[blk] == p; blk++)
-            for (int q = 0; q < 8; q++) sum[q] += part[8 * (size_t)blk + q];
-        nMatches += (size_t)(pair_first[p + 1] - pair_first[p]);
-        const double nm = (double)nMatches;
-        for (int q = 0; q < 2; q++) { mUV1[q] += sum[q]; mUV2[q] += sum[4 + q]; }
-        for (int q = 0; q < 2; q++) { mUV1[q] /= nm; mUV2[q] /= nm; }
-        mC1 = (mUV1[0] + mUV1[1]) / 2.0;
-        mC2 = (mUV2[0] + mUV2[1]) / 2.0;
-        dC1 = (std::sqrt(sum[2] / nm) + std::sqrt(sum[3] / nm)) / 2.0;
-        dC2 = (std::sqrt(sum[6] / nm) + std::sqrt(sum[7] / nm)) / 2.0;
-    }
-    out->avgc1 = mC1; out->avgc2 = mC2; out->avg = (mC1 + mC2) / 2.0;
-    out->desvc1 = dC1; out->desvc2 = dC2; out->desv = (dC1 + dC2) / 2.0;
-    return 0;
+    std::string err;
+    const int rc = pixels_stand_dev(ctx->device, ctx->st, *map, out, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
+// ---- every defined seed, reconstructPoints, the initial depth scales (triangulate.hip) ----
+// the (NRSLAM, FarPoints) variant of deftri_triangulate
 int deftri_triangulate_nrslam(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
                               const float *kb8_2, const float *T1w, const float *T2w, float min_cos, float *x3d_1,
                               float *x3d_2, uint8_t *valid) {
     if (!ctx || n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !valid)) || !kb8_1 || !kb8_2 || !T1w || !T2w)
         return DEFTRI_E_ARG;
-    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
-    if (n == 0) return 0;
-    hipSetDevice(ctx->device);
-    // Sophus: T1w.inverse() = [R1^T | -(R1^T t1)], T21 = T2w * T1w.inverse(), T2w.inverse()
-    auto inverse = [](const float *T, float *Ti) {
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Ti[4 * i + j] = T[4 * j + i];
-        for (int i = 0; i < 3; i++) Ti[4 * i + 3] = -(Ti[4 * i] * T[3] + Ti[4 * i + 1] * T[7] + Ti[4 * i + 2] * T[11]);
-    };
-    float Tp[48], T1i[12];
-    std::memcpy(Tp, T1w, 12 * sizeof(float));
-    std::memcpy(Tp + 12, T2w, 12 * sizeof(float));
-    inverse(T1w, T1i);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++)
-            Tp[24 + 4 * i + j] = T2w[4 * i] * T1i[j] + T2w[4 * i + 1] * T1i[4 + j] + T2w[4 * i + 2] * T1i[8 + j];
-        Tp[24 + 4 * i + 3] = (T2w[4 * i] * T1i[3] + T2w[4 * i + 1] * T1i[7] + T2w[4 * i + 2] * T1i[11]) + T2w[4 * i + 3];
-    }
-    inverse(T2w, Tp + 36);
-    const size_t N = (size_t)n;
-    const size_t bytes = 4 * (2 * N + 2 * N + 8 + 8 + 48 + 3 * N + 3 * N) + N + 64;
-    char *dbuf = nullptr;
-    HIPOK(hipMalloc(&dbuf, bytes));
-    float *d_uv1 = (float *)dbuf, *d_uv2 = d_uv1 + 2 * N, *d_k1 = d_uv2 + 2 * N, *d_k2 = d_k1 + 8, *d_T = d_k2 + 8;
-    float *d_x1 = d_T + 48, *d_x2 = d_x1 + 3 * N;
-    uint8_t *d_v = (uint8_t *)(d_x2 + 3 * N);
-    hipMemcpyAsync(d_uv1, uv1, 8 * N, hipMemcpyHostToDevice, ctx->st);
-    hipMemcpyAsync(d_uv2, uv2, 8 * N, hipMemcpyHostToDevice, ctx->st);
-    hipMemcpyAsync(d_k1, kb8_1, 32, hipMemcpyHostToDevice, ctx->st);
-    hipMemcpyAsync(d_k2, kb8_2, 32, hipMemcpyHostToDevice, ctx->st);
-    hipMemcpyAsync(d_T, Tp, sizeof(Tp), hipMemcpyHostToDevice, ctx->st);
-    launch_triangulate_nrslam(n, d_uv1, d_uv2, d_k1, d_k2, d_T, min_cos, d_x1, d_x2, d_v, ctx->st);
-    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(valid, d_v, N, hipMemcpyDeviceToHost, ctx->st);
-    hipError_t e = hipStreamSynchronize(ctx->st);
-    hipFree(dbuf);
-    if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("triangulate: ") + hipGetErrorString(e));
-    return 0;
+    std::string err;
+    const int rc = triangulate(ctx->device, ctx->st, n, DEFTRI_TRI_NRSLAM, DEFTRI_LOC_FARPOINTS, uv1, uv2, kb8_1, kb8_2, T1w, T2w,
+                               min_cos, x3d_1, x3d_2, valid, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
-
-// ---- every defined seed, reconstructPoints, the initial depth scales (triangulate.hip) ----
-}  // extern "C"
-namespace {
-// T1w, T2w, T21 = T2w * T1w.inverse(), T2w.inverse() (3x4 each), formed as deftri_triangulate_nrslam does
-void triangulation_poses(const float *T1w, const float *T2w, float Tp[48]) {
-    auto inverse = [](const float *T, float *Ti) {
-        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) Ti[4 * i + j] = T[4 * j + i];
-        for (int i = 0; i < 3; i++) Ti[4 * i + 3] = -(Ti[4 * i] * T[3] + Ti[4 * i + 1] * T[7] + Ti[4 * i + 2] * T[11]);
-    };
-    float T1i[12];
-    std::memcpy(Tp, T1w, 12 * sizeof(float));
-    std::memcpy(Tp + 12, T2w, 12 * sizeof(float));
-    inverse(T1w, T1i);
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++)
-            Tp[24 + 4 * i + j] = T2w[4 * i] * T1i[j] + T2w[4 * i + 1] * T1i[4 + j] + T2w[4 * i + 2] * T1i[8 + j];
-        Tp[24 + 4 * i + 3] = (T2w[4 * i] * T1i[3] + T2w[4 * i + 1] * T1i[7] + T2w[4 * i + 2] * T1i[11]) + T2w[4 * i + 3];
-    }
-    inverse(T2w, Tp + 36);
-}
-
-// "" when the reference defines the variant, else why it does not
-const char *undefined_seed(int32_t method, int32_t location, bool simulated) {
-    if (method != DEFTRI_TRI_CLASSIC && method != DEFTRI_TRI_NRSLAM && method != DEFTRI_TRI_ORBSLAM && method != DEFTRI_TRI_DEPTH)
-        return "unknown triangulation method";
-    if (location != DEFTRI_LOC_INRAYS && location != DEFTRI_LOC_TWOPOINTS && location != DEFTRI_LOC_FARPOINTS)
-        return "unknown seed location";
-    if (method == DEFTRI_TRI_ORBSLAM)
-        return "Triangulation.method ORBSLAM is undefined in the reference: triangulateORBSLAM (Geometry.cc:155-186) never "
-               "writes x3D_1 / x3D_2";
-    if (method == DEFTRI_TRI_DEPTH && simulated)
-        return "Triangulation.method DepthMeasurement is undefined in the simulated entry: its inputs are "
-               "CameraModel::unproject(x, d), an unset vector (CameraModel.h:128-135); it is defined in "
-               "deftri_reconstruct_points (Geometry.cc:189-214)";
-    return "";
-}
-
-// the inputs every triangulation kernel reads: the pixel pairs, both calibrations, the four poses
-struct TriInputs {
-    float *uv1, *uv2, *k1, *k2, *T;
-    static size_t bytes(size_t N) { return 2 * DevArena::pad(8 * N) + 2 * DevArena::pad(32) + DevArena::pad(48 * sizeof(float)); }
-    // Tp stays the caller's until the stream is synchronized
-    TriInputs(DevArena &A, size_t N, const float *h_uv1, const float *h_uv2, const float *kb8_1, const float *kb8_2,
-              const float *Tp, hipStream_t st)
-        : uv1(A.take<float>(2 * N)), uv2(A.take<float>(2 * N)), k1(A.take<float>(8)), k2(A.take<float>(8)), T(A.take<float>(48)) {
-        hipMemcpyAsync(uv1, h_uv1, 8 * N, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(uv2, h_uv2, 8 * N, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(k1, kb8_1, 32, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(k2, kb8_2, 32, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(T, Tp, 48 * sizeof(float), hipMemcpyHostToDevice, st);
-    }
-};
-}  // namespace
-extern "C" {
 
 int deftri_triangulate(deftri_ctx *ctx, int32_t n, int32_t method, int32_t location, const float *uv1, const float *uv2,
                        const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w, float min_cos,
@@ -2197,30 +2017,10 @@ int deftri_triangulate(deftri_ctx *ctx, int32_t n, int32_t method, int32_t locat
     if (!ctx) return DEFTRI_E_ARG;
     if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !valid)) || !kb8_1 || !kb8_2 || !T1w || !T2w)
         return fail(ctx, DEFTRI_E_ARG, "triangulate: null array or negative n");
-    const char *why = undefined_seed(method, location, true);
-    if (*why) return fail(ctx, DEFTRI_E_ARG, why);
-    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
-    if (n == 0) return 0;
-    hipSetDevice(ctx->device);
-    float Tp[48];
-    triangulation_poses(T1w, T2w, Tp);
-    const size_t N = (size_t)n;
-    DevArena A;
-    if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + DevArena::pad(N)))
-        return fail(ctx, DEFTRI_E_HIP, "triangulate: allocation failed");
-    const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
-    float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
-    uint8_t *d_v = A.take<uint8_t>(N);
-    if (!launch_triangulate(method, location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, min_cos, d_x1, d_x2, d_v, ctx->st)) {
-        hipStreamSynchronize(ctx->st);
-        return fail(ctx, DEFTRI_E_ARG, "triangulate: no kernel for this (method, location)");
-    }
-    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(valid, d_v, N, hipMemcpyDeviceToHost, ctx->st);
-    const hipError_t e = hipStreamSynchronize(ctx->st);
-    if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("triangulate: ") + hipGetErrorString(e));
-    return 0;
+    std::string err;
+    const int rc = triangulate(ctx->device, ctx->st, n, method, location, uv1, uv2, kb8_1, kb8_2, T1w, T2w, min_cos, x3d_1, x3d_2,
+                               valid, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
 int deftri_reconstruct_points(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
@@ -2231,52 +2031,10 @@ int deftri_reconstruct_points(deftri_ctx *ctx, int32_t n, const float *uv1, cons
     if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !status || !cos_parallax)) || !kb8_1 || !kb8_2 || !T1w ||
         !T2w || !params || !report)
         return fail(ctx, DEFTRI_E_ARG, "reconstruct_points: null array or negative n");
-    const char *why = undefined_seed(params->method, params->location, false);
-    if (*why) return fail(ctx, DEFTRI_E_ARG, why);
-    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
-    std::memset(report, 0, sizeof(*report));
-    if (n == 0) return 0;
-    hipSetDevice(ctx->device);
-    float Tp[48];
-    triangulation_poses(T1w, T2w, Tp);
-    const size_t N = (size_t)n;
-    DevArena A;
-    if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + DevArena::pad(N) + DevArena::pad(4 * N)))
-        return fail(ctx, DEFTRI_E_HIP, "reconstruct_points: allocation failed");
-    const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
-    float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
-    uint8_t *d_s = A.take<uint8_t>(N);
-    float *d_c = A.take<float>(N);
-    if (!launch_reconstruct_points(params->method, params->location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, params->depth_limit,
-                                   params->checks ? 1 : 0, d_x1, d_x2, d_s, d_c, ctx->st)) {
-        hipStreamSynchronize(ctx->st);
-        return fail(ctx, DEFTRI_E_ARG, "reconstruct_points: no kernel for this (method, location)");
-    }
-    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(status, d_s, N, hipMemcpyDeviceToHost, ctx->st);
-    hipMemcpyAsync(cos_parallax, d_c, 4 * N, hipMemcpyDeviceToHost, ctx->st);
-    const hipError_t e = hipStreamSynchronize(ctx->st);
-    if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("reconstruct_points: ") + hipGetErrorString(e));
-    // the acceptance (:370-394) from the copied-back status and cosines
-    std::vector<float> par;
-    int64_t *counters[6] = {nullptr, &report->n_nonfinite, &report->n_depth1, &report->n_err1, &report->n_depth2,
-                            &report->n_err2};
-    for (size_t i = 0; i < N; i++) {
-        if (status[i] == 0) par.push_back(cos_parallax[i]);
-        else if (status[i] <= 5) ++*counters[status[i]];
-    }
-    report->n_triangulated = 2 * (int64_t)par.size();
-    if (par.empty()) return 0;
-    const size_t idx = std::min<size_t>(50, par.size() - 1);
-    std::nth_element(par.begin(), par.begin() + (std::ptrdiff_t)idx, par.end());      // sorted order's element idx
-    const float cosp = par[idx];
-    if (cosp < 0.0f || cosp > 1.0f) return 0;                 // "Parallax must be between 0 and 1": not accepted
-    const float radians = acosf(cosp);
-    const float degrees = (float)((double)radians * (180.0 / M_PI));
-    report->parallax_deg = degrees;
-    report->accepted = (report->n_triangulated >= 25 && degrees > params->min_parallax) ? 1 : 0;
-    return 0;
+    std::string err;
+    const int rc = reconstruct_points(ctx->device, ctx->st, n, uv1, uv2, kb8_1, kb8_2, T1w, T2w, *params, x3d_1, x3d_2, status,
+                                      cos_parallax, report, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
 int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, int32_t n, const float *uv1, const float *uv2,
@@ -2287,55 +2045,10 @@ int deftri_init_depth_scales(deftri_ctx *ctx, int64_t kf_id_1, int64_t kf_id_2, 
     if (n < 0 || (n > 0 && (!uv1 || !uv2 || !x3d_1 || !x3d_2 || !keep)) || !kb8_1 || !kb8_2 || !T1w || !T2w || !scale_1 ||
         !scale_2 || !n_points)
         return fail(ctx, DEFTRI_E_ARG, "init_depth_scales: null array or negative n");
-    if (ctx->device < 0) return fail(ctx, DEFTRI_E_NODEVICE, "host-only context");
-    hipSetDevice(ctx->device);
-    DepthImageDev im[2];
-    const int64_t ids[2] = {kf_id_1, kf_id_2};
-    for (int c = 0; c < 2; c++)
-        if (!ctx->images.device_image(ids[c], &im[c].pixels, &im[c].rows, &im[c].cols, &im[c].scale))
-            return fail(ctx, DEFTRI_E_ARG, "Depth image is not initialized: keyframe " + std::to_string(ids[c]));
-    const size_t N = (size_t)n, nb = (N + 255) / 256;
-    double sum[3] = {0, 0, 0};
-    std::vector<uint8_t> h_keep(N), h_st(N);
-    if (n > 0) {
-        float Tp[48];
-        triangulation_poses(T1w, T2w, Tp);
-        DevArena A;
-        if (!A.reserve(TriInputs::bytes(N) + 2 * DevArena::pad(12 * N) + 2 * DevArena::pad(N) + DevArena::pad(24 * nb)))
-            return fail(ctx, DEFTRI_E_HIP, "init_depth_scales: allocation failed");
-        const TriInputs in(A, N, uv1, uv2, kb8_1, kb8_2, Tp, ctx->st);
-        float *d_x1 = A.take<float>(3 * N), *d_x2 = A.take<float>(3 * N);
-        uint8_t *d_keep = A.take<uint8_t>(N), *d_st = A.take<uint8_t>(N);
-        double *d_part = A.take<double>(3 * nb);
-        std::vector<double> part(3 * nb);
-        hipMemcpyAsync(d_x1, x3d_1, 12 * N, hipMemcpyHostToDevice, ctx->st);
-        hipMemcpyAsync(d_x2, x3d_2, 12 * N, hipMemcpyHostToDevice, ctx->st);
-        launch_init_depth_scales(n, in.uv1, in.uv2, d_x1, d_x2, in.k1, in.k2, in.T, min_cos, im[0], im[1], d_keep, d_st, d_part,
-                                 ctx->st);
-        hipMemcpyAsync(h_keep.data(), d_keep, N, hipMemcpyDeviceToHost, ctx->st);
-        hipMemcpyAsync(h_st.data(), d_st, N, hipMemcpyDeviceToHost, ctx->st);
-        hipMemcpyAsync(part.data(), d_part, 24 * nb, hipMemcpyDeviceToHost, ctx->st);
-        const hipError_t e = hipStreamSynchronize(ctx->st);
-        if (e != hipSuccess) return fail(ctx, DEFTRI_E_HIP, std::string("init_depth_scales: ") + hipGetErrorString(e));
-        for (size_t i = 0; i < N; i++) {
-            if (!h_st[i]) continue;
-            const int c = (h_st[i] & 15) ? 0 : 1;
-            const float *px = (c ? uv2 : uv1) + 2 * i;
-            char buf[200];
-            std::snprintf(buf, sizeof(buf), "keyframe %lld correspondence %zu: pixel (%g, %g) %s", (long long)ids[c], i,
-                          (double)px[0], (double)px[1],
-                          ((c ? h_st[i] >> 4 : h_st[i] & 15) == 1) ? "is out of range of the depth image"
-                                                                   : "reads outside the depth image");
-            return fail(ctx, DEFTRI_E_ARG, buf);
-        }
-        for (size_t b = 0; b < nb; b++)                        // workgroup order
-            for (int q = 0; q < 3; q++) sum[q] += part[3 * b + q];
-        std::memcpy(keep, h_keep.data(), N);
-    }
-    *n_points = (int64_t)sum[2];
-    *scale_1 = sum[0] / sum[2];                                // n_points == 0: 0 / 0 = NaN, as the reference (:250-251)
-    *scale_2 = sum[1] / sum[2];
-    return 0;
+    std::string err;
+    const int rc = init_depth_scales(ctx->device, ctx->st, ctx->images, kf_id_1, kf_id_2, n, uv1, uv2, x3d_1, x3d_2, kb8_1, kb8_2,
+                                     T1w, T2w, min_cos, keep, scale_1, scale_2, n_points, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
 // ---- searchForInitializaion and the epipolar inlier mask (matching.hip) ----

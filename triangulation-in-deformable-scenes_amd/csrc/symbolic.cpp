@@ -31,12 +31,12 @@ struct Builder {
     int64_t next_pos = 0;
     // per-thread scratch of the nested dissection, indexed by point (the subdomains of concurrent
     // tasks are disjoint, but their separator searches read the neighbours' sides)
-    struct Scratch {
+    struct NdWork {
         std::vector<int32_t> side;
         std::vector<int32_t> stamp;      // distinct-count scratch
         int32_t stamp_id = 0;
         std::vector<int64_t> spos;       // index of a point in the separator list being refined
-        explicit Scratch(int32_t n) : side(std::max(n, 1), 0), stamp(std::max(n, 1), 0), spos(std::max(n, 1), -1) {}
+        explicit NdWork(int32_t n) : side(std::max(n, 1), 0), stamp(std::max(n, 1), 0), spos(std::max(n, 1), -1) {}
     };
     // dissection tree under construction: fronts in postorder (own vertices, children; -1 = none)
     struct LocalTree {
@@ -138,7 +138,7 @@ struct Builder {
     // neighbours in the other half into the separator (size change: -1 + that count).  Each pass
     // makes the best balanced move repeatedly (hill-climbing through non-positive gains, moved
     // points locked) and rolls back to the smallest separator seen.
-    void refine_sep(std::vector<int64_t> &sep, int64_t &nA, int64_t &nB, int64_t ntot, Scratch &sc) {
+    void refine_sep(std::vector<int64_t> &sep, int64_t &nA, int64_t &nB, int64_t ntot, NdWork &sc) {
         auto &side = sc.side; auto &stamp = sc.stamp; auto &spos = sc.spos;
         const int64_t cap = (int64_t)std::ceil(nd_bal * (double)ntot);
         for (size_t i = 0; i < sep.size(); i++) spos[sep[i]] = (int64_t)i;
@@ -208,7 +208,7 @@ struct Builder {
     // a large subdomain near the top are dissected concurrently (left on a new thread with its own
     // scratch, right here) and appended in the sequential order, so the tree — and every elimination
     // position — is the same as a one-thread run.
-    int32_t nd(std::vector<int64_t> &nodes, int depth, Scratch &sc, LocalTree &T) {
+    int32_t nd(std::vector<int64_t> &nodes, int depth, NdWork &sc, LocalTree &T) {
         auto &side = sc.side;
         int64_t n = (int64_t)nodes.size();
         if (n <= leaf || depth > 48) {
@@ -307,7 +307,7 @@ struct Builder {
         if (depth < par_depth && n >= par_min) {
             LocalTree TL, TR;
             int32_t rl = -1;
-            std::thread th([&] { Scratch sl(P); rl = nd(L, depth + 1, sl, TL); });
+            std::thread th([&] { NdWork sl(P); rl = nd(L, depth + 1, sl, TL); });
             const int32_t rr = nd(R, depth + 1, sc, TR);
             th.join();
             cl = T.append(std::move(TL)) + rl;
@@ -356,7 +356,7 @@ struct Builder {
         if (P > 0) {
             std::vector<int64_t> nodes(P);
             std::iota(nodes.begin(), nodes.end(), 0);
-            Scratch sc(P);
+            NdWork sc(P);
             LocalTree T;
             const int32_t root = nd(nodes, 0, sc, T);
             // postorder -> fronts (elimination positions in the same order as a sequential run)

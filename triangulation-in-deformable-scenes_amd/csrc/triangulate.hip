@@ -1,14 +1,14 @@
 // triangulate.hip — the map-point producer in front of the solver, one thread per correspondence
 // (SURVEY §8(f) row 4): Mapping::triangulateSimulatedMapPoints (reference
-// Modules/Mapping/Mapping.cc:280-349) with the Simulation.yaml settings Triangulation.method
-// "NRSLAM" and seed.location "FarPoints":
+// Modules/Mapping/Mapping.cc:280-349); with the Simulation.yaml settings Triangulation.method
+// "NRSLAM" and seed.location "FarPoints" that is k_triangulate<NRSLAM, FarPoints>:
 //   xn = normalize(KannalaBrandt8::unproject(uv))            KannalaBrandt8.cc:51-83 (Newton on theta,
 //                                                             10 steps, stop at |fix| < 1e-6)
 //   triangulateNRSLAM(xn1, xn2, T1w, T2w, "FarPoints")       Geometry.cc:103-153
 //   isValidParallax: both depths >= 0, cos(ray1, ray2) <= minCos   Mapping.cc:351-366
 // Everything in fp32 without FMA contraction, as the reference's Eigen/Sophus float code.
 //
-// k_triangulate is the same producer for every seed the reference defines (useTriangulationMethod,
+// k_triangulate is that producer for every seed the reference defines (useTriangulationMethod,
 // Geometry.cc:216-230): triangulateNRSLAM with TwoPoints / FarPoints / in-rays (:103-153) and
 // triangulateClassic with TwoPoints / in-rays (:62-101).  k_reconstruct_points is the real-image
 // producer, MonocularMapInitializer::reconstructPoints (MonocularMapInitializer.cc:303-367), which also
@@ -17,9 +17,15 @@
 // Method and location are template parameters: a launch runs one variant, no thread diverges on them.
 #include <hip/hip_runtime.h>
 
-#include "../../include/deftri.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+
+#include "dev_arena.h"
 #include "device_math.h"
-#include "kernels.h"
+#include "pose_host.h"
+#include "triangulate.h"
 
 namespace deftri {
 namespace dev {
@@ -37,44 +43,8 @@ __device__ __forceinline__ V3 rotT(const float *T, V3 p) {     // R^T p
 }
 __device__ __forceinline__ V3 xform(const float *T, V3 p) { return add(rot(T, p), v3(T[3], T[7], T[11])); }
 
-// Tp: T1w, T2w, T21 = T2w T1w^-1, T2w^-1 (3x4 each, formed on the host as Sophus does)
-__global__ void k_triangulate_nrslam(int n, const float *__restrict__ uv1, const float *__restrict__ uv2,
-                                     const float *__restrict__ kb1, const float *__restrict__ kb2,
-                                     const float *__restrict__ Tp, float min_cos, float *__restrict__ x1out,
-                                     float *__restrict__ x2out, uint8_t *__restrict__ valid) {
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= n) return;
-    const float *T1w = Tp, *T2w = Tp + 12, *T21 = Tp + 24, *T2i = Tp + 36;
-    const V3 xn1 = normalized(kb8_unproject(kb1, uv1[2 * i], uv1[2 * i + 1]));   // Mapping.cc:297-298
-    const V3 xn2 = normalized(kb8_unproject(kb2, uv2[2 * i], uv2[2 * i + 1]));
-    // triangulateNRSLAM (Geometry.cc:103-153), FarPoints
-    const V3 f0 = normalized(xn1), f1 = normalized(xn2);
-    const V3 t = v3(T21[3], T21[7], T21[11]);
-    const V3 Rf0 = rot(T21, f0);
-    const V3 p = cross(Rf0, f1), q = cross(Rf0, t), r = cross(f1, t);
-    const float pn = nrm(p), qn = nrm(q), rn = nrm(r);
-    const float lambda0 = rn / pn, lambda1 = qn / pn;
-    V3 point0 = scl(lambda0, Rf0);
-    const V3 point1 = scl(lambda1, f1);
-    const V3 x1 = scl(qn / (qn + rn), add(t, scl(rn / pn, add(Rf0, f1))));
-    point0 = add(t, point0);
-    const V3 p3D1 = add(point0, sub(point0, x1));
-    const V3 p3D2 = add(point1, sub(point1, x1));
-    const V3 X1 = xform(T2i, p3D1), X2 = xform(T2i, p3D2);                    // T2w.inverse() * p
-    // isValidParallax (Mapping.cc:351-366)
-    const V3 c1 = xform(T1w, X1), c2 = xform(T2w, X2);
-    const V3 ray1 = normalized(rotT(T1w, xn1)), ray2 = normalized(rotT(T2w, xn2));
-    const float cosp = dot(ray1, ray2) / (nrm(ray1) * nrm(ray2));
-    const bool fin = isfinite(X1.x) && isfinite(X1.y) && isfinite(X1.z) && isfinite(X2.x) && isfinite(X2.y) &&
-                     isfinite(X2.z);
-    valid[i] = (c1.z >= 0.0f && c2.z >= 0.0f && cosp <= min_cos && fin) ? 1 : 0;
-    x1out[3 * i] = X1.x; x1out[3 * i + 1] = X1.y; x1out[3 * i + 2] = X1.z;
-    x2out[3 * i] = X2.x; x2out[3 * i + 1] = X2.y; x2out[3 * i + 2] = X2.z;
-}
-
 // ---- the seeds: p3D1 / p3D2 in camera 2's frame (the callers apply T2w.inverse()) ----------------
-// triangulateNRSLAM (Geometry.cc:103-153); LOC FarPoints is k_triangulate_nrslam's body operation for
-// operation
+// triangulateNRSLAM (Geometry.cc:103-153)
 template <int LOC>
 __device__ __forceinline__ void tri_nrslam(V3 xn1, V3 xn2, const float *T21, V3 &p3D1, V3 &p3D2) {
     const V3 f0 = normalized(xn1), f1 = normalized(xn2);
@@ -166,7 +136,7 @@ __device__ __forceinline__ float cos_world_rays(const float *T1w, const float *T
     return dot(ray1, ray2) / (nrm(ray1) * nrm(ray2));
 }
 
-// k_triangulate_nrslam for any defined (method, location); Tp as there
+// Tp: T1w, T2w, T21 = T2w T1w^-1, T2w^-1 (3x4 each, formed on the host as Sophus does)
 template <int METHOD, int LOC>
 __global__ void k_triangulate(int n, const float *__restrict__ uv1, const float *__restrict__ uv2,
                               const float *__restrict__ kb1, const float *__restrict__ kb2,
@@ -291,14 +261,6 @@ k_init_depth_scales(int n, const float *__restrict__ uv1, const float *__restric
 
 }  // namespace dev
 
-void launch_triangulate_nrslam(int n, const float *uv1, const float *uv2, const float *kb1, const float *kb2,
-                               const float *Tp, float min_cos, float *x1, float *x2, uint8_t *valid, hipStream_t st) {
-    if (n > 0)
-        hipLaunchKernelGGL(dev::k_triangulate_nrslam, dim3((n + 255) / 256), dim3(256), 0, st, n, uv1, uv2, kb1, kb2,
-                           Tp, min_cos, x1, x2, valid);
-}
-
-
 namespace {
 template <int METHOD>
 bool triangulate_loc(int loc, int n, const float *uv1, const float *uv2, const float *kb1, const float *kb2, const float *Tp,
@@ -327,8 +289,9 @@ bool reconstruct_loc(int loc, int n, const float *uv1, const float *uv2, const f
 #undef REC
     return false;
 }
-}  // namespace
 
+// k_triangulate of (DEFTRI_TRI_*, DEFTRI_LOC_*).  false: the reference defines no such variant (nothing
+// launched)
 bool launch_triangulate(int method, int loc, int n, const float *uv1, const float *uv2, const float *kb1, const float *kb2,
                         const float *Tp, float min_cos, float *x1, float *x2, uint8_t *valid, hipStream_t st) {
     if (n <= 0) return true;
@@ -341,6 +304,7 @@ bool launch_triangulate(int method, int loc, int n, const float *uv1, const floa
     return false;
 }
 
+// k_reconstruct_points likewise
 bool launch_reconstruct_points(int method, int loc, int n, const float *uv1, const float *uv2, const float *kb1,
                                const float *kb2, const float *Tp, float depth_limit, int checks, float *x1, float *x2,
                                uint8_t *status, float *cosp, hipStream_t st) {
@@ -355,13 +319,194 @@ bool launch_reconstruct_points(int method, int loc, int n, const float *uv1, con
     return false;
 }
 
-void launch_init_depth_scales(int n, const float *uv1, const float *uv2, const float *x3d1, const float *x3d2,
-                              const float *kb1, const float *kb2, const float *Tp, float min_cos, const DepthImageDev &im1,
-                              const DepthImageDev &im2, uint8_t *keep, uint8_t *pix_status, double *part, hipStream_t st) {
-    if (n > 0)
-        hipLaunchKernelGGL(dev::k_init_depth_scales, dim3((n + 255) / 256), dim3(256), 0, st, n, uv1, uv2, x3d1, x3d2, kb1, kb2,
-                           Tp, min_cos, im1.pixels, im1.rows, im1.cols, im1.scale, im2.pixels, im2.rows, im2.cols, im2.scale,
-                           keep, pix_status, part);
+// T1w, T2w, T21 = T2w * T1w.inverse(), T2w.inverse() (3x4 each), as Sophus forms them
+void triangulation_poses(const float *T1w, const float *T2w, float Tp[48]) {
+    float T1i[12];
+    std::memcpy(Tp, T1w, 12 * sizeof(float));
+    std::memcpy(Tp + 12, T2w, 12 * sizeof(float));
+    pose34_inverse(T1w, T1i);
+    pose34_product(T2w, T1i, Tp + 24);
+    pose34_inverse(T2w, Tp + 36);
+}
+
+// "" when the reference defines the variant, else why it does not
+const char *undefined_seed(int32_t method, int32_t location, bool simulated) {
+    if (method != DEFTRI_TRI_CLASSIC && method != DEFTRI_TRI_NRSLAM && method != DEFTRI_TRI_ORBSLAM && method != DEFTRI_TRI_DEPTH)
+        return "unknown triangulation method";
+    if (location != DEFTRI_LOC_INRAYS && location != DEFTRI_LOC_TWOPOINTS && location != DEFTRI_LOC_FARPOINTS)
+        return "unknown seed location";
+    if (method == DEFTRI_TRI_ORBSLAM)
+        return "Triangulation.method ORBSLAM is undefined in the reference: triangulateORBSLAM (Geometry.cc:155-186) never "
+               "writes x3D_1 / x3D_2";
+    if (method == DEFTRI_TRI_DEPTH && simulated)
+        return "Triangulation.method DepthMeasurement is undefined in the simulated entry: its inputs are "
+               "CameraModel::unproject(x, d), an unset vector (CameraModel.h:128-135); it is defined in "
+               "deftri_reconstruct_points (Geometry.cc:189-214)";
+    return "";
+}
+
+// the inputs every triangulation kernel reads: the pixel pairs, both calibrations, the four poses
+struct TriInputs {
+    float *uv1, *uv2, *k1, *k2, *T;
+    TriInputs(DevArena &A, size_t N) {
+        A.add(&uv1, 2 * N); A.add(&uv2, 2 * N); A.add(&k1, 8); A.add(&k2, 8); A.add(&T, 48);
+    }
+    // after A.commit(); Tp stays the caller's until the stream is synchronized
+    void upload(size_t N, const float *h_uv1, const float *h_uv2, const float *kb8_1, const float *kb8_2, const float *Tp,
+                hipStream_t st) const {
+        hipMemcpyAsync(uv1, h_uv1, 8 * N, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(uv2, h_uv2, 8 * N, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(k1, kb8_1, 32, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(k2, kb8_2, 32, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(T, Tp, 48 * sizeof(float), hipMemcpyHostToDevice, st);
+    }
+};
+
+int fail(std::string &err, int code, const std::string &what) {
+    err = what;
+    return code;
+}
+}  // namespace
+
+int triangulate(int device, hipStream_t st, int32_t n, int32_t method, int32_t location, const float *uv1, const float *uv2,
+                const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w, float min_cos, float *x3d_1,
+                float *x3d_2, uint8_t *valid, std::string &err) {
+    const char *why = undefined_seed(method, location, true);
+    if (*why) return fail(err, DEFTRI_E_ARG, why);
+    if (device < 0) return fail(err, DEFTRI_E_NODEVICE, "host-only context");
+    if (n == 0) return 0;
+    hipSetDevice(device);
+    float Tp[48];
+    triangulation_poses(T1w, T2w, Tp);
+    const size_t N = (size_t)n;
+    DevArena A;
+    TriInputs in(A, N);
+    float *d_x1, *d_x2;
+    uint8_t *d_v;
+    A.add(&d_x1, 3 * N); A.add(&d_x2, 3 * N); A.add(&d_v, N);
+    if (!A.commit()) return fail(err, DEFTRI_E_HIP, "triangulate: allocation failed");
+    in.upload(N, uv1, uv2, kb8_1, kb8_2, Tp, st);
+    if (!launch_triangulate(method, location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, min_cos, d_x1, d_x2, d_v, st)) {
+        hipStreamSynchronize(st);
+        return fail(err, DEFTRI_E_ARG, "triangulate: no kernel for this (method, location)");
+    }
+    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(valid, d_v, N, hipMemcpyDeviceToHost, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(err, DEFTRI_E_HIP, std::string("triangulate: ") + hipGetErrorString(e));
+    return 0;
+}
+
+int reconstruct_points(int device, hipStream_t st, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                       const float *kb8_2, const float *T1w, const float *T2w, const deftri_reconstruct_params &params,
+                       float *x3d_1, float *x3d_2, uint8_t *status, float *cos_parallax, deftri_reconstruct_report *report,
+                       std::string &err) {
+    const char *why = undefined_seed(params.method, params.location, false);
+    if (*why) return fail(err, DEFTRI_E_ARG, why);
+    if (device < 0) return fail(err, DEFTRI_E_NODEVICE, "host-only context");
+    std::memset(report, 0, sizeof(*report));
+    if (n == 0) return 0;
+    hipSetDevice(device);
+    float Tp[48];
+    triangulation_poses(T1w, T2w, Tp);
+    const size_t N = (size_t)n;
+    DevArena A;
+    TriInputs in(A, N);
+    float *d_x1, *d_x2, *d_c;
+    uint8_t *d_s;
+    A.add(&d_x1, 3 * N); A.add(&d_x2, 3 * N); A.add(&d_s, N); A.add(&d_c, N);
+    if (!A.commit()) return fail(err, DEFTRI_E_HIP, "reconstruct_points: allocation failed");
+    in.upload(N, uv1, uv2, kb8_1, kb8_2, Tp, st);
+    if (!launch_reconstruct_points(params.method, params.location, n, in.uv1, in.uv2, in.k1, in.k2, in.T, params.depth_limit,
+                                   params.checks ? 1 : 0, d_x1, d_x2, d_s, d_c, st)) {
+        hipStreamSynchronize(st);
+        return fail(err, DEFTRI_E_ARG, "reconstruct_points: no kernel for this (method, location)");
+    }
+    hipMemcpyAsync(x3d_1, d_x1, 12 * N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(x3d_2, d_x2, 12 * N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(status, d_s, N, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(cos_parallax, d_c, 4 * N, hipMemcpyDeviceToHost, st);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(err, DEFTRI_E_HIP, std::string("reconstruct_points: ") + hipGetErrorString(e));
+    // the acceptance (:370-394) from the copied-back status and cosines
+    std::vector<float> par;
+    int64_t *counters[6] = {nullptr, &report->n_nonfinite, &report->n_depth1, &report->n_err1, &report->n_depth2,
+                            &report->n_err2};
+    for (size_t i = 0; i < N; i++) {
+        if (status[i] == 0) par.push_back(cos_parallax[i]);
+        else if (status[i] <= 5) ++*counters[status[i]];
+    }
+    report->n_triangulated = 2 * (int64_t)par.size();
+    if (par.empty()) return 0;
+    const size_t idx = std::min<size_t>(50, par.size() - 1);
+    std::nth_element(par.begin(), par.begin() + (std::ptrdiff_t)idx, par.end());      // sorted order's element idx
+    const float cosp = par[idx];
+    if (cosp < 0.0f || cosp > 1.0f) return 0;                 // "Parallax must be between 0 and 1": not accepted
+    const float radians = acosf(cosp);
+    const float degrees = (float)((double)radians * (180.0 / M_PI));
+    report->parallax_deg = degrees;
+    report->accepted = (report->n_triangulated >= 25 && degrees > params.min_parallax) ? 1 : 0;
+    return 0;
+}
+
+int init_depth_scales(int device, hipStream_t st, DepthImages &images, int64_t kf_id_1, int64_t kf_id_2, int32_t n,
+                      const float *uv1, const float *uv2, const float *x3d_1, const float *x3d_2, const float *kb8_1,
+                      const float *kb8_2, const float *T1w, const float *T2w, float min_cos, uint8_t *keep, double *scale_1,
+                      double *scale_2, int64_t *n_points, std::string &err) {
+    if (device < 0) return fail(err, DEFTRI_E_NODEVICE, "host-only context");
+    hipSetDevice(device);
+    DepthImageDev im[2];
+    const int64_t ids[2] = {kf_id_1, kf_id_2};
+    for (int c = 0; c < 2; c++)
+        if (!images.device_image(ids[c], &im[c].pixels, &im[c].rows, &im[c].cols, &im[c].scale))
+            return fail(err, DEFTRI_E_ARG, "Depth image is not initialized: keyframe " + std::to_string(ids[c]));
+    const size_t N = (size_t)n, nb = (N + 255) / 256;
+    double sum[3] = {0, 0, 0};
+    if (n > 0) {
+        float Tp[48];
+        triangulation_poses(T1w, T2w, Tp);
+        DevArena A;
+        TriInputs in(A, N);
+        float *d_x1, *d_x2;
+        uint8_t *d_keep, *d_st;
+        double *d_part;
+        A.add(&d_x1, 3 * N); A.add(&d_x2, 3 * N); A.add(&d_keep, N); A.add(&d_st, N); A.add(&d_part, 3 * nb);
+        if (!A.commit()) return fail(err, DEFTRI_E_HIP, "init_depth_scales: allocation failed");
+        std::vector<uint8_t> h_keep(N), h_st(N);
+        std::vector<double> part(3 * nb);
+        in.upload(N, uv1, uv2, kb8_1, kb8_2, Tp, st);
+        hipMemcpyAsync(d_x1, x3d_1, 12 * N, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(d_x2, x3d_2, 12 * N, hipMemcpyHostToDevice, st);
+        // keep [n], pix_status [n], part [3 * ceil(n / 256)] = per workgroup sum 1, sum 2, count
+        hipLaunchKernelGGL(dev::k_init_depth_scales, dim3((unsigned)nb), dim3(256), 0, st, n, in.uv1, in.uv2, d_x1, d_x2, in.k1,
+                           in.k2, in.T, min_cos, im[0].pixels, im[0].rows, im[0].cols, im[0].scale, im[1].pixels, im[1].rows,
+                           im[1].cols, im[1].scale, d_keep, d_st, d_part);
+        hipMemcpyAsync(h_keep.data(), d_keep, N, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h_st.data(), d_st, N, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(part.data(), d_part, 24 * nb, hipMemcpyDeviceToHost, st);
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(err, DEFTRI_E_HIP, std::string("init_depth_scales: ") + hipGetErrorString(e));
+        for (size_t i = 0; i < N; i++) {
+            if (!h_st[i]) continue;
+            const int c = (h_st[i] & 15) ? 0 : 1;
+            const float *px = (c ? uv2 : uv1) + 2 * i;
+            char buf[200];
+            std::snprintf(buf, sizeof(buf), "keyframe %lld correspondence %zu: pixel (%g, %g) %s", (long long)ids[c], i,
+                          (double)px[0], (double)px[1],
+                          ((c ? h_st[i] >> 4 : h_st[i] & 15) == 1) ? "is out of range of the depth image"
+                                                                   : "reads outside the depth image");
+            return fail(err, DEFTRI_E_ARG, buf);
+        }
+        for (size_t b = 0; b < nb; b++)                        // workgroup order
+            for (int q = 0; q < 3; q++) sum[q] += part[3 * b + q];
+        std::memcpy(keep, h_keep.data(), N);
+    }
+    *n_points = (int64_t)sum[2];
+    *scale_1 = sum[0] / sum[2];                                // n_points == 0: 0 / 0 = NaN, as the reference (:250-251)
+    *scale_2 = sum[1] / sum[2];
+    return 0;
 }
 
 }  // namespace deftri
+

@@ -204,6 +204,25 @@ def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
 
 
+def _f32(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def _fp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _u8p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _pixel_pairs(uv1, uv2):
+    """Two matched pixel lists as float32 [n, 2] each, and n."""
+    uv1, uv2 = _f32(uv1).reshape(-1, 2), _f32(uv2).reshape(-1, 2)
+    assert len(uv2) == len(uv1)
+    return uv1, uv2, len(uv1)
+
+
 class Context:
     """One solver context (one per host thread).  device < 0 = host-only (graph / analysis)."""
 
@@ -526,32 +545,18 @@ class Context:
     def triangulate_nrslam(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, min_cos=0.9998):
         """Mapping::triangulateSimulatedMapPoints (NRSLAM, FarPoints) on the device.  T1w/T2w: SE3f
         (R, t).  Returns (x3d_1 [n,3], x3d_2 [n,3], valid [n] bool), fp32."""
-        f = lambda a: np.ascontiguousarray(a, np.float32)
-        uv1, uv2 = f(uv1), f(uv2)
-        n = len(uv1)
-        T = [f(np.concatenate([np.asarray(Tx.R, np.float32), np.asarray(Tx.t, np.float32)[:, None]], 1)) for Tx in (T1w, T2w)]
-        k1, k2 = f(kb8_1), f(kb8_2)
-        x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32); v = np.zeros(n, np.uint8)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._check(self.lib.deftri_triangulate_nrslam(self.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(T[0]), fp(T[1]),
-                                                      float(min_cos), fp(x1), fp(x2),
-                                                      v.ctypes.data_as(C.POINTER(C.c_uint8))))
-        return x1, x2, v.astype(bool)
+        return self.triangulate(uv1, uv2, kb8_1, kb8_2, T1w, T2w, min_cos, method="NRSLAM", location="FarPoints")
 
     def triangulate(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, min_cos=0.9998, method="NRSLAM", location="FarPoints"):
         """triangulate_nrslam for any (Triangulation.method, Triangulation.seed.location) the reference
         defines (deftri_triangulate); the strings map as the reference's `if` chains do.  "ORBSLAM" and
         "DepthMeasurement" raise DeftriError (DEFTRI_E_ARG): undefined in the reference (deftri.h)."""
-        f = lambda a: np.ascontiguousarray(a, np.float32)
-        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
-        n = len(uv1)
-        assert len(uv2) == n
-        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), _f32(kb8_1), _f32(kb8_2)
         x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32); v = np.zeros(n, np.uint8)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._check(self.lib.deftri_triangulate(self.h, n, trian_method_code(method), trian_location_code(location), fp(uv1),
-                                                fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb), float(min_cos), fp(x1), fp(x2),
-                                                v.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._check(self.lib.deftri_triangulate(self.h, n, trian_method_code(method), trian_location_code(location), _fp(uv1),
+                                                _fp(uv2), _fp(k1), _fp(k2), _fp(Ta), _fp(Tb), float(min_cos), _fp(x1), _fp(x2),
+                                                _u8p(v)))
         return x1, x2, v.astype(bool)
 
     def reconstruct_points(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, method="NRSLAM", location="FarPoints", depth_limit=0.0,
@@ -559,21 +564,16 @@ class Context:
         """MonocularMapInitializer::reconstructPoints for matched pixel pairs on the device
         (deftri_reconstruct_points).  Returns (x3d_1 [n,3], x3d_2 [n,3], status [n] uint8, cos_parallax
         [n] float32, report dict)."""
-        f = lambda a: np.ascontiguousarray(a, np.float32)
-        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
-        n = len(uv1)
-        assert len(uv2) == n
-        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), _f32(kb8_1), _f32(kb8_2)
         prm = _abi.ReconstructParams(method=trian_method_code(method), location=trian_location_code(location),
                                      checks=1 if checks else 0, depth_limit=float(depth_limit),
                                      min_parallax=float(min_parallax))
         rep = _abi.ReconstructReport()
         x1 = np.zeros((n, 3), np.float32); x2 = np.zeros((n, 3), np.float32)
         st = np.zeros(n, np.uint8); cosp = np.zeros(n, np.float32)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._check(self.lib.deftri_reconstruct_points(self.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb),
-                                                       C.byref(prm), fp(x1), fp(x2), st.ctypes.data_as(C.POINTER(C.c_uint8)),
-                                                       fp(cosp), C.byref(rep)))
+        self._check(self.lib.deftri_reconstruct_points(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2), _fp(Ta), _fp(Tb),
+                                                       C.byref(prm), _fp(x1), _fp(x2), _u8p(st), _fp(cosp), C.byref(rep)))
         return x1, x2, st, cosp, rep.as_dict()
 
     def init_depth_scales(self, kf_id_1, kf_id_2, uv1, uv2, x3d_1, x3d_2, kb8_1, kb8_2, T1w, T2w, min_cos=0.9998,
@@ -582,19 +582,15 @@ class Context:
         (deftri_init_depth_scales, Mapping.cc:183-254).  Returns (keep [n] bool, scale_1, scale_2,
         n_points); the scales are NaN when n_points == 0.  `out`: a (keep uint8 [n], scales float64 [2],
         n_points int64 [1]) triple to write into instead of new arrays."""
-        f = lambda a: np.ascontiguousarray(a, np.float32)
-        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
-        x1, x2 = f(x3d_1).reshape(-1, 3), f(x3d_2).reshape(-1, 3)
-        n = len(uv1)
-        assert len(uv2) == n and len(x1) == n and len(x2) == n
-        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        x1, x2 = _f32(x3d_1).reshape(-1, 3), _f32(x3d_2).reshape(-1, 3)
+        assert len(x1) == n and len(x2) == n
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), _f32(kb8_1), _f32(kb8_2)
         keep, sc, npts = out if out is not None else (np.zeros(n, np.uint8), np.zeros(2, np.float64), np.zeros(1, np.int64))
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
         s1 = C.cast(sc.ctypes.data, C.POINTER(C.c_double))
         s2 = C.cast(sc.ctypes.data + 8, C.POINTER(C.c_double))
-        self._check(self.lib.deftri_init_depth_scales(self.h, int(kf_id_1), int(kf_id_2), n, fp(uv1), fp(uv2), fp(x1), fp(x2),
-                                                      fp(k1), fp(k2), fp(Ta), fp(Tb), float(min_cos),
-                                                      keep.ctypes.data_as(C.POINTER(C.c_uint8)), s1, s2,
+        self._check(self.lib.deftri_init_depth_scales(self.h, int(kf_id_1), int(kf_id_2), n, _fp(uv1), _fp(uv2), _fp(x1), _fp(x2),
+                                                      _fp(k1), _fp(k2), _fp(Ta), _fp(Tb), float(min_cos), _u8p(keep), s1, s2,
                                                       npts.ctypes.data_as(C.POINTER(C.c_int64))))
         return keep.astype(bool), float(sc[0]), float(sc[1]), int(npts[0])
 
@@ -628,17 +624,12 @@ class Context:
     def epipolar_inliers(self, uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th):
         """The inlier mask of MonocularMapInitializer::initialize with Triangulation.checks for matched
         pixel pairs (deftri_epipolar_inliers).  Returns (inlier bool [n], err float32 [n], score)."""
-        f = lambda a: np.ascontiguousarray(a, np.float32)
-        uv1, uv2 = f(uv1).reshape(-1, 2), f(uv2).reshape(-1, 2)
-        n = len(uv1)
-        assert len(uv2) == n
-        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), f(kb8_1), f(kb8_2)
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        Ta, Tb, k1, k2 = _pose34(T1w), _pose34(T2w), _f32(kb8_1), _f32(kb8_2)
         inl = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
         score = C.c_int32(0)
-        fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-        self._check(self.lib.deftri_epipolar_inliers(self.h, n, fp(uv1), fp(uv2), fp(k1), fp(k2), fp(Ta), fp(Tb),
-                                                     float(epipolar_th), inl.ctypes.data_as(C.POINTER(C.c_uint8)), fp(err),
-                                                     C.byref(score)))
+        self._check(self.lib.deftri_epipolar_inliers(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2), _fp(Ta), _fp(Tb),
+                                                     float(epipolar_th), _u8p(inl), _fp(err), C.byref(score)))
         return inl.astype(bool), err, int(score.value)
 
     def debug_feature_grid_cells(self, grid, uv):

@@ -241,7 +241,7 @@ def triangulate_simulated(kb8_1, kb8_2, uv1, uv2, T1w, T2w, min_cos=0.9998, meth
     """Mapping::triangulateSimulatedMapPoints (Mapping.cc:280-349) with isValidParallax (:351-366),
     vectorised fp32 host restatement, for the Triangulation.method / seed.location the reference
     defines there (NRSLAM and Classic; ORBSLAM and DepthMeasurement raise ValueError).  The device
-    version is deftri_triangulate (deftri_triangulate_nrslam for the default NRSLAM, FarPoints).
+    version is deftri_triangulate (deftri_triangulate_nrslam forwards to its NRSLAM, FarPoints).
     Returns (x3d_1, x3d_2, valid)."""
     meth, loc = seed_method(method), seed_location(method, location)
     if meth == "ORBSLAM":

@@ -399,7 +399,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    2 deftri_report, 3 deftri_keyframe, 4 deftri_map, 5 deftri_ba_desc, 6 deftri_pixels_error,
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
-   14 deftri_feature_grid (13 is unassigned and answers -1, like every other index). */
+   14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report (13 is unassigned and answers
+   -1, like every other index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -702,6 +703,97 @@ int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const 
    The order inside a cell is not defined on the device. */
 int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n, const float *uv,
         int32_t *cell_start, int32_t *cell_keys);
+
+/* ---- from an image to keypoints: FAST::extract (Modules/Features/FAST.cc:81-118, FAST.h:52-97) --- */
+#define DEFTRI_FAST_MAX_LEVELS 16
+typedef struct deftri_fast_params {
+    int32_t n_scales; float scale_factor;   /* FeatureExtractor.nScales / .fScaleFactor */
+    int32_t n_max_features;                 /* nMaxFeatures_: the reference passes 2 * nFeatures (Mapping.cc:46) */
+    int32_t th_fast, min_th_fast;           /* 10 and 4 there */
+    int32_t max_keys;                       /* the capacity of the caller's vKeys: nFeatures (Frame.cc:36) */
+} deftri_fast_params;
+
+typedef struct deftri_fast_report {
+    int32_t n_levels, n_keys;
+    int32_t level_cols[DEFTRI_FAST_MAX_LEVELS], level_rows[DEFTRI_FAST_MAX_LEVELS];
+    int32_t features_per_level[DEFTRI_FAST_MAX_LEVELS];   /* vFeaturesPerLevel_ */
+    int32_t n_candidates[DEFTRI_FAST_MAX_LEVELS];         /* vToDistributeKeys */
+    int32_t n_octree[DEFTRI_FAST_MAX_LEVELS];             /* distributeOctTree's result */
+    int32_t n_after_mask[DEFTRI_FAST_MAX_LEVELS];         /* ... of which outside the dilated mask */
+    int32_t n_fallback_cells[DEFTRI_FAST_MAX_LEVELS];     /* cells redone at min_th_fast */
+    int32_t n_empty_cells[DEFTRI_FAST_MAX_LEVELS];        /* ... of which still empty */
+    int32_t n_truncated[DEFTRI_FAST_MAX_LEVELS];          /* unmasked keypoints past max_keys */
+    int32_t round_trips;                 /* blocking device-to-host copies of the call (0 on a host-only context) */
+    int32_t reserved;
+    double ms_resize, ms_cells;          /* device: the kernels' time between events (the resize with its uploads) */
+    double ms_octree, ms_keypoints;      /* host clock: the octree; the mask reads, orientation and assembly */
+    double ms_total;                     /* host clock over the call */
+} deftri_fast_report;
+
+/* FAST::extract of an 8-bit single-channel image [rows x cols, row stride in bytes], restated as it
+   stands.  border_mask: FeatureExtractor.imageBoderMask decoded by the caller (uint8, the image's size),
+   or NULL for the reference's empty imread.  Outputs, each of capacity max_keys, in the reference's
+   order (level by level, inside a level distributeOctTree's list after the mask filter): uv [2 * n]
+   = pt * vScaleFactor_[octave], octave, angle (degrees), response, size = int(31 * vScaleFactor_[level]);
+   *n_keys the number written.  report may be NULL.
+     1. Scale tables and vFeaturesPerLevel_ (FAST.h:54-78) in float; cvRound rounds half to even.
+     2. Pyramid (FAST.cc:120-139): level 0 is the image, level l = cv::resize(level l - 1,
+        Size(cvRound(cols * inv[l]), cvRound(rows * inv[l])), INTER_LINEAR); the 19-pixel reflected border
+        is never read by extract and is not built.  The resize is OpenCV's 8-bit fixed-point bilinear:
+        scale = src / dst in double; per destination index d, f = float((d + 0.5) * scale - 0.5),
+        s = floor(f), f -= s; s < 0: s = 0, f = 0; s >= src - 1: s = src - 1, f = 0, both taps on that
+        pixel; weights (cvRound((1 - f) * 2048), cvRound(f * 2048)); h = S[s] * a0 + S[s + 1] * a1 in int;
+        dst = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2.  A level that halves the one
+        above it exactly on both axes takes OpenCV's area path instead: DEFTRI_E_ARG.
+     3. Cells (:141-203): borders 16 and size - 16, W = 30, nCols, nRows, wCell, hCell, the + 6 overlap,
+        the two `continue` tests and the clamps as written.  cv::FAST(cell, th, true) is FAST-9/16 on the
+        cell alone with the cell's own 3-pixel margin excluded: with s the maximum over the 16 arcs of 9
+        contiguous ring pixels of the arc's minimum of p_i - c, and the same of c - p_i, the pixel is a
+        corner at t iff s > t, its response is s - 1, and it is kept iff that is strictly greater than
+        the responses of its 8 neighbours (0 for one that is no corner at t or lies in the margin);
+        row-major.  A cell with nothing at th_fast is redone whole at min_th_fast (:189-193).  Suppression
+        and fallback are per cell: this is not one FAST over the image.
+     4. distributeOctTree (:243-434) and DivideNode (:24-79), sequential, on the host for both context
+        kinds: nIni = round(width / height), the integer truncations of the node corners, push_front,
+        the two termination tests, the first maximum response per node.  The reference sorts
+        pair<int, ExtractorNode*> and so breaks equal sizes by address; here the most recently created
+        node goes first (what increasing allocation addresses would give) — a choice.
+     5. Mask (:223-234, :470-528): base = image > 240, OR border_mask; level i's mask is its dilation
+        by side x side, side = ceil(2^(i+1) * float(2.5 / 1.5)) * 2 + 5, read at (cvRound(y), cvRound(x))
+        in level coordinates on the full-resolution mask (kept).  A keypoint is dropped iff a base-mask
+        pixel lies in its window clipped to the image; an integral image of the base mask answers that.
+     6. IC_Angle (:443-467) with umax_ (FAST.h:82-96): integer moments over the radius-15 patch, then
+        cv::fastAtan2(float(m_01), float(m_10)): c = min / (max + float(DBL_EPSILON)), the odd polynomial
+        with 57.283627, -18.667446, 8.9140005, -2.5397246, then 90 - a, 180 - a, 360 - a; float, one
+        rounding per operation on host and device.
+     7. Assembly (:98-117): pt *= vScaleFactor_[octave], levels in order, stop at max_keys.
+   OpenCV's parts of 2, 3 and 6 are restated from their definitions and have not been run against an
+   OpenCV build.  A device context equals a host-only one bit for bit.  DEFTRI_E_ARG with a message: a
+   null required pointer, a level below 62 pixels a side (the reference divides by nCols = 0), stride <
+   cols, n_scales outside [1, 16], scale_factor <= 1, thresholds outside 1 <= min_th_fast <= th_fast <=
+   255, max_keys < 0, n_max_features < 0, a border mask of another size (cv::bitwise_or throws), a level
+   whose round(width / height) is 0 (the reference divides by it).  max_keys == 0 returns no keypoints
+   (the outputs may then be NULL). */
+int deftri_fast_extract(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const uint8_t *border_mask /* may be NULL */, int32_t mask_rows, int32_t mask_cols, int32_t mask_stride,
+        const deftri_fast_params *params,
+        float *uv, int32_t *octave, float *angle, float *response, float *size, int32_t *n_keys,
+        deftri_fast_report *report /* may be NULL */);
+
+/* TEST ONLY: one pyramid level's pixels as deftri_fast_extract builds them, packed: out [at most rows *
+   cols], *out_rows x *out_cols written. */
+int deftri_debug_fast_pyramid(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const deftri_fast_params *params, int32_t level, uint8_t *out, int32_t *out_rows, int32_t *out_cols);
+/* TEST ONLY: one level's candidates in front of distributeOctTree (vToDistributeKeys, :197-199), in the
+   reference's order: xy [2 * max_cand] relative to the 16-pixel border, response [max_cand]; *n the
+   number found, of which the first min(*n, max_cand) are written. */
+int deftri_debug_fast_candidates(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const deftri_fast_params *params, int32_t level, int32_t max_cand, int32_t *xy, float *response, int32_t *n);
+/* TEST ONLY: level `level`'s dilated mask (0 .. 15: only the side depends on it) read at n positions
+   xy (x, y) inside the image, by the method deftri_fast_extract uses: hit [n], 1 = masked. */
+int deftri_debug_fast_mask(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const uint8_t *border_mask /* may be NULL */, int32_t mask_rows, int32_t mask_cols, int32_t mask_stride,
+        int32_t level, int32_t n, const int32_t *xy, uint8_t *hit);
 
 /* Build the flattened graph only (no solve): the arrays are owned by the context and stay
    valid until the next call on it.  Used by the parity tests to compare indexing. */

@@ -29,6 +29,7 @@
 #include "../../include/deftri.h"
 #include "graph_builder.h"
 #include "kernels.h"
+#include "features.h"
 #include "matching.h"
 #include "metrics.h"
 #include "pcg.h"
@@ -1499,6 +1500,8 @@ int64_t deftri_sizeof(int32_t which) {
         case 11: return (int64_t)sizeof(deftri_depth_image);
         case 12: return (int64_t)sizeof(deftri_real_abs_errors);
         case 14: return (int64_t)sizeof(deftri_feature_grid);
+        case 15: return (int64_t)sizeof(deftri_fast_params);
+        case 16: return (int64_t)sizeof(deftri_fast_report);
         default: return -1;
     }
 }
@@ -2088,6 +2091,54 @@ int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *
         return fail(ctx, DEFTRI_E_ARG, "feature_grid_cells: null array or negative n");
     std::string err;
     const int rc = feature_grid_cells(ctx->device, ctx->st, *grid, n, uv, cell_start, cell_keys, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+// ---- FAST::extract (features.hip) ----
+int deftri_fast_extract(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                        const uint8_t *border_mask, int32_t mask_rows, int32_t mask_cols, int32_t mask_stride,
+                        const deftri_fast_params *params, float *uv, int32_t *octave, float *angle, float *response, float *size,
+                        int32_t *n_keys, deftri_fast_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || !params || !n_keys || (params->max_keys > 0 && (!uv || !octave || !angle || !response || !size)))
+        return fail(ctx, DEFTRI_E_ARG, "fast_extract: null image, params or output");
+    std::string err;
+    const int rc = fast_extract(ctx->device, ctx->st, FastImage{image, rows, cols, stride},
+                                FastImage{border_mask, mask_rows, mask_cols, mask_stride}, *params, uv, octave, angle, response, size,
+                                n_keys, report, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_debug_fast_pyramid(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                              const deftri_fast_params *params, int32_t level, uint8_t *out, int32_t *out_rows, int32_t *out_cols) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || !params || !out || !out_rows || !out_cols) return fail(ctx, DEFTRI_E_ARG, "fast_extract: null image, params or output");
+    std::string err;
+    const int rc = fast_pyramid_level(ctx->device, ctx->st, FastImage{image, rows, cols, stride}, *params, level, out, out_rows, out_cols,
+                                      err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_debug_fast_candidates(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                                 const deftri_fast_params *params, int32_t level, int32_t max_cand, int32_t *xy, float *response,
+                                 int32_t *n) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || !params || !n || max_cand < 0 || (max_cand > 0 && (!xy || !response)))
+        return fail(ctx, DEFTRI_E_ARG, "fast_extract: null image, params or output");
+    std::string err;
+    const int rc = fast_candidates(ctx->device, ctx->st, FastImage{image, rows, cols, stride}, *params, level, max_cand, xy, response, n,
+                                   err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_debug_fast_mask(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                           const uint8_t *border_mask, int32_t mask_rows, int32_t mask_cols, int32_t mask_stride, int32_t level,
+                           int32_t n, const int32_t *xy, uint8_t *hit) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || n < 0 || (n > 0 && (!xy || !hit))) return fail(ctx, DEFTRI_E_ARG, "fast_extract: null image, params or output");
+    std::string err;
+    const int rc = fast_mask_reads(ctx->device, ctx->st, FastImage{image, rows, cols, stride},
+                                   FastImage{border_mask, mask_rows, mask_cols, mask_stride}, level, n, xy, hit, err);
     return rc ? fail(ctx, rc, err) : 0;
 }
 

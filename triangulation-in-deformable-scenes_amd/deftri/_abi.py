@@ -168,6 +168,29 @@ class FeatureGrid(C.Structure):
                 ("n_scales", i32), ("scale_factor", f32)]
 
 
+FAST_MAX_LEVELS = 16
+
+
+class FastParams(C.Structure):
+    _fields_ = [("n_scales", i32), ("scale_factor", f32), ("n_max_features", i32), ("th_fast", i32), ("min_th_fast", i32),
+                ("max_keys", i32)]
+
+
+class FastReport(C.Structure):
+    _per_level = ("level_cols", "level_rows", "features_per_level", "n_candidates", "n_octree", "n_after_mask",
+                  "n_fallback_cells", "n_empty_cells", "n_truncated")
+    _fields_ = ([("n_levels", i32), ("n_keys", i32)] + [(k, i32 * FAST_MAX_LEVELS) for k in _per_level] +
+                [("round_trips", i32), ("reserved", i32), ("ms_resize", f64), ("ms_cells", f64), ("ms_octree", f64),
+                 ("ms_keypoints", f64), ("ms_total", f64)])
+
+    def as_dict(self):
+        """The per-level arrays cut to n_levels; the times (ms_*) are measurements, not results."""
+        d = {"n_levels": self.n_levels, "n_keys": self.n_keys, "round_trips": self.round_trips}
+        d.update({k: [int(v) for v in getattr(self, k)[:self.n_levels]] for k in self._per_level})
+        d.update({k: getattr(self, k) for k in ("ms_resize", "ms_cells", "ms_octree", "ms_keypoints", "ms_total")})
+        return d
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -80,6 +80,15 @@ def load():
                                               P(C.c_int32)]),
         "deftri_debug_feature_grid_cells": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
                                                       P(C.c_int32)]),
+        "deftri_fast_extract": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(C.c_uint8), C.c_int32,
+                                          C.c_int32, C.c_int32, P(_abi.FastParams), P(C.c_float), P(C.c_int32), P(C.c_float),
+                                          P(C.c_float), P(C.c_float), P(C.c_int32), P(_abi.FastReport)]),
+        "deftri_debug_fast_pyramid": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(_abi.FastParams),
+                                                C.c_int32, P(C.c_uint8), P(C.c_int32), P(C.c_int32)]),
+        "deftri_debug_fast_candidates": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(_abi.FastParams),
+                                                   C.c_int32, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_int32)]),
+        "deftri_debug_fast_mask": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(C.c_uint8), C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_uint8)]),
         "deftri_download": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double)]),
         "deftri_reset_state": (C.c_int, [C.c_void_p]),
         "deftri_eval_chi2": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -178,6 +187,7 @@ EXPORTED = [
     "deftri_measure_real_absolute_map_errors", "deftri_measure_relative_map_errors_images",
     "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
     "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
+    "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
 ]
 
 
@@ -214,6 +224,28 @@ def _fp(a):
 
 def _u8p(a):
     return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _image_u8(a, what="image"):
+    """An 8-bit single-channel image as (array with contiguous rows, rows, cols, row stride in bytes); a row
+    stride wider than the row (a view of a wider image) is passed on as it is."""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2:
+        raise ValueError(f"{what}: an 8-bit single-channel image (uint8 [rows, cols]) is required, got {a.dtype} {a.shape}")
+    if a.shape[1] > 0 and (a.strides[1] != 1 or a.strides[0] < a.shape[1]):
+        a = np.ascontiguousarray(a)
+    return a, a.shape[0], a.shape[1], (a.strides[0] if a.shape[0] > 1 else a.shape[1])
+
+
+class FastResult:
+    """The keypoints of Context.fast_extract, in the reference's order: uv float32 [n, 2], octave int32 [n],
+    angle (degrees), response and size float32 [n], and the report (deftri_fast_report as a dict)."""
+
+    def __init__(self, uv, octave, angle, response, size, report):
+        self.uv, self.octave, self.angle, self.response, self.size, self.report = uv, octave, angle, response, size, report
+
+    def __len__(self):
+        return len(self.octave)
 
 
 def _pixel_pairs(uv1, uv2):
@@ -642,6 +674,69 @@ class Context:
         self._check(self.lib.deftri_debug_feature_grid_cells(self.h, C.byref(g), len(uv), uv.ctypes.data_as(C.POINTER(C.c_float)),
                                                              ip(start), ip(keys)))
         return start, keys[:start[-1]]
+
+    @staticmethod
+    def _fast_params(params):
+        """A deftri_fast_params from an _abi.FastParams or a dict of its fields (features.fast_params)."""
+        return params if isinstance(params, _abi.FastParams) else _abi.FastParams(**params)
+
+    def fast_extract(self, image, params, border_mask=None):
+        """FAST::extract (FAST.cc:81-118) of an 8-bit single-channel image on this context: the device, or the
+        sequential host loops on a host-only one (deftri_fast_extract).  params: features.fast_params(settings)
+        or a dict of deftri_fast_params' fields; border_mask: the decoded FeatureExtractor.imageBoderMask
+        (uint8, the image's size) or None.  Returns a FastResult."""
+        img, rows, cols, stride = _image_u8(image)
+        bm, brows, bcols, bstride = _image_u8(border_mask, "border_mask") if border_mask is not None else (None, 0, 0, 0)
+        p = self._fast_params(params)
+        cap = max(int(p.max_keys), 0)
+        uv = np.zeros((cap, 2), np.float32); octave = np.zeros(cap, np.int32)
+        angle = np.zeros(cap, np.float32); response = np.zeros(cap, np.float32); size = np.zeros(cap, np.float32)
+        n = C.c_int32(0)
+        rep = _abi.FastReport()
+        self._check(self.lib.deftri_fast_extract(self.h, _u8p(img), rows, cols, stride, _u8p(bm) if bm is not None else None, brows,
+                                                 bcols, bstride, C.byref(p), _fp(uv), octave.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                 _fp(angle), _fp(response), _fp(size), C.byref(n), C.byref(rep)))
+        k = int(n.value)
+        return FastResult(uv[:k], octave[:k], angle[:k], response[:k], size[:k], rep.as_dict())
+
+    def debug_fast_pyramid(self, image, params, level):
+        """TEST ONLY: one pyramid level's pixels, uint8 [level rows, level cols] (deftri_debug_fast_pyramid)."""
+        img, rows, cols, stride = _image_u8(image)
+        p = self._fast_params(params)
+        out = np.zeros(max(rows * cols, 1), np.uint8)
+        r, c = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.deftri_debug_fast_pyramid(self.h, _u8p(img), rows, cols, stride, C.byref(p), int(level), _u8p(out),
+                                                       C.byref(r), C.byref(c)))
+        return out[:r.value * c.value].reshape(r.value, c.value).copy()
+
+    def debug_fast_candidates(self, image, params, level):
+        """TEST ONLY: one level's candidates in front of distributeOctTree, in the reference's order
+        (deftri_debug_fast_candidates).  Returns (xy int32 [n, 2] relative to the 16-pixel border, response
+        float32 [n])."""
+        img, rows, cols, stride = _image_u8(image)
+        p = self._fast_params(params)
+        ip = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        n = C.c_int32(0)
+        cap = 0
+        while True:
+            xy = np.zeros((max(cap, 1), 2), np.int32); resp = np.zeros(max(cap, 1), np.float32)
+            self._check(self.lib.deftri_debug_fast_candidates(self.h, _u8p(img), rows, cols, stride, C.byref(p), int(level), cap,
+                                                              ip(xy), _fp(resp), C.byref(n)))
+            if n.value <= cap:
+                return xy[:n.value], resp[:n.value]
+            cap = n.value
+
+    def debug_fast_mask(self, image, level, xy, border_mask=None):
+        """TEST ONLY: level `level`'s dilated reflection / border mask read at positions xy (x, y) of the image, by
+        the method fast_extract uses (deftri_debug_fast_mask).  Returns bool [n]."""
+        img, rows, cols, stride = _image_u8(image)
+        bm, brows, bcols, bstride = _image_u8(border_mask, "border_mask") if border_mask is not None else (None, 0, 0, 0)
+        xy = np.ascontiguousarray(xy, np.int32).reshape(-1, 2)
+        hit = np.zeros(max(len(xy), 1), np.uint8)
+        self._check(self.lib.deftri_debug_fast_mask(self.h, _u8p(img), rows, cols, stride, _u8p(bm) if bm is not None else None,
+                                                    brows, bcols, bstride, int(level), len(xy),
+                                                    xy.ctypes.data_as(C.POINTER(C.c_int32)), _u8p(hit)))
+        return hit[:len(xy)].astype(bool)
 
     def arap_optimization(self, m, rep_weight, global_weight, arap_weight, alpha, beta, depth_error,
                           n_iterations, want_update=True, analytic=False):

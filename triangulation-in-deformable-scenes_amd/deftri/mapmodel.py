@@ -114,7 +114,7 @@ class MapPoint:
 
 class KeyFrame:
     def __init__(self, kid, pose, kb8, n_slots, inv_sigma2, keypoints=None, octaves=None, depth=None, depth_image=None,
-                 image_depth_scale=1.0, ph=None, descriptors=None):
+                 image_depth_scale=1.0, ph=None, descriptors=None, angles=None):
         self.id = int(kid)
         self.pose = pose                              # SE3f, T_cw
         self.kb8 = np.asarray(kb8, dtype=np.float32)
@@ -131,6 +131,8 @@ class KeyFrame:
         self.set_depth_image(depth_image, image_depth_scale, ph)
         # Frame::descriptors_: one 256-bit ORB descriptor per keypoint, uint8 [n_slots, 32] (matching only)
         self.descriptors = None if descriptors is None else np.ascontiguousarray(descriptors, np.uint8).reshape(n_slots, 32)
+        # cv::KeyPoint::angle of FAST::extract (degrees), float32 [n_slots]; what ORB::describe steers by
+        self.angles = None if angles is None else np.ascontiguousarray(angles, np.float32).reshape(n_slots)
 
     def set_depth_image(self, image, image_depth_scale=1.0, ph=None):
         """Frame::setDepthIm + the image's scale and pinhole calibration."""

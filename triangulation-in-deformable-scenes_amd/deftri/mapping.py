@@ -13,10 +13,12 @@ the map construction with the initial depth scales (Mapping.cc:171-254).
                                   the same from keypoints, octaves and descriptors: the match and the inlier
                                   mask on the device (matching.py holds their host restatements), then
                                   monocular_map_initialization
+  set_keypoints_from_features()   a keyframe's keypoints, octaves and angles from FAST::extract's result
+                                  (features.extract / Context.fast_extract)
 
 The poses are inputs, as they are to the reference's RANSAC, which builds E from them in every iteration
 (MonocularMapInitializer.cc:160-163).  Still out of scope: estimating E from the samples (computeE,
-reconstructCameras), FAST and ORB extraction, and the matchers the reference never calls (guidedMatching,
+reconstructCameras), ORB::describe (the descriptors remain the caller's), and the matchers the reference never calls (guidedMatching,
 searchWithProjection, searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
 MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
 the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
@@ -248,3 +250,20 @@ def monocular_map_initialization_from_features(ctx, kf_ref, kf_cur, settings):
         matches[idx[~inlier]] = -1
     m, rep = monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings)
     return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})
+
+
+def set_keypoints_from_features(kf, result):
+    """Frame::vKeys_ of a keyframe from FAST::extract's result (a capi.FastResult): keypoints, octaves and
+    angles of the first len(result) slots; the slots behind them keep zeros, as the reference's vectors of
+    nFeatures elements do.  More keypoints than slots raise ValueError (extract stops at the capacity it is
+    given, max_keys).  Returns the number of keypoints set."""
+    n = len(result)
+    if n > kf.n_slots:
+        raise ValueError(f"{n} keypoints for a keyframe of {kf.n_slots} slots: pass max_keys = n_slots to the extraction")
+    kf.keypoints[:] = 0
+    kf.octaves[:] = 0
+    kf.angles = np.zeros(kf.n_slots, np.float32)
+    kf.keypoints[:n] = result.uv
+    kf.octaves[:n] = result.octave
+    kf.angles[:n] = result.angle
+    return n

@@ -33,7 +33,7 @@ NUMERIC = {
 STRINGS = {
     "Optimization.selection": "selection", "Optimization.weightsSelection": "weights_selection",
     "Triangulation.method": "trian_method", "Triangulation.seed.location": "trian_location",
-    "Experiment.Filepath": "exp_file",
+    "Experiment.Filepath": "exp_file", "FeatureExtractor.imageBoderMask": "border_mask_path",
 }
 
 

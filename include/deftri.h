@@ -399,8 +399,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    2 deftri_report, 3 deftri_keyframe, 4 deftri_map, 5 deftri_ba_desc, 6 deftri_pixels_error,
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
-   14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report (13 is unassigned and answers
-   -1, like every other index). */
+   14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report, 17 deftri_orb_params,
+   18 deftri_orb_report (13 is unassigned and answers -1, like every other index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -794,6 +794,77 @@ int deftri_debug_fast_candidates(deftri_ctx *ctx, const uint8_t *image, int32_t 
 int deftri_debug_fast_mask(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
         const uint8_t *border_mask /* may be NULL */, int32_t mask_rows, int32_t mask_cols, int32_t mask_stride,
         int32_t level, int32_t n, const int32_t *xy, uint8_t *hit);
+
+/* ---- from keypoints to descriptors: ORB::describe (Modules/Features/ORB.cc:20-90, ORB.h:34-68) ---- */
+typedef struct deftri_orb_params {
+    int32_t n_scales; float scale_factor;   /* FeatureExtractor.nScales / .fScaleFactor */
+} deftri_orb_params;
+
+typedef struct deftri_orb_report {
+    int32_t n_levels, n_keys;
+    int32_t level_cols[DEFTRI_FAST_MAX_LEVELS], level_rows[DEFTRI_FAST_MAX_LEVELS];   /* without the border */
+    int32_t n_outside;                   /* keypoints with status 1 */
+    int32_t round_trips;                 /* blocking device-to-host copies of the call (0 on a host-only context) */
+    double ms_pyramid, ms_describe;      /* device: the kernels' time between events (host clock on a host-only context) */
+    double ms_total;                     /* host clock over the call */
+} deftri_orb_report;
+
+/* The sampling pattern of ORB::describe: 512 points as xy [1024] = x0 y0 x1 y1 ..., in the order of the
+   reference's bit_pattern_31_ (ORB.h:70-328), which this library does not carry: the caller passes its own
+   copy.  Comparison c of the descriptor reads points 2c and 2c + 1.  Kept on the context as int8 pairs
+   and uploaded to its device once; a later call replaces it.  DEFTRI_E_ARG with a message: a null
+   pointer, a coordinate outside [-15, 15] (the 31-pixel patch). */
+int deftri_orb_set_pattern(deftri_ctx *ctx, const int32_t *xy /* [1024]: x0 y0 x1 y1 ... */);
+
+/* ORB::describe of n keypoints (uv [2 * n] in full-resolution pixels, octave [n], angle [n] in degrees, as
+   deftri_fast_extract returns them) on an 8-bit single-channel image [rows x cols, row stride in bytes],
+   restated as it stands: desc [n * 32], status [n] (0 described; 1 the reference would read memory it
+   does not own, the descriptor is zero).  report may be NULL.
+     1. Scale tables (ORB.h:39-49) in float: vScaleFactor_[0] = 1, [i] = [i - 1] * scale_factor, inv[i] =
+        1.0f / vScaleFactor_[i].  cvRound rounds half to even.
+     2. Pyramid (ORB.cc:32-52), which is not deftri_fast_extract's: per level l the interior has the size
+        (cvRound((float)cols * inv[l]), cvRound((float)rows * inv[l])), from the original image at every
+        level.  Level 0's interior is the image; level l's is cv::resize(level l - 1's interior, INTER_LINEAR)
+        of the BLURRED level l - 1 (the blur is in place, so it cascades), by the 8-bit fixed-point bilinear
+        of deftri_fast_extract 2. (a level that halves the one above it exactly on both axes: DEFTRI_E_ARG).
+        The 19-pixel border (EDGE_THRESHOLD) on all sides is BORDER_REFLECT_101 of that unblurred interior
+        (-k -> k, n - 1 + k -> n - 1 - k).  Then GaussianBlur(interior, interior, Size(7, 7), 2, 2,
+        BORDER_REFLECT_101) in place on the interior only: it reads up to 3 pixels of the border just
+        written, so it equals a reflect-101 blur of the unblurred interior, and the border keeps the
+        unblurred reflections, which descriptor samples that fall there read (kept).
+     3. The blur this call takes in OpenCV: the source is a sub-matrix and the border type is not
+        isolated, so the bit-exact 8-bit Gaussian is not taken and the call goes to the generic separable
+        filter with getGaussianKernel(7, 2, CV_32F) = exp(-x^2 / 8), x = -3 .. 3, normalized in double and
+        stored as float; for 8-bit data and a symmetric smoothing kernel both 1-D kernels become int by
+        cvRound(k * 256) = 18 34 49 55 49 34 18 (sum 257); the row pass is an int32 sum of 7 products, the
+        column pass an int32 sum of 7 products of row results, then (s + 32768) >> 16 saturated to [0, 255].
+     4. Per keypoint (ORB.cc:24-29, 54-66): x = uv.x * inv[octave], y = uv.y * inv[octave] in float, the centre
+        (cvRound(y), cvRound(x)) in level pixels; angle_r = angle * (float)(CV_PI / 180.f); a = (float)
+        cos((double)angle_r), b = (float)sin((double)angle_r), by the host's libm for both context kinds
+        (whether the reference's unqualified cos(float) is cosf or cos depends on its headers: the double
+        form is a choice).  Pattern point (px, py) is read at row offset cvRound(px * b + py * a) and column
+        offset cvRound(px * a - py * b), in float, one rounding per operation, no contraction.
+     5. Bits (:66-87): byte i bit j = sample(16 i + 2 j) < sample(16 i + 2 j + 1).
+     6. status 1: any of the 512 sample positions outside [-19, cols_l + 19) x [-19, rows_l + 19) of the
+        keypoint's level, decided on the rounded float values before the conversion to int (a non-finite
+        coordinate or angle lands here).
+   OpenCV's parts of 2 and 3 are restated from their definitions and have not been run against an OpenCV
+   build.  A device context equals a host-only one bit for bit; it makes one upload (image, keypoints and
+   resize tables in one copy) and one blocking download (descriptors and status).  DEFTRI_E_ARG with a
+   message: a null required pointer, stride < cols, n_scales outside [1, 16], scale_factor <= 1, an octave
+   outside [0, n_scales), a level with a side below 20 (reflect-101 by 19 needs it), no pattern set, n < 0.
+   n == 0 writes nothing (the arrays may then be NULL). */
+int deftri_orb_describe(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const deftri_orb_params *params, int32_t n, const float *uv, const int32_t *octave, const float *angle,
+        uint8_t *desc /* [n * 32] */, uint8_t *status /* [n] */, deftri_orb_report *report /* may be NULL */);
+
+/* TEST ONLY: one level of deftri_orb_describe's pyramid WITH its 19-pixel border, packed: out [(level rows
+   + 38) * (level cols + 38)] (at most (rows + 38) * (cols + 38)); *out_rows x *out_cols are the bordered
+   sizes.  Needs no pattern. */
+int deftri_debug_orb_pyramid(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+        const deftri_orb_params *params, int32_t level, uint8_t *out, int32_t *out_rows, int32_t *out_cols);
+/* TEST ONLY: the integer 1-D kernel of 3., as the library computes it from that definition: k [7]. */
+int deftri_debug_orb_blur_kernel(int32_t *k);
 
 /* Build the flattened graph only (no solve): the arrays are owned by the context and stay
    valid until the next call on it.  Used by the parity tests to compare indexing. */

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/deftri.h"
 
@@ -32,5 +33,17 @@ int fast_candidates(int device, hipStream_t st, const FastImage &image, const de
 // the reads of level `level`'s dilated mask at n positions xy (x, y) of the full-resolution image
 int fast_mask_reads(int device, hipStream_t st, const FastImage &image, const FastImage &border_mask, int32_t level, int32_t n,
                     const int32_t *xy, uint8_t *hit, std::string &err);
+
+
+// OpenCV's 8-bit fixed-point bilinear resize (deftri.h, deftri_fast_extract 2.), for the other pyramids
+// built from it (orb.hip).  A Tap holds the two source indices of one destination index and their weights.
+namespace dev {
+struct Tap { int s0, s1, a0, a1; };
+}
+std::vector<dev::Tap> resize_taps(int src, int dst);
+// dst [drows x dcols, packed] from src (row pitch spitch): one launch on `st` (xt, yt on the device) / the host loop
+void resize_launch(hipStream_t st, const uint8_t *src, int spitch, uint8_t *dst, int dcols, int drows, const dev::Tap *xt,
+                   const dev::Tap *yt);
+void resize_host(const uint8_t *src, int spitch, uint8_t *dst, int dcols, int drows, const dev::Tap *xt, const dev::Tap *yt);
 
 }  // namespace deftri

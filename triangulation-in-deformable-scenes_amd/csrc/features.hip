@@ -43,7 +43,6 @@ struct Levels {
     int cols[DEFTRI_FAST_MAX_LEVELS], rows[DEFTRI_FAST_MAX_LEVELS];
     int half[DEFTRI_FAST_MAX_LEVELS];   // (side - 1) / 2 of the level's dilation
 };
-struct Tap { int s0, s1, a0, a1; };    // the two source indices and their int16 weights
 struct CellDesc { int level, x0, y0, w, h, offx, offy, pad; };
 
 // OpenCV's 8-bit bilinear: the horizontal pass in int, the vertical pass with its three shifts
@@ -840,6 +839,19 @@ int run(int device, hipStream_t st, const FastImage &im, const FastImage &bm, co
 }
 
 }  // namespace
+
+// ---- the 8-bit bilinear resize, shared with ORB::describe's pyramid (orb.hip) ----
+std::vector<dev::Tap> resize_taps(int src, int dst) { return taps(src, dst); }
+
+void resize_launch(hipStream_t st, const uint8_t *src, int spitch, uint8_t *dst, int dcols, int drows, const dev::Tap *xt,
+                   const dev::Tap *yt) {
+    hipLaunchKernelGGL(dev::k_resize, dim3((dcols + 63) / 64, (drows + 3) / 4), dim3(256), 0, st, src, spitch, dst, dcols, drows, xt, yt);
+}
+
+void resize_host(const uint8_t *src, int spitch, uint8_t *dst, int dcols, int drows, const dev::Tap *xt, const dev::Tap *yt) {
+    for (int y = 0; y < drows; y++)
+        for (int x = 0; x < dcols; x++) dst[(size_t)y * dcols + x] = resize_pixel(src, spitch, xt[x], yt[y]);
+}
 
 int fast_extract(int device, hipStream_t st, const FastImage &image, const FastImage &border_mask, const deftri_fast_params &p,
                  float *uv, int32_t *octave, float *angle, float *response, float *size, int32_t *n_keys,

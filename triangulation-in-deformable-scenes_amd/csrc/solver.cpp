@@ -32,6 +32,7 @@
 #include "features.h"
 #include "matching.h"
 #include "metrics.h"
+#include "orb.h"
 #include "pcg.h"
 #include "pose_host.h"
 #include "spcg.h"
@@ -117,6 +118,7 @@ struct deftri_ctx {
     GraphResult graph;
     std::unique_ptr<GraphDevice> gdev;      // computeR on this context's device (graph_dev.hip)
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
+    OrbState orb;                           // ORB::describe's pattern, device arena and events (orb.hip)
     // speculative lambda lanes (see Lane)
     int analytic_jac = 0;                   // deftri_arap_optimization: 0 g2o numeric (reference), 1 analytic
     bool prof_analytic = false;             // deftri_profile_trial linearizes like the last solve_lm
@@ -1502,6 +1504,8 @@ int64_t deftri_sizeof(int32_t which) {
         case 14: return (int64_t)sizeof(deftri_feature_grid);
         case 15: return (int64_t)sizeof(deftri_fast_params);
         case 16: return (int64_t)sizeof(deftri_fast_report);
+        case 17: return (int64_t)sizeof(deftri_orb_params);
+        case 18: return (int64_t)sizeof(deftri_orb_report);
         default: return -1;
     }
 }
@@ -2140,6 +2144,44 @@ int deftri_debug_fast_mask(deftri_ctx *ctx, const uint8_t *image, int32_t rows, 
     const int rc = fast_mask_reads(ctx->device, ctx->st, FastImage{image, rows, cols, stride},
                                    FastImage{border_mask, mask_rows, mask_cols, mask_stride}, level, n, xy, hit, err);
     return rc ? fail(ctx, rc, err) : 0;
+}
+
+// ---- ORB::describe (orb.hip) ----
+int deftri_orb_set_pattern(deftri_ctx *ctx, const int32_t *xy) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!xy) return fail(ctx, DEFTRI_E_ARG, "orb_set_pattern: null pattern");
+    std::string err;
+    const int rc = orb_set_pattern(ctx->orb, ctx->device, ctx->st, xy, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_orb_describe(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                        const deftri_orb_params *params, int32_t n, const float *uv, const int32_t *octave, const float *angle,
+                        uint8_t *desc, uint8_t *status, deftri_orb_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || !params || (n > 0 && (!uv || !octave || !angle || !desc || !status)))
+        return fail(ctx, DEFTRI_E_ARG, "orb_describe: null image, params, keypoints or output");
+    std::string err;
+    const int rc = orb_describe(ctx->orb, ctx->device, ctx->st, FastImage{image, rows, cols, stride}, *params, n, uv, octave, angle, desc,
+                                status, report, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_debug_orb_pyramid(deftri_ctx *ctx, const uint8_t *image, int32_t rows, int32_t cols, int32_t stride,
+                             const deftri_orb_params *params, int32_t level, uint8_t *out, int32_t *out_rows, int32_t *out_cols) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!image || !params || !out || !out_rows || !out_cols)
+        return fail(ctx, DEFTRI_E_ARG, "orb_describe: null image, params, keypoints or output");
+    std::string err;
+    const int rc = orb_pyramid_level(ctx->orb, ctx->device, ctx->st, FastImage{image, rows, cols, stride}, *params, level, out, out_rows,
+                                     out_cols, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_debug_orb_blur_kernel(int32_t *k) {
+    if (!k) return DEFTRI_E_ARG;
+    orb_blur_kernel(k);
+    return 0;
 }
 
 int deftri_download(deftri_ctx *ctx, double *points, double *scales, double *tg) {

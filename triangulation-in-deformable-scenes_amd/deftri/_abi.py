@@ -191,6 +191,22 @@ class FastReport(C.Structure):
         return d
 
 
+class OrbParams(C.Structure):
+    _fields_ = [("n_scales", i32), ("scale_factor", f32)]
+
+
+class OrbReport(C.Structure):
+    _fields_ = [("n_levels", i32), ("n_keys", i32), ("level_cols", i32 * FAST_MAX_LEVELS), ("level_rows", i32 * FAST_MAX_LEVELS),
+                ("n_outside", i32), ("round_trips", i32), ("ms_pyramid", f64), ("ms_describe", f64), ("ms_total", f64)]
+
+    def as_dict(self):
+        """The level sizes cut to n_levels; the times (ms_*) are measurements, not results."""
+        d = {"n_levels": self.n_levels, "n_keys": self.n_keys, "n_outside": self.n_outside, "round_trips": self.round_trips}
+        d.update({k: [int(v) for v in getattr(self, k)[:self.n_levels]] for k in ("level_cols", "level_rows")})
+        d.update({k: getattr(self, k) for k in ("ms_pyramid", "ms_describe", "ms_total")})
+        return d
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -89,6 +89,12 @@ def load():
                                                    C.c_int32, C.c_int32, P(C.c_int32), P(C.c_float), P(C.c_int32)]),
         "deftri_debug_fast_mask": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(C.c_uint8), C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(C.c_int32), P(C.c_uint8)]),
+        "deftri_orb_set_pattern": (C.c_int, [C.c_void_p, P(C.c_int32)]),
+        "deftri_orb_describe": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(_abi.OrbParams), C.c_int32,
+                                          P(C.c_float), P(C.c_int32), P(C.c_float), P(C.c_uint8), P(C.c_uint8), P(_abi.OrbReport)]),
+        "deftri_debug_orb_pyramid": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(_abi.OrbParams),
+                                               C.c_int32, P(C.c_uint8), P(C.c_int32), P(C.c_int32)]),
+        "deftri_debug_orb_blur_kernel": (C.c_int, [P(C.c_int32)]),
         "deftri_download": (C.c_int, [C.c_void_p, P(C.c_double), P(C.c_double), P(C.c_double)]),
         "deftri_reset_state": (C.c_int, [C.c_void_p]),
         "deftri_eval_chi2": (C.c_int, [C.c_void_p, P(C.c_double)]),
@@ -188,6 +194,7 @@ EXPORTED = [
     "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
     "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
+    "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
 ]
 
 
@@ -246,6 +253,17 @@ class FastResult:
 
     def __len__(self):
         return len(self.octave)
+
+
+class OrbResult:
+    """The descriptors of Context.orb_describe: desc uint8 [n, 32], status uint8 [n] (1: a sample outside the
+    bordered level, the descriptor is zero), and the report (deftri_orb_report as a dict)."""
+
+    def __init__(self, desc, status, report):
+        self.desc, self.status, self.report = desc, status, report
+
+    def __len__(self):
+        return len(self.status)
 
 
 def _pixel_pairs(uv1, uv2):
@@ -737,6 +755,52 @@ class Context:
                                                     brows, bcols, bstride, int(level), len(xy),
                                                     xy.ctypes.data_as(C.POINTER(C.c_int32)), _u8p(hit)))
         return hit[:len(xy)].astype(bool)
+
+    @staticmethod
+    def _orb_params(params):
+        """A deftri_orb_params from an _abi.OrbParams or a dict of its fields (features.orb_params)."""
+        return params if isinstance(params, _abi.OrbParams) else _abi.OrbParams(**params)
+
+    def orb_set_pattern(self, pattern):
+        """The sampling pattern of ORB::describe for this context (deftri_orb_set_pattern): 512 points as an int
+        array of shape (512, 2) or (256, 4) (x0 y0 x1 y1 per comparison), in the order of the reference's
+        bit_pattern_31_, coordinates in [-15, 15].  A later call replaces it."""
+        a = np.asarray(pattern)
+        if a.dtype.kind not in "iu" or a.size != 1024 or a.shape not in ((512, 2), (256, 4)):
+            raise ValueError(f"pattern: an int array of shape (512, 2) or (256, 4) is required, got {a.dtype} {a.shape}")
+        xy = np.ascontiguousarray(a.reshape(-1), np.int32)
+        self._check(self.lib.deftri_orb_set_pattern(self.h, xy.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    def orb_describe(self, image, params, uv, octave, angle):
+        """ORB::describe (ORB.cc:20-90) of the keypoints (uv [n, 2] full-resolution pixels, octave [n], angle [n]
+        in degrees) on an 8-bit single-channel image on this context: the device, or the sequential host loops
+        on a host-only one (deftri_orb_describe).  params: features.orb_params(settings) or a dict of
+        deftri_orb_params' fields.  Needs orb_set_pattern first.  Returns an OrbResult."""
+        img, rows, cols, stride = _image_u8(image)
+        p = self._orb_params(params)
+        uv = _f32(uv).reshape(-1, 2)
+        octave = np.ascontiguousarray(octave, np.int32).reshape(-1)
+        angle = _f32(angle).reshape(-1)
+        n = len(octave)
+        if len(uv) != n or len(angle) != n:
+            raise ValueError(f"{len(uv)} keypoints, {n} octaves and {len(angle)} angles")
+        desc = np.zeros((n, 32), np.uint8); status = np.zeros(n, np.uint8)
+        rep = _abi.OrbReport()
+        self._check(self.lib.deftri_orb_describe(self.h, _u8p(img), rows, cols, stride, C.byref(p), n, _fp(uv),
+                                                 octave.ctypes.data_as(C.POINTER(C.c_int32)), _fp(angle), _u8p(desc), _u8p(status),
+                                                 C.byref(rep)))
+        return OrbResult(desc, status, rep.as_dict())
+
+    def debug_orb_pyramid(self, image, params, level):
+        """TEST ONLY: one level of orb_describe's pyramid with its 19-pixel border, uint8 [level rows + 38, level
+        cols + 38] (deftri_debug_orb_pyramid)."""
+        img, rows, cols, stride = _image_u8(image)
+        p = self._orb_params(params)
+        out = np.zeros((rows + 38) * (cols + 38), np.uint8)
+        r, c = C.c_int32(0), C.c_int32(0)
+        self._check(self.lib.deftri_debug_orb_pyramid(self.h, _u8p(img), rows, cols, stride, C.byref(p), int(level), _u8p(out),
+                                                      C.byref(r), C.byref(c)))
+        return out[:r.value * c.value].reshape(r.value, c.value).copy()
 
     def arap_optimization(self, m, rep_weight, global_weight, arap_weight, alpha, beta, depth_error,
                           n_iterations, want_update=True, analytic=False):

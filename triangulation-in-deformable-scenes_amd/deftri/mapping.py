@@ -13,12 +13,15 @@ the map construction with the initial depth scales (Mapping.cc:171-254).
                                   the same from keypoints, octaves and descriptors: the match and the inlier
                                   mask on the device (matching.py holds their host restatements), then
                                   monocular_map_initialization
+  extract_features()              Mapping::extractFeatures (Mapping.cc:120-129): FAST::extract, then ORB::describe
+                                  with the caller's sampling pattern (features.py)
   set_keypoints_from_features()   a keyframe's keypoints, octaves and angles from FAST::extract's result
-                                  (features.extract / Context.fast_extract)
+                                  (features.extract / Context.fast_extract), optionally its descriptors from
+                                  ORB::describe's
 
 The poses are inputs, as they are to the reference's RANSAC, which builds E from them in every iteration
 (MonocularMapInitializer.cc:160-163).  Still out of scope: estimating E from the samples (computeE,
-reconstructCameras), ORB::describe (the descriptors remain the caller's), and the matchers the reference never calls (guidedMatching,
+reconstructCameras), and the matchers the reference never calls (guidedMatching,
 searchWithProjection, searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
 MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
 the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
@@ -252,14 +255,31 @@ def monocular_map_initialization_from_features(ctx, kf_ref, kf_cur, settings):
     return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})
 
 
-def set_keypoints_from_features(kf, result):
+def extract_features(ctx, image, settings, pattern, border_mask=None):
+    """Mapping::extractFeatures (Mapping.cc:120-129) for one 8-bit grey image on `ctx`: features.extract, then
+    features.describe of its keypoints with the caller's sampling pattern.  Returns (capi.FastResult,
+    capi.OrbResult)."""
+    from . import features
+    keys = features.extract(ctx, image, settings, border_mask)
+    return keys, features.describe(ctx, image, keys, settings, pattern)
+
+
+def set_keypoints_from_features(kf, result, described=None):
     """Frame::vKeys_ of a keyframe from FAST::extract's result (a capi.FastResult): keypoints, octaves and
     angles of the first len(result) slots; the slots behind them keep zeros, as the reference's vectors of
     nFeatures elements do.  More keypoints than slots raise ValueError (extract stops at the capacity it is
-    given, max_keys).  Returns the number of keypoints set."""
+    given, max_keys).  described: ORB::describe's result for the same keypoints (a capi.OrbResult), which
+    also fills KeyFrame.descriptors (uint8 [n_slots, 32], zeros behind the keypoints, as the reference's
+    cv::Mat of nFeatures rows); without it the descriptors stay as they are.  Returns the number of
+    keypoints set."""
     n = len(result)
     if n > kf.n_slots:
         raise ValueError(f"{n} keypoints for a keyframe of {kf.n_slots} slots: pass max_keys = n_slots to the extraction")
+    if described is not None:
+        if len(described) != n:
+            raise ValueError(f"{len(described)} descriptors for {n} keypoints")
+        kf.descriptors = np.zeros((kf.n_slots, 32), np.uint8)
+        kf.descriptors[:n] = described.desc
     kf.keypoints[:] = 0
     kf.octaves[:] = 0
     kf.angles = np.zeros(kf.n_slots, np.float32)

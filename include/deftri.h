@@ -48,6 +48,8 @@ extern "C" {
 #define DEFTRI_E_GRAPH       -6   /* graph construction failed (e.g. < 3 mesh points) */
 #define DEFTRI_E_SEARCH      -7   /* the weight search ended on a failure code (nlopt::opt::optimize
                                      throws there, g2oBundleAdjustment.cc:515): the round is not run */
+#define DEFTRI_E_INTERNAL    -8   /* an invariant of the library's own did not hold (the projection matchers'
+                                     claim rounds did not settle in n + 1) */
 
 /* solver status written into deftri_report.status (g2o SparseOptimizer::optimize semantics) */
 #define DEFTRI_STATUS_OK         0  /* ran all requested iterations */
@@ -400,7 +402,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
    14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report, 17 deftri_orb_params,
-   18 deftri_orb_report (13 is unassigned and answers -1, like every other index). */
+   18 deftri_orb_report, 20 deftri_projection_report (13 and 19 are unassigned and answer -1, like every
+   other index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -703,6 +706,125 @@ int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const 
    The order inside a cell is not defined on the device. */
 int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n, const float *uv,
         int32_t *cell_start, int32_t *cell_keys);
+
+/* ---- map points into a frame by projection: what poseOnlyOptimization's frame is filled by -------- */
+typedef struct deftri_projection_report {
+    int32_t n_points;                    /* points (searchWithProjection) or reference slots (guidedMatching) */
+    int32_t n_matches;                   /* the reference's return value: status 0 */
+    int32_t n_view_cos, n_inv_dist;      /* its vCos and invDist counters: status 1 and 2 */
+    int32_t n_no_candidates;             /* status 3 */
+    int32_t n_rejected;                  /* status 4 */
+    int32_t n_undefined;                 /* status 5 */
+    int32_t rounds;                      /* claim-resolution rounds on the device (1 on a host-only context) */
+    int32_t round_trips;                 /* blocking device-to-host copies: one flag per round, then the results (0 on a host-only context) */
+    int32_t reserved;
+    double ms_setup;                     /* host clock: checks, allocation, uploads and the grid and point kernels enqueued */
+    double ms_rounds;                    /* host clock over the rounds, each with its flag read (the whole loop on a host-only context) */
+    double ms_total;                     /* host clock over the call */
+} deftri_projection_report;
+
+/* searchWithProjection(currFrame, th, vMapPoints) (Modules/Matching/DescriptorMatching.cc:164-253).  The
+   frame: its feature grid, Tcw (row-major 3x4), kb8, n2 keypoints uv2 [2 * n2], octave2 [n2], desc2 [32 * n2]
+   and slot_point [n2], in and out: -1 a free slot, anything else a slot occupied before the call (-2 by
+   convention), which keeps its value; on return a slot claimed by this call holds the index of its map
+   point.  The n map points: pos [3 * n], normal [3 * n], min_dist / max_dist [n] (the scale-invariance
+   distances), desc [32 * n], as deftri_map_point_descriptors gives them.  Per point: match [n] the slot or -1,
+   status [n], and (each may be NULL) uv [2 * n] the projection, view_cos [n], predicted_octave [n] (-1 where
+   status is 1 or 2), best / second [n] (255 where nothing was compared).  report may be NULL.
+   Status: 0 matched, 1 viewCos < 0.5, 2 outside [min_dist, max_dist], 3 no candidate in the window,
+   4 candidates but no accepted best, 5 undefined in the reference (below): not searched, claims nothing.
+   Restated as it stands, in float, one rounding per operation:
+     - rayWorld = X - Tcw^-1.translation(); viewCos = rayWorld.normalized() . normal (Eigen's normalized()
+       returns the vector itself when its squared norm is not positive); viewCos < 0.5: status 1 (:180);
+     - dist = |rayWorld|; dist < min || dist > max: status 2 (:190);
+     - predictedOctave = (int)ceil(log(max / dist) / log(getScaleFactor(1))), the float overloads of log and
+       ceil, clamped to [0, nScales] (:197-200): the upper end is nScales, not nScales - 1, and at nScales the
+       reference reads vScaleFactor_[nScales], past its end: status 5 (a NaN ratio, which has no int value,
+       too).  A non-finite projection is status 5 as well: posInGrid converts it to int;
+     - uv = project(Tcw X), with no depth test (:203-204); radius = getScaleFactor(predictedOctave) * (viewCos
+       > 0.998 ? 2.5 : 4.0), the comparison and the product in double (:206-210);
+     - candidates = getFeaturesInArea(uv, radius, predictedOctave - 1, predictedOctave + 1) with the rounding
+       and last-half-cell behaviour of deftri_match_for_initialization; none: status 3 (:220), decided
+       before the slots are looked at;
+     - a candidate whose slot is occupied is skipped entirely: neither best nor second (:230-232);
+     - best and second start at 255; accepted iff best <= th && (float)best < float(second) * 0.9 (a tie for
+       best rejects); then slot_point[bestIdx] = i (:246-249), else status 4.
+   uv and view_cos are written for every point, also where the reference never computes them.
+   The skip makes point i depend on the claims of every accepted point before it.  The device resolves
+   that in rounds and equals the sequential loop for every input: claim[j] is the lowest index of a point
+   that claimed keypoint j in the previous round (-1 occupied before the call, INT_MAX free); in a round
+   every point (one wave each) computes its result over the candidates with claim[j] >= its own index;
+   accepted points enter the next round's table by atomicMin; the rounds end when no point's accepted
+   keypoint changed.  After round r points 0 .. r - 1 hold their sequential results and keep them (point k
+   skips j exactly when some claimant below k exists, and the claimants below k are final), so the fixed
+   point is unique, is the loop's result, and is reached in at most n rounds plus the one that sees no
+   change; a round's result does not depend on the order the candidates are visited in (an accepted best
+   is strictly below the second).  More than n + 1 rounds: DEFTRI_E_INTERNAL.  One 4-byte flag is read
+   back per round.  A host-only context runs the reference's loop.  The two context kinds use different
+   libm (atan2f, sinf, cosf, logf), so uv differs by ulps and a decision can differ where an input sits within
+   those ulps of a threshold.
+   DEFTRI_E_ARG with a message: n_scales < 2 (getScaleFactor(1)), an octave of a keypoint outside [0,
+   n_scales), the grid errors of deftri_match_for_initialization, a null required pointer.  n == 0 or
+   n2 == 0 writes nothing beyond the report. */
+int deftri_search_with_projection(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8,
+        int32_t n2, const float *uv2, const int32_t *octave2, const uint8_t *desc2, int32_t *slot_point /* [n2] in/out */,
+        int32_t n, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+        const uint8_t *desc /* n x 32 */, int32_t th,
+        int32_t *match /* [n] */, uint8_t *status /* [n] */,
+        float *uv, float *view_cos, int32_t *predicted_octave, int32_t *best, int32_t *second /* may be NULL */,
+        deftri_projection_report *report /* may be NULL */);
+
+/* guidedMatching(refFrame, currFrame, th, vMatches, windowSizeFactor) (DescriptorMatching.cc:101-162).  The
+   current frame as above, but every slot starts free (clearMapPoints, :102): slot_point [n2] is output
+   only and holds the REFERENCE SLOT whose map point now sits in the slot, or -1.  The reference frame: n1
+   slots with has_point [n1] (0: the slot holds no map point and is passed over, :112), and for the slots
+   that hold one pos [3 * n1] the map point's world position, octave1 [n1] the reference keypoint's octave,
+   desc [32 * n1] the map point's own descriptor.  The points are taken in slot order.  Per slot: matches
+   [n1] the current slot or -1 (-1 for a slot without a map point), status [n1] as above with 6 = no map
+   point in the slot, and (each may be NULL) uv, best, second.  There is no view-cosine, distance or
+   octave-prediction step: the octave is octave1[i], radius = float(15 * windowSizeFactor) *
+   getScaleFactor(octave) — windowSizeFactor is an int, so the product is an integer — and the levels are
+   octave +- 1.  The skip rule, the acceptance, the claim and its resolution on the device are those of
+   deftri_search_with_projection; the kernel is the same.  DEFTRI_E_ARG as there (n_scales < 1 instead of
+   2), and for window_size_factor outside [0, 2^20].  n1 == 0 or n2 == 0 writes nothing beyond the report. */
+int deftri_guided_matching(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8,
+        int32_t n2, const float *uv2, const int32_t *octave2, const uint8_t *desc2, int32_t *slot_point /* [n2] out */,
+        int32_t n1, const uint8_t *has_point, const float *pos, const int32_t *octave1, const uint8_t *desc /* n1 x 32 */,
+        int32_t th, int32_t window_size_factor,
+        int32_t *matches /* [n1] */, uint8_t *status /* [n1] */, float *uv, int32_t *best, int32_t *second /* may be NULL */,
+        deftri_projection_report *report /* may be NULL */);
+
+/* Map::updateOrientationAndDescriptor (Modules/Map/Map.cc:270-321) for n map points: pos [3 * n]; their
+   observations as a CSR, obs_start [n + 1] into obs_kf / obs_slot (keyframe index, keypoint slot).  The
+   reference visits mMapPointObs_[mp], an unordered_map, in libstdc++'s iteration order: this entry takes
+   the observations in the order it is given, and the caller provides that order (deftri_keyframe_order of
+   the keyframe ids in insertion order gives it).  The n_kf keyframes: kf_Tcw [12 * n_kf] row-major 3x4,
+   their slots concatenated, kf_slot_start [n_kf + 1] into kf_desc [32 * slots] and kf_octave [slots];
+   n_scales and scale_factor give vScaleFactor_ as in deftri_feature_grid.  Per point: normal [3 * n],
+   max_dist / min_dist [n], desc [32 * n], ref_obs [n] the ordinal of the chosen observation, status [n].
+   Restated as it stands, in float:
+     - normal = sum over the observations, in order, of (X - Tcw^-1.translation()).normalized(), divided by
+       the count and normalized (:286-293);
+     - all pairwise Hamming distances; per observation the element nth_element puts at nObs / 2: the
+       (nObs / 2)-th smallest counting from 0, the self-distance 0 included (:299-303);
+     - the first observation whose median is strictly below the running best wins; the running best starts
+       at 255.0f, so medians of 255 or 256 leave obsIdx = 0 (:296-307);
+     - dist = |X - centre of the chosen keyframe|; maxDist = dist * getScaleFactor(refOctave), minDist =
+       maxDist / getScaleFactor(nScales - 1) (:311-315);
+     - KEPT QUIRK: refOctave is read from keypoint obsIdx of the chosen keyframe (:312), obsIdx being the
+       observation's ordinal, not its slot.
+   status 0 written; 1 no observation (the reference indexes an empty vector): the point's outputs are
+   not written, ref_obs -1.  An ordinal beyond the chosen keyframe's slots is DEFTRI_E_ARG (the outputs are
+   then undefined), as are an observation that names no keyframe or slot, an octave outside [0, n_scales),
+   n_scales < 1, and a null required pointer.  On the device one wave per map point: the lanes stride over
+   the observation pairs, and the median comes from counting (a 257-bin histogram per observation), not
+   sorting.  desc, ref_obs and status equal a host-only context's; normal and the distances are the same
+   float expressions.  n == 0 writes nothing. */
+int deftri_map_point_descriptors(deftri_ctx *ctx, int32_t n, const float *pos, const int32_t *obs_start,
+        const int32_t *obs_kf, const int32_t *obs_slot,
+        int32_t n_kf, const float *kf_Tcw, const int32_t *kf_slot_start, const uint8_t *kf_desc, const int32_t *kf_octave,
+        int32_t n_scales, float scale_factor,
+        float *normal, float *max_dist, float *min_dist, uint8_t *desc, int32_t *ref_obs, uint8_t *status);
 
 /* ---- from an image to keypoints: FAST::extract (Modules/Features/FAST.cc:81-118, FAST.h:52-97) --- */
 #define DEFTRI_FAST_MAX_LEVELS 16

@@ -18,6 +18,9 @@
 // the poses (:160-163), in every iteration, so its result is one computeScoreAndInliers (:206-223):
 //   k_epipolar_inliers                         one thread per match, the score per workgroup
 //
+// The grid geometry, the acceptance test and the wave's join are in matching_grid.h, shared with
+// projection_matching.hip.
+//
 // Float arithmetic without contraction on both sides; the host loops below are the sequential
 // restatements a host-only context runs and the kernels are tested against.
 #include <hip/hip_runtime.h>
@@ -28,62 +31,14 @@
 #include "dev_arena.h"
 #include "device_math.h"
 #include "matching.h"
+#include "matching_grid.h"
 #include "pose_host.h"
 
 namespace deftri {
 
 namespace dev {
-// Frame::initializeGrid / computeImageBoundaries (Frame.cc:213-227)
-struct GridGeom {
-    int cols, rows;
-    float min_col, min_row, width_inv, height_inv;
-};
 struct Kb8 { float k[8]; };
 struct Mat3 { float m[9]; };
-
-inline GridGeom geometry(const deftri_feature_grid &g) {
-    GridGeom G;
-    G.cols = g.cols; G.rows = g.rows;
-    G.min_col = g.min_col; G.min_row = g.min_row;
-    G.width_inv = (float)g.cols / (float)(g.max_col - g.min_col);
-    G.height_inv = (float)g.rows / (float)(g.max_row - g.min_row);
-    return G;
-}
-
-// Frame::posInGrid (Frame.cc:277-286).  The reference converts the rounded float to int before it
-// tests the range; a value no int holds (or a NaN) is outside the grid here as well.
-__host__ __device__ __forceinline__ bool pos_in_grid(const GridGeom &G, float x, float y, int &col, int &row) {
-    const float fc = roundf((x - G.min_col) * G.width_inv);
-    const float fr = roundf((y - G.min_row) * G.height_inv);
-    const bool ok = fc >= 0.0f && fc < (float)G.cols && fr >= 0.0f && fr < (float)G.rows;
-    col = ok ? (int)fc : 0;
-    row = ok ? (int)fr : 0;
-    return ok;
-}
-
-// the cell range of Frame::getFeaturesInArea (Frame.cc:296-307): each of the four calls falls back when
-// it fails, also when it fails through its other coordinate
-__host__ __device__ __forceinline__ void cell_range(const GridGeom &G, float x, float y, float radius, int &cmin, int &rmin,
-                                                    int &cmax, int &rmax) {
-    int dummy;
-    if (!pos_in_grid(G, x - radius, y, cmin, dummy)) cmin = 0;
-    if (!pos_in_grid(G, x, y - radius, dummy, rmin)) rmin = 0;
-    if (!pos_in_grid(G, x + radius, y, cmax, dummy)) cmax = G.cols - 1;
-    if (!pos_in_grid(G, x, y + radius, dummy, rmax)) rmax = G.rows - 1;
-}
-
-// DescriptorMatching.cc:92, the literal expression
-__host__ __device__ __forceinline__ bool accept_match(int best, int second, int th) {
-    return best <= th && (double)(float)best < (double)(float)second * 0.9;
-}
-
-// Eigen's normalized(): the vector itself when its squared norm is not positive
-__host__ __device__ __forceinline__ V3 eigen_normalized(V3 a) {
-    const float z = dot(a, a);
-    if (!(z > 0.0f)) return a;
-    const float n = sqrtf(z);
-    return v3(a.x / n, a.y / n, a.z / n);
-}
 
 // computeScoreAndInliers (:206-223) for one match: |float(pi/2) - acos(r1_hat . r2.normalized())|
 __host__ __device__ __forceinline__ float epipolar_error(const Kb8 &k1, const Kb8 &k2, const Mat3 &E, float u1, float v1, float u2,
@@ -132,15 +87,6 @@ __global__ void k_grid_fill(int n, const int *__restrict__ cell, int *__restrict
     if (i >= n) return;
     const int id = cell[i];
     if (id >= 0) keys[atomicAdd(&cursor[id], 1)] = i;
-}
-
-// (best, second, index) of two candidate sets joined: the two smallest distances of the union, the
-// lower index among equal bests.  Identity (255, 255, -1).
-__device__ __forceinline__ void join_best(int &b, int &s, int &idx, int b2, int s2, int idx2) {
-    const int lo = min(b, b2), hi = max(b, b2);
-    if (b2 < b || (b2 == b && idx2 >= 0 && (idx < 0 || idx2 < idx))) idx = idx2;
-    s = min(hi, min(s, s2));
-    b = lo;
 }
 
 // One wave per reference keypoint (4 per workgroup).  `radius`: windowSizeFactor * 1 * getScaleFactor(0),
@@ -233,15 +179,6 @@ int hip_fail(std::string &err, const char *what, hipError_t e) {
     return DEFTRI_E_HIP;
 }
 
-// "" for a grid Frame could have built, else what is wrong with it
-std::string grid_error(const deftri_feature_grid &g) {
-    if (g.cols <= 0 || g.rows <= 0) return "FeatureGrid.nGridCols / nGridRows must be positive";
-    if ((int64_t)g.cols * g.rows > ((int64_t)1 << 24)) return "feature grid of more than 2^24 cells";
-    if (!(g.max_col > g.min_col) || !(g.max_row > g.min_row)) return "feature grid bounds: max <= min";
-    if (g.n_scales < 1) return "FeatureExtractor.nScales < 1";
-    return "";
-}
-
 // the reference reads vScaleFactor_[octave] of the keypoint (DescriptorMatching.cc:69)
 bool octaves_ok(const deftri_feature_grid &g, int32_t n, const int32_t *octave, const char *which, std::string &err) {
     for (int32_t i = 0; i < n; i++)
@@ -251,6 +188,17 @@ bool octaves_ok(const deftri_feature_grid &g, int32_t n, const int32_t *octave, 
             return false;
         }
     return true;
+}
+
+}  // namespace
+
+// "" for a grid Frame could have built, else what is wrong with it
+std::string grid_error(const deftri_feature_grid &g) {
+    if (g.cols <= 0 || g.rows <= 0) return "FeatureGrid.nGridCols / nGridRows must be positive";
+    if ((int64_t)g.cols * g.rows > ((int64_t)1 << 24)) return "feature grid of more than 2^24 cells";
+    if (!(g.max_col > g.min_col) || !(g.max_row > g.min_row)) return "feature grid bounds: max <= min";
+    if (g.n_scales < 1) return "FeatureExtractor.nScales < 1";
+    return "";
 }
 
 // getScaleFactor(octave) of Frame's table (Frame.cc:65-70): a running float product
@@ -291,7 +239,6 @@ int hamming(const uint8_t *a, const uint8_t *b) {
     }
     return dist;
 }
-}  // namespace
 
 int feature_grid_cells(int device, hipStream_t st, const deftri_feature_grid &grid, int32_t n, const float *uv,
                        int32_t *cell_start, int32_t *cell_keys, std::string &err) {

@@ -33,6 +33,7 @@
 #include "matching.h"
 #include "metrics.h"
 #include "orb.h"
+#include "projection_matching.h"
 #include "pcg.h"
 #include "pose_host.h"
 #include "spcg.h"
@@ -1506,6 +1507,7 @@ int64_t deftri_sizeof(int32_t which) {
         case 16: return (int64_t)sizeof(deftri_fast_report);
         case 17: return (int64_t)sizeof(deftri_orb_params);
         case 18: return (int64_t)sizeof(deftri_orb_report);
+        case 20: return (int64_t)sizeof(deftri_projection_report);
         default: return -1;
     }
 }
@@ -2095,6 +2097,66 @@ int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *
         return fail(ctx, DEFTRI_E_ARG, "feature_grid_cells: null array or negative n");
     std::string err;
     const int rc = feature_grid_cells(ctx->device, ctx->st, *grid, n, uv, cell_start, cell_keys, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+// ---- guidedMatching, searchWithProjection and Map::updateOrientationAndDescriptor (projection_matching.hip) ----
+int deftri_search_with_projection(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8, int32_t n2,
+                                  const float *uv2, const int32_t *octave2, const uint8_t *desc2, int32_t *slot_point, int32_t n,
+                                  const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+                                  const uint8_t *desc, int32_t th, int32_t *match, uint8_t *status, float *uv, float *view_cos,
+                                  int32_t *predicted_octave, int32_t *best, int32_t *second, deftri_projection_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!grid || !Tcw || !kb8 || n < 0 || n2 < 0 || (n2 > 0 && (!uv2 || !octave2 || !desc2 || !slot_point)) ||
+        (n > 0 && (!pos || !normal || !min_dist || !max_dist || !desc || !match || !status)))
+        return fail(ctx, DEFTRI_E_ARG, "search_with_projection: null array or negative size");
+    ProjectionMatchArgs a{};
+    a.guided = false; a.grid = grid; a.Tcw = Tcw; a.kb8 = kb8;
+    a.n2 = n2; a.uv2 = uv2; a.octave2 = octave2; a.desc2 = desc2; a.slot_point = slot_point;
+    a.n = n; a.pos = pos; a.desc = desc; a.th = th; a.normal = normal; a.min_dist = min_dist; a.max_dist = max_dist;
+    a.match = match; a.status = status; a.uv = uv; a.view_cos = view_cos; a.predicted_octave = predicted_octave;
+    a.best = best; a.second = second; a.report = report;
+    std::string err;
+    const int rc = projection_match(ctx->device, ctx->st, a, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_guided_matching(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8, int32_t n2,
+                           const float *uv2, const int32_t *octave2, const uint8_t *desc2, int32_t *slot_point, int32_t n1,
+                           const uint8_t *has_point, const float *pos, const int32_t *octave1, const uint8_t *desc, int32_t th,
+                           int32_t window_size_factor, int32_t *matches, uint8_t *status, float *uv, int32_t *best, int32_t *second,
+                           deftri_projection_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!grid || !Tcw || !kb8 || n1 < 0 || n2 < 0 || (n2 > 0 && (!uv2 || !octave2 || !desc2 || !slot_point)) ||
+        (n1 > 0 && (!has_point || !pos || !octave1 || !desc || !matches || !status)))
+        return fail(ctx, DEFTRI_E_ARG, "guided_matching: null array or negative size");
+    ProjectionMatchArgs a{};
+    a.guided = true; a.grid = grid; a.Tcw = Tcw; a.kb8 = kb8;
+    a.n2 = n2; a.uv2 = uv2; a.octave2 = octave2; a.desc2 = desc2; a.slot_point = slot_point;
+    a.n = n1; a.pos = pos; a.desc = desc; a.th = th; a.has_point = has_point; a.octave1 = octave1;
+    a.window_size_factor = window_size_factor;
+    a.match = matches; a.status = status; a.uv = uv; a.best = best; a.second = second; a.report = report;
+    std::string err;
+    const int rc = projection_match(ctx->device, ctx->st, a, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_map_point_descriptors(deftri_ctx *ctx, int32_t n, const float *pos, const int32_t *obs_start, const int32_t *obs_kf,
+                                 const int32_t *obs_slot, int32_t n_kf, const float *kf_Tcw, const int32_t *kf_slot_start,
+                                 const uint8_t *kf_desc, const int32_t *kf_octave, int32_t n_scales, float scale_factor,
+                                 float *normal, float *max_dist, float *min_dist, uint8_t *desc, int32_t *ref_obs, uint8_t *status) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || n_kf < 0 || !kf_slot_start || (n_kf > 0 && !kf_Tcw) ||
+        (n > 0 && (!pos || !obs_start || !normal || !max_dist || !min_dist || !desc || !ref_obs || !status)))
+        return fail(ctx, DEFTRI_E_ARG, "map_point_descriptors: null array or negative size");
+    if (n > 0 && obs_start[n] > 0 && (!obs_kf || !obs_slot))
+        return fail(ctx, DEFTRI_E_ARG, "map_point_descriptors: null array or negative size");
+    if (kf_slot_start[n_kf] > 0 && (!kf_desc || !kf_octave))
+        return fail(ctx, DEFTRI_E_ARG, "map_point_descriptors: null array or negative size");
+    std::string err;
+    const int rc = map_point_descriptors(ctx->device, ctx->st, n, pos, obs_start, obs_kf, obs_slot, n_kf, kf_Tcw, kf_slot_start,
+                                         kf_desc, kf_octave, n_scales, scale_factor, normal, max_dist, min_dist, desc, ref_obs, status,
+                                         err);
     return rc ? fail(ctx, rc, err) : 0;
 }
 

@@ -207,6 +207,16 @@ class OrbReport(C.Structure):
         return d
 
 
+class ProjectionReport(C.Structure):
+    _fields_ = [("n_points", i32), ("n_matches", i32), ("n_view_cos", i32), ("n_inv_dist", i32), ("n_no_candidates", i32),
+                ("n_rejected", i32), ("n_undefined", i32), ("rounds", i32), ("round_trips", i32), ("reserved", i32),
+                ("ms_setup", f64), ("ms_rounds", f64), ("ms_total", f64)]
+
+    def as_dict(self):
+        """The counters; the times (ms_*) are measurements, not results."""
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

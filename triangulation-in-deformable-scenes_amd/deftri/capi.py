@@ -80,6 +80,19 @@ def load():
                                               P(C.c_int32)]),
         "deftri_debug_feature_grid_cells": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
                                                       P(C.c_int32)]),
+        "deftri_search_with_projection": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
+                                                    P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32,
+                                                    P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint8),
+                                                    C.c_int32, P(C.c_int32), P(C.c_uint8), P(C.c_float), P(C.c_float),
+                                                    P(C.c_int32), P(C.c_int32), P(C.c_int32), P(_abi.ProjectionReport)]),
+        "deftri_guided_matching": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
+                                             P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32, P(C.c_uint8),
+                                             P(C.c_float), P(C.c_int32), P(C.c_uint8), C.c_int32, C.c_int32, P(C.c_int32),
+                                             P(C.c_uint8), P(C.c_float), P(C.c_int32), P(C.c_int32), P(_abi.ProjectionReport)]),
+        "deftri_map_point_descriptors": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_int32), P(C.c_int32),
+                                                   C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32,
+                                                   C.c_float, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint8),
+                                                   P(C.c_int32), P(C.c_uint8)]),
         "deftri_fast_extract": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(C.c_uint8), C.c_int32,
                                           C.c_int32, C.c_int32, P(_abi.FastParams), P(C.c_float), P(C.c_int32), P(C.c_float),
                                           P(C.c_float), P(C.c_float), P(C.c_int32), P(_abi.FastReport)]),
@@ -193,6 +206,7 @@ EXPORTED = [
     "deftri_measure_real_absolute_map_errors", "deftri_measure_relative_map_errors_images",
     "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
     "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
+    "deftri_search_with_projection", "deftri_guided_matching", "deftri_map_point_descriptors",
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
 ]
@@ -264,6 +278,35 @@ class OrbResult:
 
     def __len__(self):
         return len(self.status)
+
+
+class ProjectionMatchResult:
+    """The result of Context.search_with_projection / .guided_matching: match int32 [n] (the frame's slot or -1),
+    status uint8 [n] (0 matched, 1 view cosine, 2 distance, 3 no candidates, 4 rejected, 5 undefined in the
+    reference, 6 reference slot without a map point), uv float32 [n, 2] the projections, best / second int32 [n],
+    slot_point int32 [n2] the frame's slots after the call, report (deftri_projection_report as a dict), and for
+    search_with_projection view_cos float32 [n] and predicted_octave int32 [n]."""
+
+    def __init__(self, match, status, uv, best, second, slot_point, report, view_cos=None, predicted_octave=None):
+        self.match, self.status, self.uv, self.best, self.second = match, status, uv, best, second
+        self.slot_point, self.report, self.view_cos, self.predicted_octave = slot_point, report, view_cos, predicted_octave
+
+
+class MapPointDescriptors:
+    """The result of Context.map_point_descriptors: normal float32 [n, 3], max_dist / min_dist float32 [n], desc
+    uint8 [n, 32], ref_obs int32 [n] (the chosen observation's ordinal), status uint8 [n] (1: no observation,
+    nothing written for the point)."""
+
+    def __init__(self, normal, max_dist, min_dist, desc, ref_obs, status):
+        self.normal, self.max_dist, self.min_dist, self.desc, self.ref_obs, self.status = normal, max_dist, min_dist, desc, ref_obs, status
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def _pixel_pairs(uv1, uv2):
@@ -681,6 +724,84 @@ class Context:
         self._check(self.lib.deftri_epipolar_inliers(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2), _fp(Ta), _fp(Tb),
                                                      float(epipolar_th), _u8p(inl), _fp(err), C.byref(score)))
         return inl.astype(bool), err, int(score.value)
+
+    def _frame_arrays(self, Tcw, kb8, uv2, octave2, desc2):
+        """The current frame's arguments of the projection matchers."""
+        T = _pose34(Tcw) if hasattr(Tcw, "R") else _f32(Tcw).reshape(3, 4)
+        uv2 = _f32(uv2).reshape(-1, 2); o2 = _i32(octave2)
+        d2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        if not (len(uv2) == len(o2) == len(d2)):
+            raise ValueError(f"{len(uv2)} keypoints, {len(o2)} octaves and {len(d2)} descriptors")
+        return T, _f32(kb8).reshape(8), uv2, o2, d2
+
+    def search_with_projection(self, grid, Tcw, kb8, uv2, octave2, desc2, slot_point, pos, normal, min_dist, max_dist, desc, th):
+        """searchWithProjection (DescriptorMatching.cc:164-253) on this context: the device, or the sequential
+        host loop on a host-only one (deftri_search_with_projection).  Tcw: an SE3f or float [3, 4]; slot_point
+        int [n2]: -1 free, -2 occupied (not modified; the result carries the slots after the call).  Returns a
+        ProjectionMatchResult."""
+        T, k, uv2, o2, d2 = self._frame_arrays(Tcw, kb8, uv2, octave2, desc2)
+        slot = _i32(slot_point).copy()
+        pos = _f32(pos).reshape(-1, 3); nrm = _f32(normal).reshape(-1, 3)
+        mn, mx = _f32(min_dist).reshape(-1), _f32(max_dist).reshape(-1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, n2 = len(pos), len(uv2)
+        if not (len(nrm) == len(mn) == len(mx) == len(d) == n) or len(slot) != n2:
+            raise ValueError("search_with_projection: array lengths differ")
+        g = self._feature_grid(grid)
+        match = np.full(n, -1, np.int32); status = np.zeros(n, np.uint8); uv = np.zeros((n, 2), np.float32)
+        vc = np.zeros(n, np.float32); po = np.full(n, -1, np.int32)
+        best = np.full(n, 255, np.int32); second = np.full(n, 255, np.int32)
+        rep = _abi.ProjectionReport()
+        self._check(self.lib.deftri_search_with_projection(self.h, C.byref(g), _fp(T), _fp(k), n2, _fp(uv2), _ip(o2), _u8p(d2),
+                                                           _ip(slot), n, _fp(pos), _fp(nrm), _fp(mn), _fp(mx), _u8p(d), int(th),
+                                                           _ip(match), _u8p(status), _fp(uv), _fp(vc), _ip(po), _ip(best),
+                                                           _ip(second), C.byref(rep)))
+        return ProjectionMatchResult(match, status, uv, best, second, slot, rep.as_dict(), vc, po)
+
+    def guided_matching(self, grid, Tcw, kb8, uv2, octave2, desc2, has_point, pos, octave1, desc, th, window_size_factor):
+        """guidedMatching (DescriptorMatching.cc:101-162) on this context (deftri_guided_matching).  Per reference
+        slot: has_point bool [n1], and where it is set pos [n1, 3], octave1 [n1], desc uint8 [n1, 32] of the slot's
+        map point.  Returns a ProjectionMatchResult whose slot_point holds reference slots."""
+        T, k, uv2, o2, d2 = self._frame_arrays(Tcw, kb8, uv2, octave2, desc2)
+        has = np.ascontiguousarray(has_point, np.uint8).reshape(-1)
+        pos = _f32(pos).reshape(-1, 3); o1 = _i32(octave1)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n1, n2 = len(has), len(uv2)
+        if not (len(pos) == len(o1) == len(d) == n1):
+            raise ValueError("guided_matching: array lengths differ")
+        if int(window_size_factor) != window_size_factor:
+            raise ValueError("guided_matching: windowSizeFactor is an int in the reference")
+        g = self._feature_grid(grid)
+        slot = np.full(n2, -1, np.int32)
+        match = np.full(n1, -1, np.int32); status = np.where(has != 0, 0, 6).astype(np.uint8); uv = np.zeros((n1, 2), np.float32)
+        best = np.full(n1, 255, np.int32); second = np.full(n1, 255, np.int32)
+        rep = _abi.ProjectionReport()
+        self._check(self.lib.deftri_guided_matching(self.h, C.byref(g), _fp(T), _fp(k), n2, _fp(uv2), _ip(o2), _u8p(d2), _ip(slot),
+                                                    n1, _u8p(has), _fp(pos), _ip(o1), _u8p(d), int(th), int(window_size_factor),
+                                                    _ip(match), _u8p(status), _fp(uv), _ip(best), _ip(second), C.byref(rep)))
+        return ProjectionMatchResult(match, status, uv, best, second, slot, rep.as_dict())
+
+    def map_point_descriptors(self, pos, obs_start, obs_kf, obs_slot, kf_Tcw, kf_slot_start, kf_desc, kf_octave, n_scales,
+                              scale_factor):
+        """Map::updateOrientationAndDescriptor (Map.cc:270-321) for a batch of map points on this context
+        (deftri_map_point_descriptors).  Observations as a CSR (obs_start [n + 1] into obs_kf / obs_slot), in the
+        order given; keyframes as kf_Tcw float [n_kf, 3, 4] and their slots concatenated (kf_slot_start [n_kf + 1]
+        into kf_desc uint8 [slots, 32] and kf_octave [slots]).  Returns a MapPointDescriptors."""
+        pos = _f32(pos).reshape(-1, 3)
+        os_, ok, osl = _i32(obs_start), _i32(obs_kf), _i32(obs_slot)
+        T = _f32(kf_Tcw).reshape(-1, 3, 4); ks = _i32(kf_slot_start)
+        kd = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32); ko = _i32(kf_octave)
+        n, n_kf = len(pos), len(T)
+        if len(os_) != n + 1 or len(ks) != n_kf + 1 or len(ok) != len(osl) or len(kd) != len(ko):
+            raise ValueError("map_point_descriptors: array lengths differ")
+        if len(ok) != os_[-1] or len(kd) != ks[-1]:
+            raise ValueError("map_point_descriptors: the CSR ends do not match the array lengths")
+        normal = np.zeros((n, 3), np.float32); mx = np.zeros(n, np.float32); mn = np.zeros(n, np.float32)
+        desc = np.zeros((n, 32), np.uint8); ref = np.full(n, -1, np.int32); status = np.zeros(n, np.uint8)
+        self._check(self.lib.deftri_map_point_descriptors(self.h, n, _fp(pos), _ip(os_), _ip(ok), _ip(osl), n_kf, _fp(T), _ip(ks),
+                                                          _u8p(kd), _ip(ko), int(n_scales), float(scale_factor), _fp(normal),
+                                                          _fp(mx), _fp(mn), _u8p(desc), _ip(ref), _u8p(status)))
+        return MapPointDescriptors(normal, mx, mn, desc, ref, status)
 
     def debug_feature_grid_cells(self, grid, uv):
         """TEST ONLY: the cell lists of keypoints `uv` as the match builds them (deftri_debug_feature_grid_cells).

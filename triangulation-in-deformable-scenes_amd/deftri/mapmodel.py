@@ -103,6 +103,13 @@ class SE3f:
 
 class MapPoint:
     _next_id = 0
+    # what Map::updateOrientationAndDescriptor gives a map point (MapPoint.h: mDescriptor_, normalOrientation_,
+    # fMinDistance_, fMaxDistance_); None until Map.update_orientation_and_descriptor has run.  Class defaults,
+    # so a map point that never got them carries nothing more than its position and id
+    descriptor = None           # uint8 [32]
+    normal = None               # float32 [3]
+    min_distance = None
+    max_distance = None
 
     def __init__(self, position, pid=None):
         self.position = np.asarray(position, dtype=np.float32).copy()
@@ -207,6 +214,52 @@ class Map:
         """libstdc++ unordered_map<ID,KF> iteration order of this map's insertion sequence."""
         from .capi import keyframe_order
         return keyframe_order(list(self.keyframes.keys()))
+
+    def update_orientation_and_descriptor(self, ctx, mp_ids=None, grid=None):
+        """Map::updateOrientationAndDescriptor (Map.cc:270-321) for the map points `mp_ids` (default: all) on `ctx`
+        (Context.map_point_descriptors): sets descriptor, normal, min_distance and max_distance.  The observations
+        of a map point are taken in the iteration order of the reference's unordered_map (deftri_keyframe_order
+        of the keyframe ids in the order the observations were added).  grid: matching.feature_grid(settings),
+        for nScales and fScaleFactor; without it the map's own `scale_factor` attribute and the keyframes'
+        inv_sigma2 table length are used.  A map point without observations is left as it is.  Returns the
+        per-point status (uint8, 1: no observation)."""
+        from .capi import _pose34, keyframe_order
+        ids = list(self.map_points.keys()) if mp_ids is None else [int(i) for i in mp_ids]
+        kf_ids = list(self.keyframes.keys())
+        if grid is not None:
+            n_scales, factor = int(grid["n_scales"]), float(grid["scale_factor"])
+        elif getattr(self, "scale_factor", None) is not None and kf_ids:
+            n_scales, factor = len(self.keyframes[kf_ids[0]].inv_sigma2), float(self.scale_factor)
+        else:
+            raise ValueError("update_orientation_and_descriptor: pass grid=matching.feature_grid(settings) or set Map.scale_factor")
+        kf_index = {kid: n for n, kid in enumerate(kf_ids)}
+        for kid in kf_ids:
+            if self.keyframes[kid].descriptors is None:
+                raise ValueError(f"update_orientation_and_descriptor: keyframe {kid} has no descriptors")
+        kfs = [self.keyframes[kid] for kid in kf_ids]
+        slot_start = np.concatenate([[0], np.cumsum([kf.n_slots for kf in kfs])]).astype(np.int32)
+        kf_desc = np.concatenate([kf.descriptors for kf in kfs]) if kfs else np.zeros((0, 32), np.uint8)
+        kf_oct = np.concatenate([kf.octaves for kf in kfs]) if kfs else np.zeros(0, np.int32)
+        kf_T = np.array([_pose34(kf.pose) for kf in kfs], np.float32).reshape(-1, 3, 4)
+        orders = {}
+        obs_start, obs_kf, obs_slot = [0], [], []
+        for pid in ids:
+            obs = self.mp_obs.get(pid, {})
+            key = tuple(obs.keys())
+            if key not in orders:
+                orders[key] = keyframe_order(list(key)) if key else []
+            for kid in orders[key]:
+                obs_kf.append(kf_index[int(kid)])
+                obs_slot.append(obs[int(kid)])
+            obs_start.append(len(obs_kf))
+        pos = np.array([self.map_points[pid].position for pid in ids], np.float32).reshape(-1, 3)
+        r = ctx.map_point_descriptors(pos, obs_start, obs_kf, obs_slot, kf_T, slot_start, kf_desc, kf_oct, n_scales, factor)
+        for n, pid in enumerate(ids):
+            if r.status[n] == 0:
+                mp = self.map_points[pid]
+                mp.descriptor, mp.normal = r.desc[n].copy(), r.normal[n].copy()
+                mp.min_distance, mp.max_distance = float(r.min_dist[n]), float(r.max_dist[n])
+        return r.status
 
     def clone(self):
         """Map::clone (Map.cc:30-58): an independent copy whose keyframes were inserted in this map's

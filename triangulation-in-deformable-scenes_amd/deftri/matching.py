@@ -11,7 +11,14 @@ for the library's entries; written from the reference, not from the library's ho
   epipolar_inliers(..., dtype=)   the mask of MonocularMapInitializer::initialize with Triangulation.checks
                                   (MonocularMapInitializer.cc:93-104, :119-178, :206-223), fp32 or fp64
 
-The device versions are capi.Context.match_for_initialization and .epipolar_inliers.  Quirks kept as they
+  search_with_projection_ref / guided_matching_ref / map_point_descriptors_ref
+                                  searchWithProjection (DescriptorMatching.cc:164-253), guidedMatching (:101-162) and
+                                  Map::updateOrientationAndDescriptor (Map.cc:270-321), fp32 or fp64
+  guided_matching(ctx, ...) / search_with_projection(ctx, ...)
+                                  the two matchers on a context, setting the frame's map point slots
+
+The device versions are capi.Context.match_for_initialization, .epipolar_inliers, .search_with_projection,
+.guided_matching and .map_point_descriptors.  Quirks kept as they
 stand: posInGrid rounds half away from zero to a cell index, so a keypoint in the last half cell on the right
 or at the bottom is in no cell and never a candidate; only reference keypoints of octave <= 0 are searched;
 best and second start at 255; a tie for best rejects; the matches are not one-to-one; the RANSAC scores the
@@ -195,3 +202,262 @@ def epipolar_inliers(uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th, dtype=np.flo
         err = np.abs(half_pi - np.arccos(d)).astype(dt)
         inl = err < dt.type(F(epipolar_th))
     return inl, err, int(inl.sum())
+
+
+# ---- map points into a frame by projection: guidedMatching, searchWithProjection and what they read ------------
+# status of a point (deftri.h): 0 matched, 1 viewCos < 0.5, 2 outside the invariance distances, 3 no candidate,
+# 4 candidates but no accepted best, 5 undefined in the reference, 6 a reference slot without a map point
+MATCHED, VIEW_COS, INV_DIST, NO_CANDIDATES, REJECTED, UNDEFINED, EMPTY_SLOT = range(7)
+
+
+def _pose_arrays(Tcw, dt):
+    """(R [3, 3], t [3]) in dt of an SE3f or a [3, 4] matrix."""
+    if hasattr(Tcw, "R"):
+        return np.asarray(Tcw.R, F).astype(dt), np.asarray(Tcw.t, F).astype(dt)
+    T = np.asarray(Tcw, F).reshape(3, 4).astype(dt)
+    return T[:, :3].copy(), T[:, 3].copy()
+
+
+def _camera_centre(R, t):
+    """Tcw.inverse().translation() = -(R^T t), the sum in the order written."""
+    return np.array([-((R[0, i] * t[0] + R[1, i] * t[1]) + R[2, i] * t[2]) for i in range(3)], R.dtype)
+
+
+def _to_camera(R, t, X):
+    """Tcw * X = R X + t for rows of X, the sums in the order written."""
+    return np.stack([((R[i, 0] * X[:, 0] + R[i, 1] * X[:, 1]) + R[i, 2] * X[:, 2]) + t[i] for i in range(3)], 1)
+
+
+def _project_points(Tcw, kb8, X, dt):
+    from .mapping import _kb8_project
+    R, t = _pose_arrays(Tcw, dt)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        return _kb8_project(kb8, _to_camera(R, t, X.astype(dt)), dt).astype(dt)
+
+
+def _window_search(grid, cells, uv2, octave2, desc2, slot, i, x, y, radius, octave, desc_i, th):
+    """The part guidedMatching (:129-158) and searchWithProjection (:216-249) share for point i: the window,
+    the skip of occupied slots, best and second, the acceptance and the claim.  Returns (match, status, best,
+    second)."""
+    cand = features_in_area(grid, cells, uv2, octave2, x, y, radius, octave - 1, octave + 1)
+    if not cand:
+        return -1, NO_CANDIDATES, 255, 255
+    best, second, best_idx = 255, 255, -1
+    dist = hamming(np.repeat(desc_i[None], len(cand), 0), desc2[cand])
+    for j, d in zip(cand, dist):
+        if slot[j] != -1:                                    # getMapPoint(j): skipped entirely
+            continue
+        d = int(d)
+        if d < best:
+            second, best, best_idx = best, d, j
+        elif d < second:
+            second = d
+    if accept(best, second, th):
+        slot[best_idx] = i
+        return best_idx, MATCHED, best, second
+    return -1, REJECTED, best, second
+
+
+def _frame(uv2, octave2, desc2):
+    return (np.asarray(uv2, F).reshape(-1, 2), np.asarray(octave2, np.int64).reshape(-1),
+            np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32))
+
+
+def _report(status):
+    return {"n_points": len(status), "n_matches": int((status == MATCHED).sum()), "n_view_cos": int((status == VIEW_COS).sum()),
+            "n_inv_dist": int((status == INV_DIST).sum()), "n_no_candidates": int((status == NO_CANDIDATES).sum()),
+            "n_rejected": int((status == REJECTED).sum()), "n_undefined": int((status == UNDEFINED).sum())}
+
+
+def search_with_projection_ref(grid, Tcw, kb8, uv2, octave2, desc2, slot_point, pos, normal, min_dist, max_dist, desc, th,
+                               dtype=np.float32):
+    """searchWithProjection(currFrame, th, vMapPoints) (DescriptorMatching.cc:164-253), the sequential loop, with
+    the float arithmetic in `dtype` (float32 as the reference, or float64).  slot_point [n2]: -1 free, anything
+    else occupied.  Returns a dict: match, status, uv, view_cos, predicted_octave, best, second, slot_point,
+    report, and the values the decisions were taken on: dist, ratio (log(max / dist) / log(getScaleFactor(1))
+    before ceil) and radius."""
+    dt = np.dtype(dtype).type
+    uv2, octave2, desc2 = _frame(uv2, octave2, desc2)
+    X = np.asarray(pos, F).reshape(-1, 3).astype(dt)
+    nrm = np.asarray(normal, F).reshape(-1, 3).astype(dt)
+    mn, mx = np.asarray(min_dist, F).reshape(-1).astype(dt), np.asarray(max_dist, F).reshape(-1).astype(dt)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    n, n_scales = len(X), grid["n_scales"]
+    scale = scale_factors(grid)
+    slot = np.asarray(slot_point, np.int32).copy()
+    cells = build_grid(grid, uv2)
+    R, t = _pose_arrays(Tcw, dt)
+    centre = _camera_centre(R, t)
+    uv = _project_points(Tcw, kb8, X, dt)
+    out = {"match": np.full(n, -1, np.int32), "status": np.zeros(n, np.uint8), "uv": uv, "view_cos": np.zeros(n, dt),
+           "predicted_octave": np.full(n, -1, np.int32), "best": np.full(n, 255, np.int32), "second": np.full(n, 255, np.int32),
+           "dist": np.zeros(n, dt), "ratio": np.full(n, np.nan, dt), "radius": np.zeros(n, dt)}
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        log_scale1 = np.log(dt(scale[1]))
+        for i in range(n):
+            ray = X[i] - centre                                                     # :177
+            z = (ray[0] * ray[0] + ray[1] * ray[1]) + ray[2] * ray[2]
+            rn = ray / np.sqrt(z) if z > 0 else ray
+            vc = dt((rn[0] * nrm[i, 0] + rn[1] * nrm[i, 1]) + rn[2] * nrm[i, 2])   # :178
+            out["view_cos"][i] = vc
+            dist = np.sqrt(z)
+            out["dist"][i] = dist
+            if vc < 0.5:                                                            # :180
+                out["status"][i] = VIEW_COS
+                continue
+            if dist < mn[i] or dist > mx[i]:                                        # :190
+                out["status"][i] = INV_DIST
+                continue
+            ratio = dt(np.log(dt(mx[i] / dist)) / log_scale1)                       # :196
+            out["ratio"][i] = ratio
+            c = np.ceil(ratio)
+            octave = n_scales if (np.isnan(c) or c > n_scales) else 0 if c < 0 else int(c)   # :197-200
+            out["predicted_octave"][i] = octave
+            if octave >= n_scales or not np.all(np.isfinite(uv[i])):                # vScaleFactor_[nScales]; posInGrid's int
+                out["status"][i] = UNDEFINED
+                continue
+            radius = dt(float(scale[octave]) * (2.5 if float(vc) > 0.998 else 4.0))   # :206-210, in double
+            out["radius"][i] = radius
+            out["match"][i], out["status"][i], out["best"][i], out["second"][i] = _window_search(
+                grid, cells, uv2, octave2, desc2, slot, i, uv[i, 0], uv[i, 1], radius, octave, desc[i], th)
+    out["slot_point"] = slot
+    out["report"] = _report(out["status"])
+    return out
+
+
+def guided_matching_ref(grid, Tcw, kb8, uv2, octave2, desc2, has_point, pos, octave1, desc, th, window_size_factor,
+                        dtype=np.float32):
+    """guidedMatching(refFrame, currFrame, th, vMatches, windowSizeFactor) (DescriptorMatching.cc:101-162), the
+    sequential loop over the reference frame's slots, the projection in `dtype`.  Returns a dict: match, status, uv,
+    best, second, slot_point (the reference slot in each of the current frame's slots, or -1), report, radius."""
+    dt = np.dtype(dtype).type
+    uv2, octave2, desc2 = _frame(uv2, octave2, desc2)
+    has = np.asarray(has_point).reshape(-1).astype(bool)
+    X = np.asarray(pos, F).reshape(-1, 3).astype(dt)
+    octave1 = np.asarray(octave1, np.int64).reshape(-1)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    n1 = len(has)
+    scale = scale_factors(grid)
+    slot = np.full(len(uv2), -1, np.int32)                                          # clearMapPoints (:102)
+    cells = build_grid(grid, uv2)
+    uv = _project_points(Tcw, kb8, X, dt)
+    uv[~has] = 0
+    out = {"match": np.full(n1, -1, np.int32), "status": np.where(has, 0, EMPTY_SLOT).astype(np.uint8), "uv": uv,
+           "best": np.full(n1, 255, np.int32), "second": np.full(n1, 255, np.int32), "radius": np.zeros(n1, dt)}
+    window15 = 15 * int(window_size_factor)                                         # an int product (:127)
+    for i in np.nonzero(has)[0]:
+        if not np.all(np.isfinite(uv[i])):
+            out["status"][i] = UNDEFINED
+            continue
+        octave = int(octave1[i])
+        radius = F(F(window15) * scale[octave])
+        out["radius"][i] = radius
+        out["match"][i], out["status"][i], out["best"][i], out["second"][i] = _window_search(
+            grid, cells, uv2, octave2, desc2, slot, int(i), uv[i, 0], uv[i, 1], radius, octave, desc[i], th)
+    out["slot_point"] = slot
+    out["report"] = _report(out["status"])
+    return out
+
+
+def map_point_descriptors_ref(pos, obs_start, obs_kf, obs_slot, kf_Tcw, kf_slot_start, kf_desc, kf_octave, n_scales,
+                              scale_factor, dtype=np.float32):
+    """Map::updateOrientationAndDescriptor (Map.cc:270-321) for a batch of map points, the observations in the
+    order given, the float arithmetic in `dtype`.  Returns a dict: normal, max_dist, min_dist, desc, ref_obs,
+    status (1: no observation, nothing written) and medians (per point the list of its observations' medians).
+    An ordinal beyond the chosen keyframe's slots raises ValueError."""
+    dt = np.dtype(dtype).type
+    X = np.asarray(pos, F).reshape(-1, 3).astype(dt)
+    T = np.asarray(kf_Tcw, F).reshape(-1, 3, 4).astype(dt)
+    kf_desc = np.ascontiguousarray(kf_desc, np.uint8).reshape(-1, 32)
+    scale = scale_factors({"n_scales": n_scales, "scale_factor": scale_factor})
+    centres = [_camera_centre(Tk[:, :3], Tk[:, 3]) for Tk in T]
+    n = len(X)
+    out = {"normal": np.zeros((n, 3), dt), "max_dist": np.zeros(n, dt), "min_dist": np.zeros(n, dt),
+           "desc": np.zeros((n, 32), np.uint8), "ref_obs": np.full(n, -1, np.int32), "status": np.zeros(n, np.uint8),
+           "medians": [[] for _ in range(n)]}
+
+    def normalized(v):
+        z = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+        return v / np.sqrt(z) if z > 0 else v
+
+    for p in range(n):
+        o0, o1 = int(obs_start[p]), int(obs_start[p + 1])
+        n_obs = o1 - o0
+        if n_obs == 0:
+            out["status"][p] = 1
+            continue
+        kfs = [int(k) for k in obs_kf[o0:o1]]
+        rows = [int(kf_slot_start[k]) + int(s) for k, s in zip(kfs, obs_slot[o0:o1])]
+        normal = np.zeros(3, dt)
+        for k in kfs:                                                               # :286-287
+            normal = normal + normalized(X[p] - centres[k])
+        normal = normalized(normal / dt(n_obs))                                     # :293
+        best_median, obs_idx = F(255.0), 0                                          # :296
+        for i in range(n_obs):
+            d = np.sort(hamming(np.repeat(kf_desc[rows[i]][None], n_obs, 0), kf_desc[rows]))
+            med = int(d[n_obs // 2])                                                # nth_element's element
+            out["medians"][p].append(med)
+            if med < best_median:
+                best_median, obs_idx = F(med), i
+        k = kfs[obs_idx]
+        if obs_idx >= int(kf_slot_start[k + 1]) - int(kf_slot_start[k]):
+            raise ValueError(f"map point {p}: keypoint {obs_idx} (the chosen observation's ordinal, Map.cc:312) is no slot of "
+                             f"keyframe {k}")
+        ray = X[p] - centres[k]
+        dist = np.sqrt((ray[0] * ray[0] + ray[1] * ray[1]) + ray[2] * ray[2])       # :311
+        ref_octave = int(kf_octave[int(kf_slot_start[k]) + obs_idx])                # :312, the ordinal as a slot
+        mx = dt(dist * dt(scale[ref_octave]))
+        out["normal"][p], out["max_dist"][p], out["min_dist"][p] = normal, mx, dt(mx / dt(scale[n_scales - 1]))
+        out["desc"][p] = kf_desc[rows[obs_idx]]
+        out["ref_obs"][p] = obs_idx
+    return out
+
+
+def _frame_of(cur_frame, what):
+    if getattr(cur_frame, "descriptors", None) is None:
+        raise ValueError(f"{what}: the frame has no descriptors")
+    return cur_frame.pose, cur_frame.kb8, cur_frame.keypoints, cur_frame.octaves, cur_frame.descriptors
+
+
+def guided_matching(ctx, ref_frame, cur_frame, grid, th, window_size_factor):
+    """guidedMatching(refFrame, currFrame, th, vMatches, windowSizeFactor) on `ctx` (Context.guided_matching): clears
+    cur_frame.map_points and sets the matched slots to the reference frame's map points, as the reference sets
+    vMapPoints_.  A KeyFrame serves as either frame.  Returns (matches int32 [reference slots], report); a map point
+    without a descriptor raises ValueError."""
+    frame = _frame_of(cur_frame, "guided_matching")
+    n1 = ref_frame.n_slots
+    has = np.array([mp is not None for mp in ref_frame.map_points], bool)
+    pos = np.zeros((n1, 3), F); desc = np.zeros((n1, 32), np.uint8)
+    for i, mp in enumerate(ref_frame.map_points):
+        if mp is None:
+            continue
+        if getattr(mp, "descriptor", None) is None:
+            raise ValueError(f"guided_matching: map point {mp.id} has no descriptor (Map.update_orientation_and_descriptor)")
+        pos[i], desc[i] = mp.position, mp.descriptor
+    res = ctx.guided_matching(grid, *frame, has, pos, ref_frame.octaves, desc, th, window_size_factor)
+    cur_frame.map_points = [None if i < 0 else ref_frame.map_points[i] for i in res.slot_point]
+    return res.match, res.report
+
+
+def search_with_projection(ctx, cur_frame, grid, th, map_points):
+    """searchWithProjection(currFrame, th, vMapPoints) on `ctx` (Context.search_with_projection): the slots of
+    cur_frame.map_points that hold a map point stay as they are, the matched free ones are set.  Returns (matches
+    int32 [map points]: the slot or -1, report); a map point without descriptor, normal or invariance distances
+    raises ValueError."""
+    frame = _frame_of(cur_frame, "search_with_projection")
+    map_points = list(map_points)
+    for mp in map_points:
+        if any(getattr(mp, k, None) is None for k in ("descriptor", "normal", "min_distance", "max_distance")):
+            raise ValueError(f"search_with_projection: map point {mp.id} lacks its descriptor, normal or invariance distances "
+                             "(Map.update_orientation_and_descriptor)")
+    n = len(map_points)
+    pos = np.array([mp.position for mp in map_points], F).reshape(n, 3)
+    nrm = np.array([mp.normal for mp in map_points], F).reshape(n, 3)
+    mn = np.array([mp.min_distance for mp in map_points], F); mx = np.array([mp.max_distance for mp in map_points], F)
+    desc = np.array([mp.descriptor for mp in map_points], np.uint8).reshape(n, 32)
+    slot = np.array([-1 if mp is None else -2 for mp in cur_frame.map_points], np.int32)
+    res = ctx.search_with_projection(grid, *frame, slot, pos, nrm, mn, mx, desc, th)
+    for j, i in enumerate(res.slot_point):
+        if i >= 0:
+            cur_frame.map_points[j] = map_points[i]
+    return res.match, res.report

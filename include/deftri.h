@@ -402,8 +402,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
    14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report, 17 deftri_orb_params,
-   18 deftri_orb_report, 20 deftri_projection_report (13 and 19 are unassigned and answer -1, like every
-   other index). */
+   18 deftri_orb_report, 20 deftri_projection_report, 22 deftri_essential_report (13, 19 and 21 are
+   unassigned and answer -1, like every other index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -698,6 +698,75 @@ int deftri_match_for_initialization(deftri_ctx *ctx, const deftri_feature_grid *
 int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2,
         const float *kb8_1, const float *kb8_2, const float *T1w, const float *T2w,
         float epipolar_th, uint8_t *inlier, float *err /* may be NULL */, int32_t *score);
+
+/* ---- the second pose from the matches alone: E by RANSAC, then the cameras --------------------- */
+typedef struct deftri_essential_report {
+    int32_t n_matches, n_hypotheses;
+    int32_t n_degenerate;                /* hypotheses flagged degenerate (below) */
+    int32_t best;                        /* the hypothesis kept, -1 when every score is 0 */
+    int32_t best_score;                  /* nInliers (:175) */
+    int32_t round_trips;                 /* blocking device-to-host copies: 1 (0 on a host-only context) */
+    double ms_rays, ms_models, ms_score; /* the stages: device events around the kernels (k_best counts as score),
+                                            the host clock on a host-only context */
+    double ms_total;                     /* host clock over the call */
+} deftri_essential_report;
+
+/* findEssentialWithRANSAC (MonocularMapInitializer.cc:119-178) with the model the reference left commented
+   out (:158): per hypothesis computeE (:180-203) of its 8 matches, computeScoreAndInliers (:206-223)
+   against all n matches, and the first E of the highest score (:167-171).  uv1 / uv2 [2 * n] the matched
+   pixel pairs; samples int32 [n_hyp * 8] the eight match indices of each hypothesis in the order the
+   reference's loop would draw them.  The draws are an input: the reference takes them from cv::kmeans
+   under OpenCV's RNG and random_shuffle under srand(10) (:125-155), neither of which is restated.
+   Outputs: E_best [9] row-major, inlier [n], and (each may be NULL) err [n], scores [n_hyp], E_all
+   [n_hyp * 9], degenerate [n_hyp], report.
+     - Rays: unproject(uv).normalized() in float (:79-80), once per match.
+     - Model: A (8 x 9) with row i = [r1_i * r2_i.x, r1_i * r2_i.y, r1_i * r2_i.z]; e = the right singular
+       vector of its smallest singular value as a row-major 3 x 3; Ef = U diag(1, 1, 0) V^T of e; E = -Ef.
+       Instead of the two JacobiSVDs: the null vector of A by elimination with complete pivoting (rank 8
+       leaves an exact one-dimensional null space) and Ef = e (v1 v1^T / s1 + v2 v2^T / s2) from the two
+       largest eigenpairs (s_i^2, v_i) of e^T e, all in fp64 from the float rays without contraction; E is
+       rounded to float at the end (the reference's is a Matrix3f).
+     - Sign: an SVD leaves the null vector's sign open.  Here its component of largest magnitude is
+       positive (the lowest index on ties), then E = -Ef.  The score does not depend on it.
+     - A hypothesis is degenerate when its sample repeats an index, a sampled ray is not finite, a pivot of
+       the elimination is exactly zero, the second singular value of e is exactly zero, or E is not finite.
+       It is flagged, its E_all row is zero, it scores 0 and is never the best.
+     - Score: per match |float(pi/2) - acos((E r1).normalized() . r2.normalized())| < epipolar_th, the
+       arithmetic of deftri_epipolar_inliers.
+     - Best: replaced on score > bestScore from 0, so the lowest index among the highest scores.  When
+       every score is 0: report.best = -1, E_best is zero, every inlier is 0 (the reference's empty
+       vBestInliers) and err is NaN.  Otherwise inlier and err are those of E_best.
+   The device scores every hypothesis against every match at once (integer counts: the result does not
+   depend on the order) with one upload and one download; a host-only context runs the same functions as
+   sequential loops.  The model arithmetic is the same on both, the rays differ where the two libm's sinf /
+   cosf do.  DEFTRI_E_ARG with a message: n < 8 (as deftri_epipolar_inliers), n_hyp < 1, a sample index
+   outside [0, n), a null required pointer. */
+int deftri_find_essential_ransac(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2,
+        const float *kb8_1, const float *kb8_2, int32_t n_hyp, const int32_t *samples, float epipolar_th,
+        float *E_best /* [9] */, uint8_t *inlier /* [n] */,
+        float *err, int32_t *scores, float *E_all, uint8_t *degenerate /* may be NULL */,
+        deftri_essential_report *report /* may be NULL */);
+
+/* reconstructCameras (MonocularMapInitializer.cc:246-262) over decomposeE (:264-279) for the matches with
+   use[i] != 0 (use [n] may be NULL: all of them), their rays built as reconstructEnvironment does
+   (:228-237).  The reference unprojects both views with its single calibration_; a caller who wants
+   exactly that passes the same kb8 twice.  E [9] row-major; T2w [12] the row-major 3 x 4 (Rgood, t); *away
+   the vote.
+     - R1 = U W^T V^T and R2 = U W V^T of E's SVD, each negated when its determinant is negative; Rgood = R2
+       if trace(R2) > trace(R1), else R1.  As a set {R1, R2} does not depend on the freedom in U and V.
+     - t = U.col(2).normalized(), whose sign the SVD leaves open; the vote depends on it ((R r1 - r2) . (r2 -
+       t) is not odd in t).  Here: the unit left null vector of E with its component of largest magnitude
+       positive (the lowest index on ties).
+     - away = sum over the matches of sign((Rgood r1 - r2) . (r2 - t)), in float per match, an integer sum;
+       t is negated when away is negative (signbit, :259).
+   The decomposition runs on the host in fp64 from the float E (the two largest eigenpairs of E^T E, u_i =
+   E v_i / s_i, u3 = u1 x u2) and is rounded to float; the vote is a kernel on a device context, the
+   sequential loop on a host-only one.  DEFTRI_E_ARG with a message: n < 0, a null required pointer, an E
+   with fewer than two non-zero singular values or a non-finite entry.  n == 0 returns (Rgood, +t) and
+   away 0. */
+int deftri_reconstruct_cameras(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2,
+        const float *kb8_1, const float *kb8_2, const uint8_t *use /* may be NULL */, const float *E,
+        float *T2w /* [12] */, int32_t *away);
 
 /* TEST ONLY: the cell lists of n keypoints as deftri_match_for_initialization builds them for the current
    frame (the device's CSR on a device context, Frame::distributeFeatures' grid on a host-only one):

@@ -30,6 +30,7 @@
 
 #include "dev_arena.h"
 #include "device_math.h"
+#include "epipolar.h"
 #include "matching.h"
 #include "matching_grid.h"
 #include "pose_host.h"
@@ -37,19 +38,7 @@
 namespace deftri {
 
 namespace dev {
-struct Kb8 { float k[8]; };
-struct Mat3 { float m[9]; };
-
-// computeScoreAndInliers (:206-223) for one match: |float(pi/2) - acos(r1_hat . r2.normalized())|
-__host__ __device__ __forceinline__ float epipolar_error(const Kb8 &k1, const Kb8 &k2, const Mat3 &E, float u1, float v1, float u2,
-                                                         float v2) {
-    const V3 r1 = normalized(kb8_unproject(k1.k, u1, v1)), r2 = normalized(kb8_unproject(k2.k, u2, v2));   // :79-80
-    const V3 Er = v3(E.m[0] * r1.x + E.m[1] * r1.y + E.m[2] * r1.z, E.m[3] * r1.x + E.m[4] * r1.y + E.m[5] * r1.z,
-                     E.m[6] * r1.x + E.m[7] * r1.y + E.m[8] * r1.z);
-    const V3 r1_hat = eigen_normalized(Er), r2n = eigen_normalized(r2);
-    const float d = r1_hat.x * r2n.x + r1_hat.y * r2n.y + r1_hat.z * r2n.z;
-    return fabsf((float)(M_PI / 2) - acosf(d));
-}
+// epipolar_error (computeScoreAndInliers for one match) is in epipolar.h, shared with essential.hip
 
 // the cell of every keypoint (c * rows + r, -1 outside the grid) and the cells' sizes
 __global__ void k_grid_cells(int n, const float *__restrict__ uv, GridGeom G, int *__restrict__ cell, int *__restrict__ count) {

@@ -30,6 +30,7 @@
 #include "graph_builder.h"
 #include "kernels.h"
 #include "features.h"
+#include "essential.h"
 #include "matching.h"
 #include "metrics.h"
 #include "orb.h"
@@ -1508,6 +1509,7 @@ int64_t deftri_sizeof(int32_t which) {
         case 17: return (int64_t)sizeof(deftri_orb_params);
         case 18: return (int64_t)sizeof(deftri_orb_report);
         case 20: return (int64_t)sizeof(deftri_projection_report);
+        case 22: return (int64_t)sizeof(deftri_essential_report);
         default: return -1;
     }
 }
@@ -2087,6 +2089,34 @@ int deftri_epipolar_inliers(deftri_ctx *ctx, int32_t n, const float *uv1, const 
     std::string msg;
     const int rc = epipolar_inliers(ctx->device, ctx->st, n, uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th, inlier, err, score,
                                     msg);
+    return rc ? fail(ctx, rc, msg) : 0;
+}
+
+// ---- findEssentialWithRANSAC with a model per hypothesis, and reconstructCameras (essential.hip) ----
+int deftri_find_essential_ransac(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                                 const float *kb8_2, int32_t n_hyp, const int32_t *samples, float epipolar_th, float *E_best,
+                                 uint8_t *inlier, float *err, int32_t *scores, float *E_all, uint8_t *degenerate,
+                                 deftri_essential_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!uv1 || !uv2 || !kb8_1 || !kb8_2 || !samples || !E_best || !inlier)
+        return fail(ctx, DEFTRI_E_ARG, "find_essential_ransac: null array");
+    if (n < 8)
+        return fail(ctx, DEFTRI_E_ARG, "find_essential_ransac: fewer than 8 matches: cv::kmeans refuses fewer samples than its 8 "
+                                       "clusters (MonocularMapInitializer.cc:130) and the reference throws");
+    if (n_hyp < 1) return fail(ctx, DEFTRI_E_ARG, "find_essential_ransac: n_hyp < 1");
+    std::string msg;
+    const int rc = find_essential_ransac(ctx->device, ctx->st, n, uv1, uv2, kb8_1, kb8_2, n_hyp, samples, epipolar_th, E_best, inlier,
+                                         err, scores, E_all, degenerate, report, msg);
+    return rc ? fail(ctx, rc, msg) : 0;
+}
+
+int deftri_reconstruct_cameras(deftri_ctx *ctx, int32_t n, const float *uv1, const float *uv2, const float *kb8_1,
+                               const float *kb8_2, const uint8_t *use, const float *E, float *T2w, int32_t *away) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || (n > 0 && (!uv1 || !uv2)) || !kb8_1 || !kb8_2 || !E || !T2w || !away)
+        return fail(ctx, DEFTRI_E_ARG, "reconstruct_cameras: null array or negative n");
+    std::string msg;
+    const int rc = reconstruct_cameras(ctx->device, ctx->st, n, uv1, uv2, kb8_1, kb8_2, use, E, T2w, away, msg);
     return rc ? fail(ctx, rc, msg) : 0;
 }
 

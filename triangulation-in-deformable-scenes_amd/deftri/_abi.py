@@ -217,6 +217,15 @@ class ProjectionReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class EssentialReport(C.Structure):
+    _fields_ = [("n_matches", i32), ("n_hypotheses", i32), ("n_degenerate", i32), ("best", i32), ("best_score", i32),
+                ("round_trips", i32), ("ms_rays", f64), ("ms_models", f64), ("ms_score", f64), ("ms_total", f64)]
+
+    def as_dict(self):
+        """The counters; the times (ms_*) are measurements, not results."""
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -78,6 +78,11 @@ def load():
         "deftri_epipolar_inliers": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
                                               P(C.c_float), P(C.c_float), C.c_float, P(C.c_uint8), P(C.c_float),
                                               P(C.c_int32)]),
+        "deftri_find_essential_ransac": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                                   C.c_int32, P(C.c_int32), C.c_float, P(C.c_float), P(C.c_uint8), P(C.c_float),
+                                                   P(C.c_int32), P(C.c_float), P(C.c_uint8), P(_abi.EssentialReport)]),
+        "deftri_reconstruct_cameras": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float),
+                                                 P(C.c_uint8), P(C.c_float), P(C.c_float), P(C.c_int32)]),
         "deftri_debug_feature_grid_cells": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
                                                       P(C.c_int32)]),
         "deftri_search_with_projection": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
@@ -207,6 +212,7 @@ EXPORTED = [
     "deftri_triangulate", "deftri_reconstruct_points", "deftri_init_depth_scales",
     "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
     "deftri_search_with_projection", "deftri_guided_matching", "deftri_map_point_descriptors",
+    "deftri_find_essential_ransac", "deftri_reconstruct_cameras",
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
 ]
@@ -290,6 +296,15 @@ class ProjectionMatchResult:
     def __init__(self, match, status, uv, best, second, slot_point, report, view_cos=None, predicted_octave=None):
         self.match, self.status, self.uv, self.best, self.second = match, status, uv, best, second
         self.slot_point, self.report, self.view_cos, self.predicted_octave = slot_point, report, view_cos, predicted_octave
+
+
+class EssentialResult:
+    """The result of Context.find_essential_ransac: E float32 [3, 3] the best model (zero when there is none),
+    inlier bool [n] and err float32 [n] under it (NaN without one), scores int32 [n_hyp], E_all float32 [n_hyp, 3, 3],
+    degenerate bool [n_hyp], report (deftri_essential_report as a dict; report["best"] is -1 when every score is 0)."""
+
+    def __init__(self, E, inlier, err, scores, E_all, degenerate, report):
+        self.E, self.inlier, self.err, self.scores, self.E_all, self.degenerate, self.report = E, inlier, err, scores, E_all, degenerate, report
 
 
 class MapPointDescriptors:
@@ -724,6 +739,43 @@ class Context:
         self._check(self.lib.deftri_epipolar_inliers(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2), _fp(Ta), _fp(Tb),
                                                      float(epipolar_th), _u8p(inl), _fp(err), C.byref(score)))
         return inl.astype(bool), err, int(score.value)
+
+    def find_essential_ransac(self, uv1, uv2, kb8_1, kb8_2, samples, epipolar_th):
+        """findEssentialWithRANSAC (MonocularMapInitializer.cc:119-178) with a model per hypothesis for matched pixel
+        pairs (deftri_find_essential_ransac): samples int [n_hyp, 8] the match indices each hypothesis is fitted to.
+        Every hypothesis is scored against every match on the device, or in sequential loops on a host-only
+        context.  Returns an EssentialResult."""
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        k1, k2 = _f32(kb8_1).reshape(8), _f32(kb8_2).reshape(8)
+        smp = np.ascontiguousarray(samples, np.int32)
+        if smp.ndim != 2 or smp.shape[1] != 8:
+            raise ValueError(f"find_essential_ransac: samples must be [n_hyp, 8], got {smp.shape}")
+        H = len(smp)
+        E = np.zeros((3, 3), np.float32); inl = np.zeros(n, np.uint8); err = np.zeros(n, np.float32)
+        scores = np.zeros(H, np.int32); E_all = np.zeros((H, 3, 3), np.float32); deg = np.zeros(H, np.uint8)
+        rep = _abi.EssentialReport()
+        self._check(self.lib.deftri_find_essential_ransac(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2), H, _ip(smp),
+                                                          float(epipolar_th), _fp(E), _u8p(inl), _fp(err), _ip(scores), _fp(E_all),
+                                                          _u8p(deg), C.byref(rep)))
+        return EssentialResult(E, inl.astype(bool), err, scores, E_all, deg.astype(bool), rep.as_dict())
+
+    def reconstruct_cameras(self, uv1, uv2, kb8_1, kb8_2, E, use=None):
+        """reconstructCameras (MonocularMapInitializer.cc:246-262) for matched pixel pairs (deftri_reconstruct_cameras):
+        E float [3, 3], use bool [n] the matches that vote (None: all).  Returns (T2w as an SE3f (Rgood, t), away)."""
+        from .mapmodel import SE3f
+        uv1, uv2, n = _pixel_pairs(uv1, uv2)
+        k1, k2 = _f32(kb8_1).reshape(8), _f32(kb8_2).reshape(8)
+        E = _f32(E).reshape(3, 3)
+        T = np.zeros((3, 4), np.float32)
+        away = C.c_int32(0)
+        u = None
+        if use is not None:
+            u = np.ascontiguousarray(use, np.uint8).reshape(-1)
+            if len(u) != n:
+                raise ValueError(f"reconstruct_cameras: {n} matches and {len(u)} flags")
+        self._check(self.lib.deftri_reconstruct_cameras(self.h, n, _fp(uv1), _fp(uv2), _fp(k1), _fp(k2),
+                                                        None if u is None else _u8p(u), _fp(E), _fp(T), C.byref(away)))
+        return SE3f(T[:, :3].copy(), T[:, 3].copy()), int(away.value)
 
     def _frame_arrays(self, Tcw, kb8, uv2, octave2, desc2):
         """The current frame's arguments of the projection matchers."""

@@ -13,20 +13,26 @@ the map construction with the initial depth scales (Mapping.cc:171-254).
                                   the same from keypoints, octaves and descriptors: the match and the inlier
                                   mask on the device (matching.py holds their host restatements), then
                                   monocular_map_initialization
+  compute_max_tries() / ransac_samples() / reconstruct_environment()
+                                  the map from two keyframes without a pose for the second: the RANSAC over E with a
+                                  model per hypothesis and reconstructCameras on the device (MonocularMapInitializer.cc:
+                                  114-279; matching.py holds their host restatements), then monocular_map_initialization
   extract_features()              Mapping::extractFeatures (Mapping.cc:120-129): FAST::extract, then ORB::describe
                                   with the caller's sampling pattern (features.py)
   set_keypoints_from_features()   a keyframe's keypoints, octaves and angles from FAST::extract's result
                                   (features.extract / Context.fast_extract), optionally its descriptors from
                                   ORB::describe's
 
-The poses are inputs, as they are to the reference's RANSAC, which builds E from them in every iteration
-(MonocularMapInitializer.cc:160-163).  Still out of scope: estimating E from the samples (computeE,
-reconstructCameras), and the matchers the reference never calls (guidedMatching,
-searchWithProjection, searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
+To monocular_map_initialization and _from_features the poses are inputs, as they are to the reference's RANSAC,
+which builds E from them in every iteration (MonocularMapInitializer.cc:160-163); reconstruct_environment
+estimates E from the samples (computeE) and the second pose from it (reconstructCameras).  Still out of scope:
+the matchers the reference never calls (searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
 MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
 the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
 reconstructPoints, which receives minCos as fMinParallax, :60).
 """
+import math
+
 import numpy as np
 
 from . import matching, sim
@@ -252,6 +258,86 @@ def monocular_map_initialization_from_features(ctx, kf_ref, kf_cur, settings):
             return None, report
         matches[idx[~inlier]] = -1
     m, rep = monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings)
+    return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})
+
+
+def compute_max_tries(inlier_fraction, success_likelihood):
+    """computeMaxTries (MonocularMapInitializer.cc:114-117): log(1 - p) / log(1 - w^8) of two floats, truncated;
+    (0.8, 0.95), the reference's arguments (:140), gives 16."""
+    w, p = float(np.float32(inlier_fraction)), np.float32(success_likelihood)
+    return int(math.log(float(np.float32(1) - p)) / math.log(1.0 - w ** 8))
+
+
+def ransac_samples(uv1, n_hyp, seed=10, return_labels=False):
+    """Samples for Context.find_essential_ransac in the shape of MonocularMapInitializer.cc:128-155, not its draws:
+    the reference keypoints uv1 [n, 2] in eight spatial clusters (Lloyd iterations from eight seeded picks, ten
+    rounds; an empty cluster takes the point farthest from its centre out of a cluster that has more than one), and per
+    hypothesis one index drawn from each cluster, in cluster order.  The reference clusters with cv::kmeans under
+    OpenCV's RNG and draws with random_shuffle under srand(10); neither sequence is reproduced.  Returns int32
+    [n_hyp, 8] (and the labels int [n] with return_labels).  Fewer than 8 points raise ValueError, as cv::kmeans
+    refuses them."""
+    uv = np.asarray(uv1, np.float64).reshape(-1, 2)
+    n = len(uv)
+    if n < 8:
+        raise ValueError(f"ransac_samples: {n} points for 8 clusters")
+    rng = np.random.default_rng(seed)
+    centres = uv[rng.choice(n, 8, replace=False)].copy()
+    labels = np.zeros(n, np.int64)
+    for _ in range(10):
+        d = ((uv[:, None, :] - centres[None]) ** 2).sum(2)
+        labels = np.argmin(np.where(np.isnan(d), np.inf, d), 1)
+        for c in range(8):
+            if (labels == c).any():
+                centres[c] = np.nanmean(uv[labels == c], 0) if np.isfinite(uv[labels == c]).all(1).any() else centres[c]
+    for c in range(8):
+        if not (labels == c).any():
+            size = np.bincount(labels, minlength=8)
+            d = ((uv - centres[labels]) ** 2).sum(1)
+            d = np.where(np.isnan(d), -1.0, d)
+            d[size[labels] < 2] = -2.0
+            k = int(np.argmax(d))
+            labels[k] = c
+            centres[c] = uv[k]
+    clusters = [np.flatnonzero(labels == c) for c in range(8)]
+    samples = np.stack([[cl[rng.integers(len(cl))] for cl in clusters] for _ in range(int(n_hyp))]).astype(np.int32)
+    return (samples, labels) if return_labels else samples
+
+
+def reconstruct_environment(ctx, kf_ref, kf_cur, matches, settings, samples=None, n_hypotheses=None, seed=10):
+    """reconstructEnvironment (MonocularMapInitializer.cc:225-244) behind findEssentialWithRANSAC with a model per
+    hypothesis (:119-203), for two keyframes of which only the reference has a pose, on the device of `ctx`:
+      the RANSAC over the matched pixel pairs (Context.find_essential_ransac) with `samples` [n_hyp, 8], indices into
+      the matched pairs in the order of the reference keypoints (default: ransac_samples of n_hypotheses, by default
+      computeMaxTries(0.8, 0.95) = 16, under `seed`); its inliers are vTriangulated;
+      reconstructCameras on the inliers (Context.reconstruct_cameras): kf_cur.pose = (Rgood, t), kf_ref's pose is
+      passed through as the reference passes T1w;
+      monocular_map_initialization on the matches masked to the inliers.
+    Returns (Map, report): report["n_inliers"] the best score, ["best"], ["n_hypotheses"], ["n_degenerate"], ["away"]
+    next to monocular_map_initialization's.  The Map is None and kf_cur.pose is restored when every score is 0 or
+    reconstructPoints does not accept the pair.  Fewer than 8 matches raise, as cv::kmeans does in the reference."""
+    matches = np.asarray(matches, np.int64).copy()
+    idx = np.flatnonzero(matches >= 0)
+    uv1 = np.ascontiguousarray(kf_ref.keypoints[idx], np.float32)
+    uv2 = np.ascontiguousarray(kf_cur.keypoints[matches[idx]], np.float32)
+    if samples is None:
+        samples = ransac_samples(uv1, compute_max_tries(0.8, 0.95) if n_hypotheses is None else n_hypotheses, seed)
+    res = ctx.find_essential_ransac(uv1, uv2, kf_ref.kb8, kf_cur.kb8, samples, settings.epipolar_th)
+    report = {"n_matches": len(idx), "n_inliers": res.report["best_score"], "best": res.report["best"],
+              "n_hypotheses": res.report["n_hypotheses"], "n_degenerate": res.report["n_degenerate"], "accepted": 0}
+    if res.report["best"] < 0:                                # vBestInliers stays empty: nothing to triangulate
+        return None, report
+    matches[idx[~res.inlier]] = -1
+    pose, away = ctx.reconstruct_cameras(uv1, uv2, kf_ref.kb8, kf_cur.kb8, res.E, res.inlier)
+    report["away"] = away
+    old = kf_cur.pose
+    kf_cur.pose = pose
+    try:
+        m, rep = monocular_map_initialization(ctx, kf_ref, kf_cur, matches, settings)
+    except Exception:
+        kf_cur.pose = old
+        raise
+    if m is None:
+        kf_cur.pose = old
     return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})
 
 

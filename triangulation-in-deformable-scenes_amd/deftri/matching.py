@@ -11,14 +11,18 @@ for the library's entries; written from the reference, not from the library's ho
   epipolar_inliers(..., dtype=)   the mask of MonocularMapInitializer::initialize with Triangulation.checks
                                   (MonocularMapInitializer.cc:93-104, :119-178, :206-223), fp32 or fp64
 
+  unit_rays / compute_essential / epipolar_errors / find_essential_ransac_ref / reconstruct_cameras_ref
+                                  the RANSAC with a model per hypothesis (computeE :180-203, :119-178) and
+                                  reconstructCameras (:246-279) on unit rays, fp32 or fp64, with numpy's SVD
+
   search_with_projection_ref / guided_matching_ref / map_point_descriptors_ref
                                   searchWithProjection (DescriptorMatching.cc:164-253), guidedMatching (:101-162) and
                                   Map::updateOrientationAndDescriptor (Map.cc:270-321), fp32 or fp64
   guided_matching(ctx, ...) / search_with_projection(ctx, ...)
                                   the two matchers on a context, setting the frame's map point slots
 
-The device versions are capi.Context.match_for_initialization, .epipolar_inliers, .search_with_projection,
-.guided_matching and .map_point_descriptors.  Quirks kept as they
+The device versions are capi.Context.match_for_initialization, .epipolar_inliers, .find_essential_ransac,
+.reconstruct_cameras, .search_with_projection, .guided_matching and .map_point_descriptors.  Quirks kept as they
 stand: posInGrid rounds half away from zero to a cell index, so a keypoint in the last half cell on the right
 or at the bottom is in no cell and never a candidate; only reference keypoints of octave <= 0 are searched;
 best and second start at 255; a tie for best rejects; the matches are not one-to-one; the RANSAC scores the
@@ -202,6 +206,129 @@ def epipolar_inliers(uv1, uv2, kb8_1, kb8_2, T1w, T2w, epipolar_th, dtype=np.flo
         err = np.abs(half_pi - np.arccos(d)).astype(dt)
         inl = err < dt.type(F(epipolar_th))
     return inl, err, int(inl.sum())
+
+
+# ---- E from the matches alone: computeE per hypothesis, the score of every hypothesis, reconstructCameras ------
+def unit_rays(kb8, uv, dtype=np.float64):
+    """unproject(uv).normalized() (MonocularMapInitializer.cc:79-80) for rows of uv, in `dtype`."""
+    from .mapping import _kb8_unproject
+    dt = np.dtype(dtype)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r = _kb8_unproject(kb8, np.asarray(uv, F).reshape(-1, 2), dt).astype(dt)
+        return (r / np.linalg.norm(r, axis=1, keepdims=True)).astype(dt)
+
+
+def _largest_positive(v):
+    """v with the sign that makes its component of largest magnitude positive (the lowest index on ties)."""
+    return -v if v[int(np.argmax(np.abs(v)))] < 0 else v
+
+
+def compute_essential(r1, r2, dtype=np.float64):
+    """computeE (MonocularMapInitializer.cc:180-203) of eight ray pairs r1, r2 [8, 3] in `dtype`, with numpy's SVD:
+    A's row i = [r1_i * r2_i.x, r1_i * r2_i.y, r1_i * r2_i.z]; e = the right singular vector of the smallest singular
+    value, its component of largest magnitude positive (the library's choice of the sign an SVD leaves open), as a
+    3 x 3; Ef = U diag(1, 1, 0) V^T of e; returns -Ef.  None for a degenerate sample: a ray that is not finite, A of
+    rank below 8, or a zero second singular value of e."""
+    dt = np.dtype(dtype)
+    r1 = np.asarray(r1, dt).reshape(8, 3); r2 = np.asarray(r2, dt).reshape(8, 3)
+    if not (np.isfinite(r1).all() and np.isfinite(r2).all()):
+        return None
+    A = np.concatenate([r1 * r2[:, 0:1], r1 * r2[:, 1:2], r1 * r2[:, 2:3]], 1)
+    _, s, Vt = np.linalg.svd(A)
+    if not s[7] > 0:
+        return None
+    e = _largest_positive(Vt[8]).reshape(3, 3)
+    U, s3, Vt3 = np.linalg.svd(e)
+    if not s3[1] > 0:
+        return None
+    return (-(U @ np.diag(np.array([1, 1, 0], dt)) @ Vt3)).astype(dt)
+
+
+def sample_condition(r1, r2):
+    """sigma_1 / sigma_8 of a sample's A (fp64): how far an error of the rays is amplified in its null vector."""
+    r1 = np.asarray(r1, np.float64).reshape(8, 3); r2 = np.asarray(r2, np.float64).reshape(8, 3)
+    s = np.linalg.svd(np.concatenate([r1 * r2[:, 0:1], r1 * r2[:, 1:2], r1 * r2[:, 2:3]], 1), compute_uv=False)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return float(s[0] / s[7])
+
+
+def epipolar_errors(E, r1, r2, dtype=np.float64):
+    """computeScoreAndInliers' error (:207-211) of every ray pair under E, in `dtype`: |pi/2 - acos((E r1).normalized()
+    . r2.normalized())|, the sums in the order written."""
+    dt = np.dtype(dtype)
+    E = np.asarray(E, dt).reshape(3, 3); r1 = np.asarray(r1, dt); r2 = np.asarray(r2, dt)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        Er = np.stack([(E[a, 0] * r1[:, 0] + E[a, 1] * r1[:, 1]) + E[a, 2] * r1[:, 2] for a in range(3)], 1)
+        a, b = _eigen_normalized(Er), _eigen_normalized(r2)
+        d = ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]).astype(dt)
+        return np.abs(dt.type(np.pi / 2) - np.arccos(d)).astype(dt)
+
+
+def find_essential_ransac_ref(r1, r2, samples, epipolar_th, dtype=np.float64, E_all=None):
+    """findEssentialWithRANSAC (:119-178) with computeE in every iteration, on unit rays r1, r2 [n, 3] and samples
+    [n_hyp, 8], in `dtype`.  E_all [n_hyp, 3, 3] replaces the models (the scores of given models; a zero model counts
+    as degenerate).  A degenerate hypothesis (a repeated index, or compute_essential's None) scores 0.  The best is
+    replaced on score > bestScore from 0 (:167).  Returns a dict: E, best (-1: every score 0), inlier, err (NaN
+    without a best), scores, E_all, degenerate, err_all [n_hyp, n]."""
+    dt = np.dtype(dtype)
+    r1 = np.asarray(r1, dt); r2 = np.asarray(r2, dt)
+    samples = np.asarray(samples, np.int64).reshape(-1, 8)
+    H, n = len(samples), len(r1)
+    if samples.min() < 0 or samples.max() >= n:
+        raise ValueError("a sample index outside [0, n)")
+    models = np.zeros((H, 3, 3), dt); deg = np.zeros(H, bool)
+    scores = np.zeros(H, np.int64); err_all = np.full((H, n), np.nan, dt)
+    th = dt.type(F(epipolar_th))
+    best, best_score = -1, 0
+    for h in range(H):
+        if E_all is not None:
+            E = np.asarray(E_all[h], dt).reshape(3, 3)
+            E = None if not E.any() else E
+        else:
+            E = None if len(set(samples[h].tolist())) < 8 else compute_essential(r1[samples[h]], r2[samples[h]], dt)
+        if E is None:
+            deg[h] = True
+            continue
+        models[h] = E
+        err_all[h] = epipolar_errors(E, r1, r2, dt)
+        with np.errstate(invalid="ignore"):
+            scores[h] = int((err_all[h] < th).sum())
+        if scores[h] > best_score:
+            best, best_score = h, int(scores[h])
+    with np.errstate(invalid="ignore"):
+        inl = err_all[best] < th if best >= 0 else np.zeros(n, bool)
+    return {"E": models[best] if best >= 0 else np.zeros((3, 3), dt), "best": best, "inlier": inl,
+            "err": err_all[best] if best >= 0 else np.full(n, np.nan, dt), "scores": scores, "E_all": models,
+            "degenerate": deg, "err_all": err_all}
+
+
+def reconstruct_cameras_ref(E, r1, r2, use=None, dtype=np.float64, flip_t0=False):
+    """reconstructCameras (:246-262) over decomposeE (:264-279) on unit rays, in `dtype`, with numpy's SVD: R1 = U W^T
+    V^T, R2 = U W V^T, each negated when its determinant is negative; Rgood = R2 if trace(R2) > trace(R1) else R1; t =
+    U.col(2) with its component of largest magnitude positive (the library's choice; flip_t0 starts from the other
+    sign); away = sum of sign((Rgood r1 - r2) . (r2 - t)) over the used rows; t negated when away < 0.  Returns
+    (Rgood, t, away)."""
+    dt = np.dtype(dtype)
+    E = np.asarray(E, dt).reshape(3, 3); r1 = np.asarray(r1, dt); r2 = np.asarray(r2, dt)
+    if use is not None:
+        use = np.asarray(use, bool)
+        r1, r2 = r1[use], r2[use]
+    U, _, Vt = np.linalg.svd(E)
+    W = np.array([[0, -1, 0], [1, 0, 0], [0, 0, 1]], dt)
+    R1 = U @ W.T @ Vt
+    R2 = U @ W @ Vt
+    R1 = -R1 if np.linalg.det(R1) < 0 else R1
+    R2 = -R2 if np.linalg.det(R2) < 0 else R2
+    Rg = R2 if np.trace(R2) > np.trace(R1) else R1
+    t = _largest_positive(U[:, 2] / np.linalg.norm(U[:, 2])).astype(dt)
+    if flip_t0:
+        t = -t
+    with np.errstate(invalid="ignore"):
+        a = np.stack([(Rg[i, 0] * r1[:, 0] + Rg[i, 1] * r1[:, 1]) + Rg[i, 2] * r1[:, 2] for i in range(3)], 1) - r2
+        b = r2 - t
+        s = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+        away = int((s > 0).sum()) - int((s < 0).sum())
+    return Rg.astype(dt), (-t if away < 0 else t).astype(dt), away
 
 
 # ---- map points into a frame by projection: guidedMatching, searchWithProjection and what they read ------------

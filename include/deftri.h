@@ -402,8 +402,9 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    7 deftri_plan_info, 8 deftri_deformation_params, 9 deftri_deformation_report,
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
    14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report, 17 deftri_orb_params,
-   18 deftri_orb_report, 20 deftri_projection_report, 22 deftri_essential_report (13, 19 and 21 are
-   unassigned and answer -1, like every other index). */
+   18 deftri_orb_report, 20 deftri_projection_report, 22 deftri_essential_report,
+   23 deftri_triangulation_match_report (13, 19 and 21 are unassigned and answer -1, like every other
+   index). */
 int64_t deftri_sizeof(int32_t which);
 
 /* ---- map-level API (Modules/Optimization/g2oBundleAdjustment.h:56-60) ---------------- */
@@ -894,6 +895,94 @@ int deftri_map_point_descriptors(deftri_ctx *ctx, int32_t n, const float *pos, c
         int32_t n_kf, const float *kf_Tcw, const int32_t *kf_slot_start, const uint8_t *kf_desc, const int32_t *kf_octave,
         int32_t n_scales, float scale_factor,
         float *normal, float *max_dist, float *min_dist, uint8_t *desc, int32_t *ref_obs, uint8_t *status);
+
+/* ---- growing the map past two keyframes: searchForTriangulation and fuse ------------------------- */
+typedef struct deftri_triangulation_match_report {
+    int32_t n1, n2;
+    int32_t n_matches;                   /* the reference's return value: rows of status 0 */
+    int32_t n_occupied;                  /* status 1 */
+    int32_t n_unmatched;                 /* status 2 */
+    int32_t n_stolen;                    /* status 3 */
+    int32_t n_flag_skipped;              /* status 4 */
+    int32_t flag_row;                    /* the row accepted at distance exactly 2 that set vbMatched2[2]; -1: none */
+    int64_t n_listed;                    /* pairs in the device's candidate lists (0 on a host-only context) */
+    int32_t round_trips;                 /* blocking device-to-host copies: 1, or 2 when the lists outgrew the first buffer (0 on a host-only context) */
+    int32_t reserved;
+    double ms_device;                    /* host clock: checks, uploads, kernels and the download */
+    double ms_loop;                      /* host clock over the sequential loop (the whole search on a host-only context) */
+    double ms_total;                     /* host clock over the call */
+} deftri_triangulation_match_report;
+
+/* searchForTriangulation(kf1, kf2, th, fEpipolarTh, E, vMatches) (Modules/Matching/DescriptorMatching.cc:255-328).
+   Keyframe 1: n1 keypoints uv1 [2 * n1], desc1 [32 * n1], has_point1 [n1] (non-zero: the slot already holds a
+   map point); keyframe 2 likewise.  One kb8: the reference unprojects both frames with kf1's calibration
+   (:267).  E [9] row-major.  Outputs: matches [n1] the keypoint of keyframe 2 or -1; best_dist [n1] (may be
+   NULL) the distance a row was accepted at, 255 where it never was; status [n1]; *n_matches; report (may be
+   NULL).  Status: 0 matched, 1 slot occupied, not searched, 2 no eligible candidate below th, 3 matched, then
+   un-matched by a later row that took its keypoint (best_dist keeps the distance), 4 passed over by the flag
+   quirk.  Restated as it stands:
+     - rows in order; row i is searched only if has_point1[i] == 0 (:277);
+     - ray1 = (E * unproject(uv1_i)).normalized(), the unprojected ray not normalized first (:282);
+     - bestDist starts at 255; candidates j in order; skipped if has_point2[j] != 0 (:288), if dist > 50 or
+       dist > bestDist (:293), or if vMatchedDistance[j] <= dist (:296); only then ray2 =
+       unproject(uv2_j).normalized() and the epipolar test, and only a pass sets bestDist = dist, bestIdx = j;
+     - the test: float err = fabs(M_PI/2 - acos(ray2.dot(ray1))) < fEpipolarTh.  The dot product is a float
+       and acos its float overload (the file is `using namespace std`); M_PI/2 is a double, so the difference
+       and fabs are double, rounded to float when stored in err; the comparison is float.  This is not
+       computeScoreAndInliers' float(pi/2) - acos(.) in float (deftri_epipolar_inliers).  normalized() is
+       Eigen's (a vector whose squared norm is not positive is returned as it is); a NaN compares false, so a
+       non-finite ray fails every test;
+     - bestDist moves only on a pass, so a row's result does not depend on the order of j: it is the minimum
+       dist over the j that pass every test, the LARGEST such j among equals (an equal distance replaces);
+     - accepted iff bestDist < th, strictly (:310).  Then vMatchedDistance[bestIdx] = bestDist, and a row
+       that held bestIdx before loses it (matches -1, *n_matches one less): the steal, always by a strictly
+       smaller distance.  A robbed row does not search again;
+     - SIZES: the reference sizes vMatchedDistance and vnMatches21 by n1 and indexes them by j.  Here they
+       have n2 elements: identical for n2 <= n1, and a definition where the reference writes past its vectors;
+     - KEPT QUIRK (flag_quirk != 0): vbMatched2 is read as vbMatched2[2] for every j and written as
+       vbMatched2[bestDist] = true, so the whole vector is one boolean: some earlier row was accepted at
+       distance exactly 2.  From then on every j is passed over and no row matches: status 4; the report
+       names the row that set it.  (For n2 <= 2 the reference reads past the vector; here the boolean stands
+       for it.)  flag_quirk == 0 ignores the vector; vMatchedDistance already makes the result one-to-one.
+   On a device context: a ray kernel (one thread per keypoint of either frame); a candidate kernel, one wave
+   per searched row, that lists the pairs with a free slot, dist <= min(50, th - 1) and a passed epipolar test
+   (a pair with dist >= th can only raise a bestDist that is not accepted) compacted per row in ascending j,
+   sized by a count pass and a scan; one download; then the loop above over the lists, whose remaining tests
+   are dist > bestDist and vMatchedDistance.  The first fill pass has room for 64 n1 + 4096 pairs; only a
+   call with more takes a second fill pass into a buffer of the exact size and a second download
+   (round_trips 2).  The result equals a host-only context's loop over all pairs for every input, except
+   where err sits within the two libm's ulps (sinf, cosf, acosf) of epipolar_th.
+   DEFTRI_E_ARG with a message: th > 255 (a row without candidate would pass bestDist < th and the reference
+   uses an uninitialised bestIdx), n1 < 0 or n2 < 0, a null required pointer.  n1 == 0 or n2 == 0 returns 0
+   with every match -1. */
+int deftri_search_for_triangulation(deftri_ctx *ctx, int32_t n1, const float *uv1, const uint8_t *desc1,
+        const uint8_t *has_point1, int32_t n2, const float *uv2, const uint8_t *desc2, const uint8_t *has_point2,
+        const float *kb8, const float *E /* [9] */, int32_t th, float epipolar_th, int32_t flag_quirk,
+        int32_t *matches /* [n1] */, int32_t *best_dist /* [n1], may be NULL */, uint8_t *status /* [n1] */,
+        int32_t *n_matches, deftri_triangulation_match_report *report /* may be NULL */);
+
+/* The search of fuse(pKF, th, vMapPoints, pMap) (DescriptorMatching.cc:330-428) for n map points against the
+   keyframe, given as the frame of deftri_guided_matching (grid, Tcw, kb8, uv2, octave2, desc2).  Inside fuse
+   the search for point i does not depend on earlier iterations — no candidate is skipped because its slot is
+   taken — only the map edits are sequential, and those stay with the caller.  Per point: consider [n] (0: the
+   point is passed over, status 6), pos [3 * n], octave [n] (the reference reads pKF->getKeyPoint(i).octave,
+   the list index used as a keypoint index, :366: the caller passes what it wants read), desc [32 * n].
+   Outputs: match [n] the accepted keypoint or -1, status [n], and (each may be NULL) uv [2 * n], best, second
+   [n], report with rounds = 1.
+     - uv = project(Tcw X), no depth test (:362-363); a non-finite projection is status 5;
+     - radius = (float)(2.5 * (double)getScaleFactor(octave)) (:369), levels octave +- 1;
+     - getFeaturesInArea with the rounding and last-half-cell behaviour of deftri_match_for_initialization;
+       no candidate: status 3 (:375);
+     - best and second start at 255; accepted iff best <= th && (float)best < float(second) * 0.9, else
+       status 4 (a best of 255 or more leaves bestIdx unset, :400, and is rejected by the same test).
+   The kernel is deftri_search_with_projection's with every slot free, run once; one blocking copy.  An
+   octave outside [0, n_scales) on a considered point or on a keypoint is DEFTRI_E_ARG, as are the grid
+   errors and a null required pointer.  n == 0 or n2 == 0 writes nothing beyond the report. */
+int deftri_fuse_search(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8,
+        int32_t n2, const float *uv2, const int32_t *octave2, const uint8_t *desc2,
+        int32_t n, const uint8_t *consider, const float *pos, const int32_t *octave, const uint8_t *desc /* n x 32 */,
+        int32_t th, int32_t *match /* [n] */, uint8_t *status /* [n] */, float *uv, int32_t *best,
+        int32_t *second /* may be NULL */, deftri_projection_report *report /* may be NULL */);
 
 /* ---- from an image to keypoints: FAST::extract (Modules/Features/FAST.cc:81-118, FAST.h:52-97) --- */
 #define DEFTRI_FAST_MAX_LEVELS 16

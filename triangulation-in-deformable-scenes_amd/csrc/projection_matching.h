@@ -13,17 +13,18 @@
 namespace deftri {
 
 // The arguments of deftri_search_with_projection (guided == false) and deftri_guided_matching (guided ==
-// true), already checked for null required pointers by the callers.  The per-point outputs other than
+// true; fuse == true on top of it: deftri_fuse_search, DescriptorMatching.cc:330-428), already checked for null required pointers by the callers.  The per-point outputs other than
 // match may be null.
 struct ProjectionMatchArgs {
     bool guided;
+    bool fuse;                     // the search of fuse: guided's inputs (has_point: consider), no slots, one round
     const deftri_feature_grid *grid;
     const float *Tcw, *kb8;
     int32_t n2;
     const float *uv2;
     const int32_t *octave2;
     const uint8_t *desc2;
-    int32_t *slot_point;           // searchWithProjection: in and out; guidedMatching: out
+    int32_t *slot_point;           // searchWithProjection: in and out; guidedMatching: out; fuse: null
     int32_t n;
     const float *pos;
     const uint8_t *desc;

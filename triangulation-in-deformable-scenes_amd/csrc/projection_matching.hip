@@ -9,6 +9,8 @@
 // The skip makes point i depend on the claims of every accepted point before it.
 //   k_prepare_points     one thread per point: view cosine, distance, predicted octave, projection, radius
 //   k_match_round        one 64-lane wave per point, against the claims of the previous round
+// The search of fuse (:330-428, deftri_fuse_search) is the same window search with every slot free and no
+// claims, so one round of k_match_round is its result; its prepare step is prepare_fuse.
 // Claims are resolved in rounds (deftri.h has the argument): claim[j] holds the lowest index of a point
 // that claimed keypoint j in the previous round (-1: occupied before the call, INT_MAX: free); point i
 // skips j iff claim[j] < i; accepted points write their index into the next round's table with
@@ -113,13 +115,26 @@ __host__ __device__ __forceinline__ PointPrep prepare_guided(const ProjCam &C, V
     return p;
 }
 
+// fuse :362-369 for one considered map point: no depth test, radius = 2.5 * getScaleFactor(octave) in double
+__host__ __device__ __forceinline__ PointPrep prepare_fuse(const ProjCam &C, V3 X, int octave, const float *scale) {
+    PointPrep p;
+    p.view_cos = 0.0f;
+    p.octave = octave;
+    project_world(C, X, p.x, p.y);
+    p.radius = (float)(2.5 * (double)scale[octave]);
+    p.status = finite2(p.x, p.y) ? 0 : ST_UNDEFINED;
+    return p;
+}
+
+enum { MODE_PROJECTION = 0, MODE_GUIDED = 1, MODE_FUSE = 2 };
+
 struct PrepOut {
     float *x, *y, *radius, *view_cos;
     int *octave, *match, *best, *second;
     uint8_t *status;
 };
 
-__global__ void k_prepare_points(int n, bool guided, ProjCam C, const float *__restrict__ pos, const float *__restrict__ normal,
+__global__ void k_prepare_points(int n, int mode, ProjCam C, const float *__restrict__ pos, const float *__restrict__ normal,
                                  const float *__restrict__ min_dist, const float *__restrict__ max_dist,
                                  const uint8_t *__restrict__ has_point, const int *__restrict__ octave1, int window15, int n_scales,
                                  const float *__restrict__ scale, float log_scale1, PrepOut o) {
@@ -127,8 +142,8 @@ __global__ void k_prepare_points(int n, bool guided, ProjCam C, const float *__r
     if (i >= n) return;
     PointPrep p;
     const V3 X = v3(pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]);
-    if (guided) {
-        if (has_point[i]) p = prepare_guided(C, X, octave1[i], window15, scale);
+    if (mode != MODE_PROJECTION) {
+        if (has_point[i]) p = mode == MODE_FUSE ? prepare_fuse(C, X, octave1[i], scale) : prepare_guided(C, X, octave1[i], window15, scale);
         else { p.x = p.y = p.radius = p.view_cos = 0.0f; p.octave = -1; p.status = ST_EMPTY_SLOT; }
     } else {
         p = prepare_projection(C, X, v3(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]), min_dist[i], max_dist[i], n_scales,
@@ -357,7 +372,7 @@ void fill_report(const ProjectionMatchArgs &a, int rounds, int round_trips, doub
 
 int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, std::string &err) {
     const auto t0 = std::chrono::steady_clock::now();
-    const char *name = a.guided ? "guided_matching" : "search_with_projection";
+    const char *name = a.fuse ? "fuse_search" : a.guided ? "guided_matching" : "search_with_projection";
     const deftri_feature_grid &grid = *a.grid;
     const std::string why = grid_error(grid);
     if (!why.empty()) {
@@ -381,7 +396,7 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
     if (a.guided)
         for (int32_t i = 0; i < a.n; i++)
             if (a.has_point[i] && (a.octave1[i] < 0 || a.octave1[i] >= grid.n_scales)) {
-                err = std::string(name) + ": reference keypoint " + std::to_string(i) + " has octave " + std::to_string(a.octave1[i]) +
+                err = std::string(name) + (a.fuse ? ": map point " : ": reference keypoint ") + std::to_string(i) + " has octave " + std::to_string(a.octave1[i]) +
                       ", outside [0, nScales = " + std::to_string(grid.n_scales) + ")";
                 return DEFTRI_E_ARG;
             }
@@ -409,7 +424,8 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
             const V3 X = v3(a.pos[3 * i], a.pos[3 * i + 1], a.pos[3 * i + 2]);
             PointPrep p;
             if (a.guided) {
-                if (a.has_point[i]) p = prepare_guided(C, X, a.octave1[i], window15, scale.data());
+                if (a.has_point[i])
+                    p = a.fuse ? prepare_fuse(C, X, a.octave1[i], scale.data()) : prepare_guided(C, X, a.octave1[i], window15, scale.data());
                 else { p.x = p.y = p.radius = p.view_cos = 0.0f; p.octave = -1; p.status = ST_EMPTY_SLOT; }
             } else {
                 p = prepare_projection(C, X, v3(a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2]), a.min_dist[i],
@@ -445,7 +461,7 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
                         }
                     }
                     if (accept_match(best, second, a.th)) {                   // :246-249
-                        slot[best_idx] = i;
+                        if (!a.fuse) slot[best_idx] = i;                      // fuse: the slots are the caller's to edit
                         m = best_idx;
                         status = ST_MATCHED;
                     } else status = ST_REJECTED;
@@ -459,7 +475,7 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
             if (a.best) a.best[i] = best;
             if (a.second) a.second[i] = second;
         }
-        std::memcpy(a.slot_point, slot.data(), sizeof(int32_t) * (size_t)n2);
+        if (a.slot_point) std::memcpy(a.slot_point, slot.data(), sizeof(int32_t) * (size_t)n2);
         const double total = ms_since(t0);
         fill_report(a, 1, 0, 0.0, total, total);
         return 0;
@@ -504,12 +520,23 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
     hipMemcpyAsync(d_claim[0], d_base, 4 * N2, hipMemcpyDeviceToDevice, st);
     launch_grid(G, n2, d_uv2, d_cell, d_count, d_start, d_cursor, d_keys, st);
     const PrepOut po{d_x, d_y, d_radius, d_cos, d_octave, d_match, d_best, d_second, d_status};
-    hipLaunchKernelGGL(dev::k_prepare_points, dim3((n + 255) / 256), dim3(256), 0, st, n, a.guided, C, d_pos, d_normal, d_min, d_max,
+    hipLaunchKernelGGL(dev::k_prepare_points, dim3((n + 255) / 256), dim3(256), 0, st, n,
+                       a.fuse ? (int)MODE_FUSE : a.guided ? (int)MODE_GUIDED : (int)MODE_PROJECTION, C, d_pos, d_normal, d_min, d_max,
                        d_has, d_oct1, window15, (int)grid.n_scales, d_scale, log_scale1, po);
     const double ms_setup = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();
     // the rounds: round r reads claim[(r - 1) & 1] and writes claim[r & 1]; one flag read each
     int rounds = 0, round_trips = 0, changed = 1;
+    if (a.fuse) {
+        // every slot is free and stays free: one round is the result, read back with the results
+        hipMemsetAsync(d_changed, 0, sizeof(int), st);
+        hipMemcpyAsync(d_claim[1], d_base, 4 * N2, hipMemcpyDeviceToDevice, st);
+        hipLaunchKernelGGL(dev::k_match_round, dim3((n + 3) / 4), dim3(256), 0, st, n, d_x, d_y, d_radius, d_octave, d_desc, d_uv2,
+                           d_oct2, d_desc2, G, d_start, d_keys, a.th, d_claim[0], d_claim[1], d_match, d_best, d_second, d_status,
+                           d_changed);
+        rounds = 1;
+        changed = 0;
+    }
     while (changed && rounds <= n) {
         int *prev = d_claim[rounds & 1], *next = d_claim[(rounds + 1) & 1];
         hipMemsetAsync(d_changed, 0, sizeof(int), st);
@@ -545,7 +572,7 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
     round_trips++;
     if (a.uv)
         for (size_t i = 0; i < N; i++) { a.uv[2 * i] = x[i]; a.uv[2 * i + 1] = y[i]; }
-    for (size_t j = 0; j < N2; j++) a.slot_point[j] = slot_in[j] != -1 ? slot_in[j] : (claim[j] == INT_MAX ? -1 : claim[j]);
+    for (size_t j = 0; a.slot_point && j < N2; j++) a.slot_point[j] = slot_in[j] != -1 ? slot_in[j] : (claim[j] == INT_MAX ? -1 : claim[j]);
     fill_report(a, rounds, round_trips, ms_setup, ms_rounds, ms_since(t0));
     return 0;
 }

@@ -41,6 +41,7 @@
 #include "exit_guard.h"
 #include "symbolic.h"
 #include "triangulate.h"
+#include "triangulation_matching.h"
 
 using namespace deftri;
 
@@ -1510,6 +1511,7 @@ int64_t deftri_sizeof(int32_t which) {
         case 18: return (int64_t)sizeof(deftri_orb_report);
         case 20: return (int64_t)sizeof(deftri_projection_report);
         case 22: return (int64_t)sizeof(deftri_essential_report);
+        case 23: return (int64_t)sizeof(deftri_triangulation_match_report);
         default: return -1;
     }
 }
@@ -2187,6 +2189,44 @@ int deftri_map_point_descriptors(deftri_ctx *ctx, int32_t n, const float *pos, c
     const int rc = map_point_descriptors(ctx->device, ctx->st, n, pos, obs_start, obs_kf, obs_slot, n_kf, kf_Tcw, kf_slot_start,
                                          kf_desc, kf_octave, n_scales, scale_factor, normal, max_dist, min_dist, desc, ref_obs, status,
                                          err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+// ---- searchForTriangulation (triangulation_matching.hip) and the search of fuse (projection_matching.hip) ----
+int deftri_search_for_triangulation(deftri_ctx *ctx, int32_t n1, const float *uv1, const uint8_t *desc1, const uint8_t *has_point1,
+                                    int32_t n2, const float *uv2, const uint8_t *desc2, const uint8_t *has_point2, const float *kb8,
+                                    const float *E, int32_t th, float epipolar_th, int32_t flag_quirk, int32_t *matches,
+                                    int32_t *best_dist, uint8_t *status, int32_t *n_matches,
+                                    deftri_triangulation_match_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!kb8 || !E || !n_matches || n1 < 0 || n2 < 0 || (n1 > 0 && (!uv1 || !desc1 || !has_point1 || !matches || !status)) ||
+        (n2 > 0 && (!uv2 || !desc2 || !has_point2)))
+        return fail(ctx, DEFTRI_E_ARG, "search_for_triangulation: null array or negative size");
+    TriangulationMatchArgs a{};
+    a.n1 = n1; a.uv1 = uv1; a.desc1 = desc1; a.has_point1 = has_point1;
+    a.n2 = n2; a.uv2 = uv2; a.desc2 = desc2; a.has_point2 = has_point2;
+    a.kb8 = kb8; a.E = E; a.th = th; a.epipolar_th = epipolar_th; a.flag_quirk = flag_quirk;
+    a.matches = matches; a.best_dist = best_dist; a.status = status; a.n_matches = n_matches; a.report = report;
+    std::string err;
+    const int rc = search_for_triangulation(ctx->device, ctx->st, a, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_fuse_search(deftri_ctx *ctx, const deftri_feature_grid *grid, const float *Tcw, const float *kb8, int32_t n2,
+                       const float *uv2, const int32_t *octave2, const uint8_t *desc2, int32_t n, const uint8_t *consider,
+                       const float *pos, const int32_t *octave, const uint8_t *desc, int32_t th, int32_t *match, uint8_t *status,
+                       float *uv, int32_t *best, int32_t *second, deftri_projection_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!grid || !Tcw || !kb8 || n < 0 || n2 < 0 || (n2 > 0 && (!uv2 || !octave2 || !desc2)) ||
+        (n > 0 && (!consider || !pos || !octave || !desc || !match || !status)))
+        return fail(ctx, DEFTRI_E_ARG, "fuse_search: null array or negative size");
+    ProjectionMatchArgs a{};
+    a.guided = true; a.fuse = true; a.grid = grid; a.Tcw = Tcw; a.kb8 = kb8;
+    a.n2 = n2; a.uv2 = uv2; a.octave2 = octave2; a.desc2 = desc2; a.slot_point = nullptr;
+    a.n = n; a.pos = pos; a.desc = desc; a.th = th; a.has_point = consider; a.octave1 = octave;
+    a.match = match; a.status = status; a.uv = uv; a.best = best; a.second = second; a.report = report;
+    std::string err;
+    const int rc = projection_match(ctx->device, ctx->st, a, err);
     return rc ? fail(ctx, rc, err) : 0;
 }
 

@@ -226,6 +226,16 @@ class EssentialReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class TriangulationMatchReport(C.Structure):
+    _fields_ = [("n1", i32), ("n2", i32), ("n_matches", i32), ("n_occupied", i32), ("n_unmatched", i32), ("n_stolen", i32),
+                ("n_flag_skipped", i32), ("flag_row", i32), ("n_listed", i64), ("round_trips", i32), ("reserved", i32),
+                ("ms_device", f64), ("ms_loop", f64), ("ms_total", f64)]
+
+    def as_dict(self):
+        """The counters; n_listed and round_trips describe the device's work, the times (ms_*) are measurements."""
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

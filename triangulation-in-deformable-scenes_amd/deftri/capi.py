@@ -98,6 +98,14 @@ def load():
                                                    C.c_int32, P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32,
                                                    C.c_float, P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint8),
                                                    P(C.c_int32), P(C.c_uint8)]),
+        "deftri_search_for_triangulation": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_uint8), P(C.c_uint8), C.c_int32,
+                                                      P(C.c_float), P(C.c_uint8), P(C.c_uint8), P(C.c_float), P(C.c_float),
+                                                      C.c_int32, C.c_float, C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_uint8),
+                                                      P(C.c_int32), P(_abi.TriangulationMatchReport)]),
+        "deftri_fuse_search": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32, P(C.c_float),
+                                         P(C.c_int32), P(C.c_uint8), C.c_int32, P(C.c_uint8), P(C.c_float), P(C.c_int32),
+                                         P(C.c_uint8), C.c_int32, P(C.c_int32), P(C.c_uint8), P(C.c_float), P(C.c_int32),
+                                         P(C.c_int32), P(_abi.ProjectionReport)]),
         "deftri_fast_extract": (C.c_int, [C.c_void_p, P(C.c_uint8), C.c_int32, C.c_int32, C.c_int32, P(C.c_uint8), C.c_int32,
                                           C.c_int32, C.c_int32, P(_abi.FastParams), P(C.c_float), P(C.c_int32), P(C.c_float),
                                           P(C.c_float), P(C.c_float), P(C.c_int32), P(_abi.FastReport)]),
@@ -213,6 +221,7 @@ EXPORTED = [
     "deftri_match_for_initialization", "deftri_epipolar_inliers", "deftri_debug_feature_grid_cells",
     "deftri_search_with_projection", "deftri_guided_matching", "deftri_map_point_descriptors",
     "deftri_find_essential_ransac", "deftri_reconstruct_cameras",
+    "deftri_search_for_triangulation", "deftri_fuse_search",
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
 ]
@@ -296,6 +305,16 @@ class ProjectionMatchResult:
     def __init__(self, match, status, uv, best, second, slot_point, report, view_cos=None, predicted_octave=None):
         self.match, self.status, self.uv, self.best, self.second = match, status, uv, best, second
         self.slot_point, self.report, self.view_cos, self.predicted_octave = slot_point, report, view_cos, predicted_octave
+
+
+class TriangulationMatchResult:
+    """The result of Context.search_for_triangulation: matches int32 [n1] (the keypoint of keyframe 2 or -1), best_dist
+    int32 [n1] (255 where the row was never accepted), status uint8 [n1] (0 matched, 1 slot occupied, 2 no eligible
+    candidate below th, 3 matched and then robbed by a later row, 4 passed over by the flag quirk), n_matches (the
+    reference's return value) and report (deftri_triangulation_match_report as a dict)."""
+
+    def __init__(self, matches, best_dist, status, n_matches, report):
+        self.matches, self.best_dist, self.status, self.n_matches, self.report = matches, best_dist, status, n_matches, report
 
 
 class EssentialResult:
@@ -832,6 +851,47 @@ class Context:
                                                     n1, _u8p(has), _fp(pos), _ip(o1), _u8p(d), int(th), int(window_size_factor),
                                                     _ip(match), _u8p(status), _fp(uv), _ip(best), _ip(second), C.byref(rep)))
         return ProjectionMatchResult(match, status, uv, best, second, slot, rep.as_dict())
+
+    def search_for_triangulation(self, uv1, desc1, has_point1, uv2, desc2, has_point2, kb8, E, th, epipolar_th, flag_quirk=True):
+        """searchForTriangulation (DescriptorMatching.cc:255-328) on this context (deftri_search_for_triangulation): the
+        ray and candidate kernels plus the loop over the candidate lists on the device, the loop over all pairs on a
+        host-only one.  has_point1 / has_point2 bool [n]: the slot already holds a map point.  flag_quirk: keep the
+        reference's vbMatched2[2] (deftri.h).  Returns a TriangulationMatchResult."""
+        uv1, uv2 = _f32(uv1).reshape(-1, 2), _f32(uv2).reshape(-1, 2)
+        d1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32); d2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        h1 = np.ascontiguousarray(has_point1, np.uint8).reshape(-1); h2 = np.ascontiguousarray(has_point2, np.uint8).reshape(-1)
+        n1, n2 = len(uv1), len(uv2)
+        if not (len(d1) == len(h1) == n1 and len(d2) == len(h2) == n2):
+            raise ValueError("search_for_triangulation: array lengths differ")
+        k = _f32(kb8).reshape(8); E = _f32(E).reshape(3, 3)
+        matches = np.full(n1, -1, np.int32); best = np.full(n1, 255, np.int32); status = np.zeros(n1, np.uint8)
+        n_matches = C.c_int32(0)
+        rep = _abi.TriangulationMatchReport()
+        self._check(self.lib.deftri_search_for_triangulation(self.h, n1, _fp(uv1), _u8p(d1), _u8p(h1), n2, _fp(uv2), _u8p(d2),
+                                                             _u8p(h2), _fp(k), _fp(E), int(th), float(epipolar_th),
+                                                             1 if flag_quirk else 0, _ip(matches), _ip(best), _u8p(status),
+                                                             C.byref(n_matches), C.byref(rep)))
+        return TriangulationMatchResult(matches, best, status, int(n_matches.value), rep.as_dict())
+
+    def fuse_search(self, grid, Tcw, kb8, uv2, octave2, desc2, consider, pos, octave, desc, th):
+        """The search of fuse (DescriptorMatching.cc:330-428) for a list of map points against a keyframe on this context
+        (deftri_fuse_search).  Per point: consider bool [n], pos [n, 3], octave [n], desc uint8 [n, 32].  Returns a
+        ProjectionMatchResult without slot_point: the map edits are the caller's (matching.fuse)."""
+        T, k, uv2, o2, d2 = self._frame_arrays(Tcw, kb8, uv2, octave2, desc2)
+        con = np.ascontiguousarray(consider, np.uint8).reshape(-1)
+        pos = _f32(pos).reshape(-1, 3); o1 = _i32(octave)
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n, n2 = len(con), len(uv2)
+        if not (len(pos) == len(o1) == len(d) == n):
+            raise ValueError("fuse_search: array lengths differ")
+        g = self._feature_grid(grid)
+        match = np.full(n, -1, np.int32); status = np.where(con != 0, 0, 6).astype(np.uint8); uv = np.zeros((n, 2), np.float32)
+        best = np.full(n, 255, np.int32); second = np.full(n, 255, np.int32)
+        rep = _abi.ProjectionReport()
+        self._check(self.lib.deftri_fuse_search(self.h, C.byref(g), _fp(T), _fp(k), n2, _fp(uv2), _ip(o2), _u8p(d2), n, _u8p(con),
+                                                _fp(pos), _ip(o1), _u8p(d), int(th), _ip(match), _u8p(status), _fp(uv), _ip(best),
+                                                _ip(second), C.byref(rep)))
+        return ProjectionMatchResult(match, status, uv, best, second, None, rep.as_dict())
 
     def map_point_descriptors(self, pos, obs_start, obs_kf, obs_slot, kf_Tcw, kf_slot_start, kf_desc, kf_octave, n_scales,
                               scale_factor):

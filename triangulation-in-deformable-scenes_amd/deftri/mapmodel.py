@@ -5,7 +5,8 @@ solver reads and writes (SURVEY §8b "Ownership"):
   KeyFrame  : id, pose T_cw (SE3f), KB8 calibration, keypoints + octaves, per-index simulated
               depth, invSigma2 table, estimatedDepthScale_, MapPoint slots (KeyFrame.cc:93-210)
   Map       : keyframes (unordered_map<ID,KF>), map points, observations
-              (Map::addObservation / isMapPointInKeyFrame, Map.cc:100-132, 257-264),
+              (Map::addObservation / isMapPointInKeyFrame, Map.cc:100-132, 257-264; removeMapPoint and
+              fuseMapPoints, :71-84, :211-237, which matching.fuse edits the map with),
               global KF-pair transformations (Map.cc:323-330)
 
 Iteration order of the reference's `std::unordered_map<ID, KeyFrame_>` (libstdc++, integer
@@ -192,6 +193,41 @@ class Map:
         for cov in self.mp_obs[mp_id]:
             self.covis[kf_id][cov] -= 1
             self.covis[cov][kf_id] -= 1
+
+    def _observation_order(self, mp_id):
+        """The (keyframe id, slot) pairs of a map point in the order the reference iterates mMapPointObs_[mp] — or a
+        copy of it: a libstdc++ unordered_map copy iterates like its source — which is
+        deftri_keyframe_order of the keyframe ids in the order the observations were added."""
+        from .capi import keyframe_order
+        obs = self.mp_obs.get(mp_id, {})
+        return [(int(k), obs[int(k)]) for k in keyframe_order(list(obs.keys()))] if obs else []
+
+    def remove_map_point(self, mp_id):
+        """Map::removeMapPoint (Map.cc:71-84): every observation removed (the covisibility counts with it), the
+        keyframes' slots cleared, the point erased."""
+        for kf_id, idx in self._observation_order(mp_id):
+            self.remove_observation(kf_id, mp_id)
+            self.keyframes[kf_id].map_points[idx] = None
+        self.map_points.pop(mp_id, None)
+        self.mp_obs.pop(mp_id, None)
+
+    def fuse_map_points(self, mp1, mp2):
+        """Map::fuseMapPoints (Map.cc:211-237): the point with strictly more observations is kept, otherwise mp2; the
+        other's observations move to it, in the reference's iteration order, except in a keyframe that already
+        sees the kept point, whose slot of the deleted point is only cleared; then the other point is removed.
+        Unlike Map::addObservation this does not update the kept point's descriptor (as add_observation does not):
+        Map.update_orientation_and_descriptor does.  Returns the id of the kept point."""
+        n1, n2 = len(self.mp_obs.get(mp1, {})), len(self.mp_obs.get(mp2, {}))
+        keep, delete = (mp1, mp2) if n1 > n2 else (mp2, mp1)
+        kept = self.map_points[keep]
+        for kf_id, idx in self._observation_order(delete):
+            self.remove_observation(kf_id, delete)
+            self.keyframes[kf_id].map_points[idx] = None
+            if self.is_map_point_in_keyframe(keep, kf_id) == -1:
+                self.add_observation(kf_id, keep, idx)
+                self.keyframes[kf_id].map_points[idx] = kept
+        self.remove_map_point(delete)
+        return keep
 
     def get_local_map_of_keyframe(self, kf_id):
         """Map::getLocalMapOfKeyFrame (Map.cc:178-209): (local map point ids, local KF ids, fixed KF

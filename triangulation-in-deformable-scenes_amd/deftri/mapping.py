@@ -25,8 +25,8 @@ the map construction with the initial depth scales (Mapping.cc:171-254).
 
 To monocular_map_initialization and _from_features the poses are inputs, as they are to the reference's RANSAC,
 which builds E from them in every iteration (MonocularMapInitializer.cc:160-163); reconstruct_environment
-estimates E from the samples (computeE) and the second pose from it (reconstructCameras).  Still out of scope:
-the matchers the reference never calls (searchForTriangulation, fuse).  Two quirks of the reference are kept as they stand: the current keyframe's
+estimates E from the samples (computeE) and the second pose from it (reconstructCameras).  The two matchers the
+reference never calls (searchForTriangulation, fuse) are matching.search_for_triangulation and matching.fuse.  Two quirks of the reference are kept as they stand: the current keyframe's
 MapPoint goes into slot i, the reference keyframe's index, not vMatches[i] (Mapping.cc:208-209), and
 the parallax angle in DEGREES is compared with Triangulation.minCos (:220, and the acceptance test of
 reconstructPoints, which receives minCos as fMinParallax, :60).

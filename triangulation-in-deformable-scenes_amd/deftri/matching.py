@@ -20,9 +20,16 @@ for the library's entries; written from the reference, not from the library's ho
                                   Map::updateOrientationAndDescriptor (Map.cc:270-321), fp32 or fp64
   guided_matching(ctx, ...) / search_with_projection(ctx, ...)
                                   the two matchers on a context, setting the frame's map point slots
+  search_for_triangulation_ref / fuse_search_ref
+                                  searchForTriangulation (DescriptorMatching.cc:255-328) and the search inside fuse
+                                  (:361-406), fp32 or fp64
+  search_for_triangulation(ctx, kf1, kf2, ...) / fuse(ctx, map, kf, ...)
+                                  the two on a context: matches between two KeyFrames' free keypoints, and a list of
+                                  map points fused into a KeyFrame (Map.fuse_map_points / add_observation)
 
 The device versions are capi.Context.match_for_initialization, .epipolar_inliers, .find_essential_ransac,
-.reconstruct_cameras, .search_with_projection, .guided_matching and .map_point_descriptors.  Quirks kept as they
+.reconstruct_cameras, .search_with_projection, .guided_matching, .map_point_descriptors, .search_for_triangulation
+and .fuse_search.  Quirks kept as they
 stand: posInGrid rounds half away from zero to a cell index, so a keypoint in the last half cell on the right
 or at the bottom is in no cell and never a candidate; only reference keypoints of octave <= 0 are searched;
 best and second start at 255; a tie for best rejects; the matches are not one-to-one; the RANSAC scores the
@@ -588,3 +595,189 @@ def search_with_projection(ctx, cur_frame, grid, th, map_points):
         if i >= 0:
             cur_frame.map_points[j] = map_points[i]
     return res.match, res.report
+
+
+# ---- growing the map past two keyframes: searchForTriangulation and fuse ---------------------------------------
+# status of a row of searchForTriangulation (deftri.h): 0 matched, 1 its slot holds a map point, 2 no eligible
+# candidate below th, 3 matched and then robbed by a later row, 4 passed over by the vbMatched2[2] quirk
+TRI_MATCHED, TRI_OCCUPIED, TRI_NONE, TRI_STOLEN, TRI_FLAG = range(5)
+
+
+def triangulation_rays(kb8, E, uv1, uv2, dtype=np.float32):
+    """ray1 = (E * unproject(uv1)).normalized() (DescriptorMatching.cc:282; the unprojected ray is not normalized first)
+    and ray2 = unproject(uv2).normalized() (:300), both with the one calibration (:267), in `dtype`."""
+    from .mapping import _kb8_unproject
+    dt = np.dtype(dtype)
+    E = np.asarray(E, F).reshape(3, 3).astype(dt)
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        a = _kb8_unproject(kb8, np.asarray(uv1, F).reshape(-1, 2), dt).astype(dt)
+        b = _kb8_unproject(kb8, np.asarray(uv2, F).reshape(-1, 2), dt).astype(dt)
+        Ea = np.stack([(E[r, 0] * a[:, 0] + E[r, 1] * a[:, 1]) + E[r, 2] * a[:, 2] for r in range(3)], 1).astype(dt)
+        return _eigen_normalized(Ea).astype(dt), _eigen_normalized(b).astype(dt)
+
+
+def triangulation_epipolar_errors(ray1, ray2, dtype=np.float32):
+    """float err = fabs(M_PI/2 - acos(ray2.dot(ray1))) (:303) for every pair [n1, n2]: in float32 the dot product and
+    acos are float, the difference and fabs double, the result rounded to float; in float64 everything is double."""
+    dt = np.dtype(dtype)
+    with np.errstate(invalid="ignore"):
+        d = ((ray2[None, :, 0] * ray1[:, None, 0] + ray2[None, :, 1] * ray1[:, None, 1]) + ray2[None, :, 2] * ray1[:, None, 2]).astype(dt)
+        return np.abs(np.pi / 2 - np.arccos(d).astype(dt).astype(np.float64)).astype(dt)
+
+
+def search_for_triangulation_ref(uv1, desc1, has_point1, uv2, desc2, has_point2, kb8, E, th, epipolar_th, flag_quirk=True,
+                                 dtype=np.float32):
+    """searchForTriangulation(kf1, kf2, th, fEpipolarTh, E, vMatches) (DescriptorMatching.cc:255-328), the sequential
+    loop, the float arithmetic in `dtype`.  vMatchedDistance and vnMatches21 have n2 elements (the reference sizes them
+    by n1 and indexes them by j); vbMatched2 is the one boolean it amounts to (element 2 is all that is read), ignored
+    with flag_quirk false.  Returns a dict: matches, best_dist, status, n_matches, report (the counters and flag_row),
+    and what the decisions were taken on: dist [n1, n2] and err [n1, n2]."""
+    if th > 255:
+        raise ValueError("search_for_triangulation: th > 255: the reference would use an uninitialised bestIdx")
+    dt = np.dtype(dtype)
+    desc1 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32); desc2 = np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+    has1 = np.asarray(has_point1).reshape(-1).astype(bool); has2 = np.asarray(has_point2).reshape(-1).astype(bool)
+    n1, n2 = len(desc1), len(desc2)
+    ray1, ray2 = triangulation_rays(kb8, E, uv1, uv2, dt)
+    err = triangulation_epipolar_errors(ray1, ray2, dt)
+    bits1 = np.unpackbits(desc1, axis=1).astype(np.int32); bits2 = np.unpackbits(desc2, axis=1).astype(np.int32)
+    dist = (bits1.sum(1)[:, None] + bits2.sum(1)[None, :] - 2 * (bits1 @ bits2.T)).astype(np.int64)   # = hamming(), by bits
+    with np.errstate(invalid="ignore"):
+        passed = err < dt.type(F(epipolar_th))
+    matches = np.full(n1, -1, np.int32); best_d = np.full(n1, 255, np.int32)
+    status = np.where(has1, TRI_OCCUPIED, TRI_NONE).astype(np.uint8)
+    matched_dist = np.full(n2, np.iinfo(np.int32).max, np.int64); match21 = np.full(n2, -1, np.int64)
+    flag, flag_row, n_matches = False, -1, 0
+    for i in range(n1):
+        if has1[i]:                                          # :277
+            continue
+        if flag_quirk and flag:                              # :288: vbMatched2[2] passes every j over
+            status[i] = TRI_FLAG
+            continue
+        best, best_idx = 255, -1
+        for j in np.nonzero(~has2 & (dist[i] <= 50))[0]:     # :288, :293's first half; ascending j
+            d = int(dist[i, j])
+            if d > best:                                     # :293
+                continue
+            if matched_dist[j] <= d:                         # :296
+                continue
+            if passed[i, j]:                                 # :303-307
+                best, best_idx = d, int(j)
+        if best < th:                                        # :310
+            if match21[best_idx] >= 0:                       # :314-317
+                matches[match21[best_idx]] = -1
+                status[match21[best_idx]] = TRI_STOLEN
+                n_matches -= 1
+            matches[i], best_d[i], status[i] = best_idx, best, TRI_MATCHED
+            match21[best_idx] = i
+            if best == 2 and not flag:                       # vbMatched2[bestDist] = true
+                flag, flag_row = True, i
+            matched_dist[best_idx] = best
+            n_matches += 1
+    report = {"n1": n1, "n2": n2, "n_matches": n_matches, "n_occupied": int((status == TRI_OCCUPIED).sum()),
+              "n_unmatched": int((status == TRI_NONE).sum()), "n_stolen": int((status == TRI_STOLEN).sum()),
+              "n_flag_skipped": int((status == TRI_FLAG).sum()), "flag_row": flag_row}
+    return {"matches": matches, "best_dist": best_d, "status": status, "n_matches": n_matches, "report": report,
+            "dist": dist, "err": err}
+
+
+def fuse_search_ref(grid, Tcw, kb8, uv2, octave2, desc2, consider, pos, octave, desc, th, dtype=np.float32):
+    """The search of fuse (DescriptorMatching.cc:361-406) for every considered point, the projection in `dtype`: no
+    depth test, radius = 2.5 * getScaleFactor(octave) in double, levels octave +- 1, no slot is skipped.  Returns a
+    dict: match, status, uv, best, second, report, radius."""
+    dt = np.dtype(dtype).type
+    uv2, octave2, desc2 = _frame(uv2, octave2, desc2)
+    con = np.asarray(consider).reshape(-1).astype(bool)
+    X = np.asarray(pos, F).reshape(-1, 3).astype(dt)
+    octave = np.asarray(octave, np.int64).reshape(-1)
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+    n = len(con)
+    scale = scale_factors(grid)
+    free = np.full(len(uv2), -1, np.int32)
+    cells = build_grid(grid, uv2)
+    uv = _project_points(Tcw, kb8, X, dt)
+    uv[~con] = 0
+    out = {"match": np.full(n, -1, np.int32), "status": np.where(con, 0, EMPTY_SLOT).astype(np.uint8), "uv": uv,
+           "best": np.full(n, 255, np.int32), "second": np.full(n, 255, np.int32), "radius": np.zeros(n, dt)}
+    for i in np.nonzero(con)[0]:
+        if not np.all(np.isfinite(uv[i])):
+            out["status"][i] = UNDEFINED
+            continue
+        o = int(octave[i])
+        radius = F(2.5 * float(scale[o]))                                           # :369
+        out["radius"][i] = radius
+        out["match"][i], out["status"][i], out["best"][i], out["second"][i] = _window_search(
+            grid, cells, uv2, octave2, desc2, free.copy(), int(i), uv[i, 0], uv[i, 1], radius, o, desc[i], th)
+    out["report"] = _report(out["status"])
+    return out
+
+
+def search_for_triangulation(ctx, kf1, kf2, th, epipolar_th, E=None, flag_quirk=True):
+    """searchForTriangulation(kf1, kf2, th, fEpipolarTh, E, vMatches) on `ctx` (Context.search_for_triangulation) for two
+    KeyFrames: the keypoints whose slot holds no map point are matched, with kf1's calibration for both (:267).  E
+    defaults to essential_from_poses(kf1.pose, kf2.pose), the convention computeScoreAndInliers uses.  flag_quirk
+    True is the reference as it stands: after a row accepted at distance exactly 2 no row matches (deftri.h).  Edits
+    nothing.  Returns (matches int32 [kf1's slots], report)."""
+    for kf in (kf1, kf2):
+        if getattr(kf, "descriptors", None) is None:
+            raise ValueError(f"search_for_triangulation: keyframe {kf.id} has no descriptors")
+    if E is None:
+        E = essential_from_poses(kf1.pose, kf2.pose)
+    has1 = np.array([mp is not None for mp in kf1.map_points], bool)
+    has2 = np.array([mp is not None for mp in kf2.map_points], bool)
+    res = ctx.search_for_triangulation(kf1.keypoints, kf1.descriptors, has1, kf2.keypoints, kf2.descriptors, has2, kf1.kb8, E,
+                                       th, epipolar_th, flag_quirk)
+    return res.matches, res.report
+
+
+def fuse(ctx, m, kf, th, map_points, grid):
+    """fuse(pKF, th, vMapPoints, pMap) (DescriptorMatching.cc:330-428) on `ctx`: one search for all the points that are
+    not None (Context.fuse_search; inside fuse a point's search does not depend on earlier iterations), then the
+    reference's loop on the host with its three skips evaluated at that moment — the point is null, it has no
+    observation (for instance an earlier fusion deleted it), it is already in kf — and for an accepted point
+    Map.fuse_map_points with the map point in the matched slot, or Map.add_observation and the slot.  The kept quirk
+    of :366: point i is searched at the octave of kf's keypoint i, the list index used as a keypoint index, so a
+    list longer than kf's slots raises ValueError.  The descriptors Map::addObservation would refresh per edit are
+    refreshed once at the end for the surviving touched points (Map.update_orientation_and_descriptor): a point
+    whose descriptor an earlier iteration changed is by then in kf or gone and is skipped, and the final descriptor
+    depends only on the final observations and their order.  Returns (n_fused, report)."""
+    frame = _frame_of(kf, "fuse")
+    map_points = list(map_points)
+    n = len(map_points)
+    if n > kf.n_slots:
+        raise ValueError(f"fuse: {n} map points but keyframe {kf.id} has {kf.n_slots} keypoints: the reference reads "
+                         "getKeyPoint(i) of the list index (DescriptorMatching.cc:366)")
+    consider = np.array([mp is not None for mp in map_points], bool)
+    pos = np.zeros((n, 3), F); desc = np.zeros((n, 32), np.uint8)
+    for i, mp in enumerate(map_points):
+        if mp is None:
+            continue
+        if getattr(mp, "descriptor", None) is None:
+            raise ValueError(f"fuse: map point {mp.id} has no descriptor (Map.update_orientation_and_descriptor)")
+        pos[i], desc[i] = mp.position, mp.descriptor
+    res = ctx.fuse_search(grid, *frame, consider, pos, np.asarray(kf.octaves, np.int32)[:n], desc, th)
+    n_fused, touched = 0, {}
+    for i, mp in enumerate(map_points):
+        if mp is None:                                                              # :347
+            continue
+        if len(m.mp_obs.get(mp.id, {})) == 0:                                       # :350
+            continue
+        if m.is_map_point_in_keyframe(mp.id, kf.id) != -1:                          # :353
+            continue
+        if res.status[i] != MATCHED:
+            continue
+        j = int(res.match[i])
+        other = kf.map_points[j]
+        if other is not None:                                                       # :411-413
+            touched[m.fuse_map_points(mp.id, other.id)] = True
+        else:                                                                       # :416-419
+            kf.map_points[j] = mp
+            m.add_observation(kf.id, mp.id, j)
+            touched[mp.id] = True
+        n_fused += 1
+    alive = [pid for pid in touched if pid in m.map_points and m.mp_obs.get(pid)]
+    if alive:
+        m.update_orientation_and_descriptor(ctx, alive, grid)
+    report = dict(res.report)
+    report["n_fused"] = n_fused
+    return n_fused, report

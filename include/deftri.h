@@ -777,6 +777,68 @@ int deftri_reconstruct_cameras(deftri_ctx *ctx, int32_t n, const float *uv1, con
 int deftri_debug_feature_grid_cells(deftri_ctx *ctx, const deftri_feature_grid *grid, int32_t n, const float *uv,
         int32_t *cell_start, int32_t *cell_keys);
 
+/* ---- the frame the matchers read: undistorted keys, grid bounds and cell lists ------------------- */
+/* cv::undistortPoints(src, dst, K, dist, R = empty, P = K) with its default termination (5 iterations,
+   count only), as Frame::undistortKeys calls it (Frame.cc:252-275), for n points: uv_in / uv_out [2 * n]
+   pixels, calib [4] = fx, fy, cx, cy (calibration_->getParameter(0..3)), dist [n_dist] = k1, k2, p1, p2
+   [, k3] (Camera.k1, k2, p1, p2, k3; n_dist 4 or 5, k3 = 0 with 4).  OpenCV's function is restated from
+   its definition and has not been run against an OpenCV build.  Per point, in double from the floats,
+   one rounding per operation (no contraction), on host and device:
+       ifx = 1.0 / fx;  ify = 1.0 / fy;  x0 = (u - cx) * ifx;  y0 = (v - cy) * ify;  x = x0;  y = y0
+       5 times:  r2 = x*x + y*y;  icdist = 1.0 / (1 + ((k3*r2 + k2)*r2 + k1)*r2)
+                 if icdist < 0:  x = x0; y = y0; stop
+                 dX = 2*p1*x*y + p2*(r2 + 2*x*x);  dY = p1*(r2 + 2*y*y) + 2*p2*x*y
+                 x = (x0 - dX) * icdist;  y = (y0 - dY) * icdist
+       out = (float(x*fx + cx), float(y*fy + cy))
+   Kept as it stands: 5 iterations whether or not they have converged; double inside, float out; ifx a
+   reciprocal that is multiplied by; a negative icdist gives the point up and returns the round trip of
+   its distorted position, float(x0*fx + cx), which need not be u; all-zero coefficients still run the
+   path; a NaN propagates.  The rational (k4..k6), thin-prism and tilt terms are absent: the reference
+   never passes more than 5 coefficients.  The device runs one thread per point with one upload and one
+   blocking download; a host-only context runs the sequential loop; the two are equal bit for bit.  n == 0
+   writes nothing.  uv_in == uv_out is allowed (the reference calls it in place).
+   DEFTRI_E_ARG with a message: a null required pointer, n < 0, n_dist not 4 or 5, fx or fy zero or not
+   finite (the reference would divide by it). */
+int deftri_undistort_points(deftri_ctx *ctx, int32_t n, const float *uv_in, const float *calib /* [4] */,
+        const float *dist, int32_t n_dist, float *uv_out);
+
+/* Frame::computeImageBoundaries (Frame.cc:221-250): bounds [4] = minCol_, minRow_, maxCol_, maxRow_.
+   n_dist == 0 (no Camera.k1): 0, 0, cols, rows, and calib / dist may be NULL.  Otherwise the corners
+   (0, 0), (cols, 0), (0, rows), (cols, rows) as float go through deftri_undistort_points' function to o0..o3
+   and min_col = min(o0.x, o2.x), min_row = min(o0.y, o1.y), max_col = max(o1.x, o3.x), max_row = max(o2.y,
+   o3.y).  Four points: computed on the host on every context.  DEFTRI_E_ARG with a message: a null
+   required pointer, n_dist not 0, 4 or 5, fx or fy zero or not finite while n_dist > 0, max <= min after
+   undistortion (also a bound that is not a number). */
+int deftri_image_bounds(deftri_ctx *ctx, int32_t cols, int32_t rows, const float *calib, const float *dist,
+        int32_t n_dist, float *bounds /* [4] */);
+
+/* What Frame's constructor and Frame::distributeFeatures (Frame.cc:46-50, :188-211) make of the n keypoint
+   slots FAST::extract filled, in one call:
+     1. *grid: the bounds of deftri_image_bounds for (cols, rows) = (Camera.cols, Camera.rows) with grid_cols,
+        grid_rows (FeatureGrid.nGridCols / nGridRows), n_scales and scale_factor as given: what every
+        matcher takes; the two inverse cell sizes follow from it in float as initializeGrid computes them;
+     2. uv [2 * n]: Frame::undistortKeys of uv_dis [2 * n] (deftri_undistort_points), or a copy of it when
+        n_dist == 0.  Every slot is undistorted, also the zeros behind the extracted keypoints of a frame
+        with nFeatures slots, as the reference's loop over all of vKeysDis_ does.  uv == uv_dis is allowed;
+     3. grid_[col][row] as a CSR: cell_start [grid_cols * grid_rows + 1], cell (col, row) holding the
+        keypoint indices cell_items[cell_start[col * grid_rows + row] .. cell_start[col * grid_rows + row + 1])
+        in keypoint order, as push_back leaves them; cell_items [n], -1 behind the last list; in_grid [n]
+        (may be NULL) 1 where the slot's own posInGrid is true.  A slot is stored only there: the rounding
+        and the last-half-cell behaviour are those of deftri_match_for_initialization, and an undistorted
+        position that rounds to column or row -1, or is NaN, is in no cell.
+   The device undistorts a slot, finds its cell and counts the cell in one launch, then builds the lists
+   with the kernels the matchers build theirs with and puts each list into keypoint order; the keys do
+   not travel to the host in between; one upload and one blocking download.  A host-only context runs the
+   sequential loops; every output is equal bit for bit.  n == 0 writes *grid and a cell_start of zeros.
+   DEFTRI_E_ARG with a message, every output untouched: a null required pointer, n < 0, n_dist not 0, 4
+   or 5, fx or fy zero or not finite while n_dist > 0, grid_cols or grid_rows <= 0 or more than 2^24 cells,
+   max <= min after undistortion, n_scales < 1. */
+int deftri_distribute_features(deftri_ctx *ctx, int32_t grid_cols, int32_t grid_rows, int32_t n_scales,
+        float scale_factor, int32_t cols, int32_t rows, const float *calib, const float *dist, int32_t n_dist,
+        int32_t n, const float *uv_dis, float *uv /* out */, deftri_feature_grid *grid /* out */,
+        int32_t *cell_start /* out, grid_cols * grid_rows + 1 */, int32_t *cell_items /* out, n */,
+        uint8_t *in_grid /* out, n, may be NULL */);
+
 /* ---- map points into a frame by projection: what poseOnlyOptimization's frame is filled by -------- */
 typedef struct deftri_projection_report {
     int32_t n_points;                    /* points (searchWithProjection) or reference slots (guidedMatching) */

@@ -8,6 +8,7 @@
 // candidates are visited in does not change them, and an accepted best is strictly below the second:
 // its index is unique.  The device therefore reduces in any order and equals the sequential loop.
 //   k_grid_cells / k_grid_scan / k_grid_fill   the current frame's cell lists as a CSR
+//   k_grid_order                               the lists in keypoint order (undistort.hip's distributeFeatures)
 //   k_match_init                               one 64-lane wave per reference keypoint
 //   k_count_matches                            nMatches
 // posInGrid rounds to the nearest cell index, so a keypoint in the last half cell of the image gets
@@ -76,6 +77,20 @@ __global__ void k_grid_fill(int n, const int *__restrict__ cell, int *__restrict
     if (i >= n) return;
     const int id = cell[i];
     if (id >= 0) keys[atomicAdd(&cursor[id], 1)] = i;
+}
+
+// the filled lists put into keypoint order, as the reference's push_back leaves them: keypoint i goes to the
+// place in its cell's run given by how many of the run's keys are below it.  `keys` is read, `ordered` written.
+__global__ void k_grid_order(int n, const int *__restrict__ cell, const int *__restrict__ start, const int *__restrict__ keys,
+                             int *__restrict__ ordered) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const int id = cell[i];
+    if (id < 0) return;
+    const int k0 = start[id], k1 = start[id + 1];
+    int below = 0;
+    for (int k = k0; k < k1; k++) below += keys[k] < i ? 1 : 0;
+    ordered[k0 + below] = i;
 }
 
 // One wave per reference keypoint (4 per workgroup).  `radius`: windowSizeFactor * 1 * getScaleFactor(0),
@@ -203,8 +218,19 @@ void launch_grid(const GridGeom &G, int n, const float *d_uv, int *d_cell, int *
     const int ncell = G.cols * G.rows;
     hipMemsetAsync(d_count, 0, sizeof(int) * (size_t)ncell, st);
     hipLaunchKernelGGL(dev::k_grid_cells, dim3((n + 255) / 256), dim3(256), 0, st, n, d_uv, G, d_cell, d_count);
+    launch_grid_lists(ncell, n, d_cell, d_count, d_start, d_cursor, d_keys, st);
+}
+
+// the lists from every keypoint's cell and the cells' sizes: the scan and the fill
+void launch_grid_lists(int ncell, int n, const int *d_cell, const int *d_count, int *d_start, int *d_cursor, int *d_keys,
+                       hipStream_t st) {
     hipLaunchKernelGGL(dev::k_grid_scan, dim3(1), dim3(256), 0, st, ncell, d_count, d_start, d_cursor);
     hipLaunchKernelGGL(dev::k_grid_fill, dim3((n + 255) / 256), dim3(256), 0, st, n, d_cell, d_cursor, d_keys);
+}
+
+// d_keys' runs in keypoint order into d_ordered [n]
+void launch_grid_order(int n, const int *d_cell, const int *d_start, const int *d_keys, int *d_ordered, hipStream_t st) {
+    hipLaunchKernelGGL(dev::k_grid_order, dim3((n + 255) / 256), dim3(256), 0, st, n, d_cell, d_start, d_keys, d_ordered);
 }
 
 // Frame::distributeFeatures' grid (Frame.cc:204-210) on the host: grid[c * rows + r] in keypoint order

@@ -95,6 +95,11 @@ float scale_factor(const deftri_feature_grid &g, int octave);
 // [n], d_count / d_cursor [ncell], d_start [ncell + 1], d_keys [n]; ncell = cols * rows
 void launch_grid(const dev::GridGeom &G, int n, const float *d_uv, int *d_cell, int *d_count, int *d_start, int *d_cursor,
                  int *d_keys, hipStream_t st);
+// its second half for a caller that wrote d_cell and d_count (zeroed first) itself: k_grid_scan / k_grid_fill
+void launch_grid_lists(int ncell, int n, const int *d_cell, const int *d_count, int *d_start, int *d_cursor, int *d_keys,
+                       hipStream_t st);
+// d_keys' runs in keypoint order into d_ordered [n], as the reference's push_back leaves them (k_grid_order)
+void launch_grid_order(int n, const int *d_cell, const int *d_start, const int *d_keys, int *d_ordered, hipStream_t st);
 // Frame::distributeFeatures' grid (Frame.cc:204-210) on the host: grid[c * rows + r] in keypoint order
 std::vector<std::vector<int32_t>> host_grid(const dev::GridGeom &G, int32_t n, const float *uv);
 // HammingDistance (DescriptorMatching.cc:21-36) over 8 32-bit words

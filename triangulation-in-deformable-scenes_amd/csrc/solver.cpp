@@ -42,6 +42,7 @@
 #include "symbolic.h"
 #include "triangulate.h"
 #include "triangulation_matching.h"
+#include "undistort.h"
 
 using namespace deftri;
 
@@ -2227,6 +2228,40 @@ int deftri_fuse_search(deftri_ctx *ctx, const deftri_feature_grid *grid, const f
     a.match = match; a.status = status; a.uv = uv; a.best = best; a.second = second; a.report = report;
     std::string err;
     const int rc = projection_match(ctx->device, ctx->st, a, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+// ---- Frame::undistortKeys, computeImageBoundaries and distributeFeatures (undistort.hip) ----
+int deftri_undistort_points(deftri_ctx *ctx, int32_t n, const float *uv_in, const float *calib, const float *dist, int32_t n_dist,
+                            float *uv_out) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0) return fail(ctx, DEFTRI_E_ARG, "undistort_points: negative n");
+    if (!calib || !dist || (n > 0 && (!uv_in || !uv_out))) return fail(ctx, DEFTRI_E_ARG, "undistort_points: null array");
+    std::string err;
+    const int rc = undistort_points(ctx->device, ctx->st, n, uv_in, calib, dist, n_dist, uv_out, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_image_bounds(deftri_ctx *ctx, int32_t cols, int32_t rows, const float *calib, const float *dist, int32_t n_dist,
+                        float *bounds) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (!bounds || (n_dist > 0 && (!calib || !dist))) return fail(ctx, DEFTRI_E_ARG, "image_bounds: null array");
+    std::string err;
+    const int rc = image_bounds(cols, rows, calib, dist, n_dist, bounds, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_distribute_features(deftri_ctx *ctx, int32_t grid_cols, int32_t grid_rows, int32_t n_scales, float scale_factor,
+                               int32_t cols, int32_t rows, const float *calib, const float *dist, int32_t n_dist, int32_t n,
+                               const float *uv_dis, float *uv, deftri_feature_grid *grid, int32_t *cell_start, int32_t *cell_items,
+                               uint8_t *in_grid) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0) return fail(ctx, DEFTRI_E_ARG, "distribute_features: negative n");
+    if (!grid || !cell_start || (n_dist > 0 && (!calib || !dist)) || (n > 0 && (!uv_dis || !uv || !cell_items)))
+        return fail(ctx, DEFTRI_E_ARG, "distribute_features: null array");
+    std::string err;
+    const int rc = distribute_features(ctx->device, ctx->st, grid_cols, grid_rows, n_scales, scale_factor, cols, rows, calib, dist,
+                                       n_dist, n, uv_dis, uv, grid, cell_start, cell_items, in_grid, err);
     return rc ? fail(ctx, rc, err) : 0;
 }
 

@@ -85,6 +85,12 @@ def load():
                                                  P(C.c_uint8), P(C.c_float), P(C.c_float), P(C.c_int32)]),
         "deftri_debug_feature_grid_cells": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), C.c_int32, P(C.c_float), P(C.c_int32),
                                                       P(C.c_int32)]),
+        "deftri_undistort_points": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_float), P(C.c_float), P(C.c_float), C.c_int32,
+                                              P(C.c_float)]),
+        "deftri_image_bounds": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_float), P(C.c_float), C.c_int32, P(C.c_float)]),
+        "deftri_distribute_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
+                                                 P(C.c_float), P(C.c_float), C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
+                                                 P(_abi.FeatureGrid), P(C.c_int32), P(C.c_int32), P(C.c_uint8)]),
         "deftri_search_with_projection": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
                                                     P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32,
                                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint8),
@@ -224,6 +230,7 @@ EXPORTED = [
     "deftri_search_for_triangulation", "deftri_fuse_search",
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
+    "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
 ]
 
 
@@ -293,6 +300,25 @@ class OrbResult:
 
     def __len__(self):
         return len(self.status)
+
+
+class DistributedFeatures:
+    """The result of Context.distribute_features: uv float32 [n, 2] the undistorted keys (Frame::vKeys_), grid (the
+    dict of deftri_feature_grid's fields every matcher takes), cell_start int32 [cols * rows + 1] and cell_items int32
+    [n] (grid_[col][row] as a CSR over cells col * rows + row, keypoint order within a cell, -1 behind the last
+    list), in_grid bool [n]."""
+
+    def __init__(self, uv, grid, cell_start, cell_items, in_grid):
+        self.uv, self.grid, self.cell_start, self.cell_items, self.in_grid = uv, grid, cell_start, cell_items, in_grid
+
+    def __len__(self):
+        return len(self.uv)
+
+    def cells(self):
+        """grid_[col][row] as nested lists, the shape matching.build_grid returns."""
+        cols, rows = self.grid["cols"], self.grid["rows"]
+        s = self.cell_start
+        return [[self.cell_items[s[c * rows + r]:s[c * rows + r + 1]].tolist() for r in range(rows)] for c in range(cols)]
 
 
 class ProjectionMatchResult:
@@ -925,6 +951,52 @@ class Context:
         self._check(self.lib.deftri_debug_feature_grid_cells(self.h, C.byref(g), len(uv), uv.ctypes.data_as(C.POINTER(C.c_float)),
                                                              ip(start), ip(keys)))
         return start, keys[:start[-1]]
+
+    @staticmethod
+    def _camera(calib, dist):
+        """(calib float32 [4] or None, dist float32 [n_dist], n_dist) of fx, fy, cx, cy and Settings.distortion."""
+        dist = _f32(dist if dist is not None else []).reshape(-1)
+        calib = None if calib is None else _f32(calib).reshape(-1)
+        if calib is not None and len(calib) != 4:
+            raise ValueError(f"calib: fx, fy, cx, cy expected, got {len(calib)} values")
+        return calib, dist, len(dist)
+
+    def undistort_points(self, uv, calib, dist, in_place=False):
+        """cv::undistortPoints(uv, uv, K, dist, Mat(), K) as Frame::undistortKeys calls it (deftri_undistort_points):
+        uv float32 [n, 2], calib = fx, fy, cx, cy, dist = k1, k2, p1, p2[, k3].  Returns float32 [n, 2]; with
+        in_place the library reads and writes one buffer, as the reference does."""
+        uv = np.array(uv, np.float32).reshape(-1, 2) if in_place else _f32(uv).reshape(-1, 2)
+        calib, dist, n_dist = self._camera(calib, dist)
+        out = uv if in_place else np.zeros_like(uv)
+        self._check(self.lib.deftri_undistort_points(self.h, len(uv), _fp(uv), None if calib is None else _fp(calib), _fp(dist),
+                                                     n_dist, _fp(out)))
+        return out
+
+    def image_bounds(self, cols, rows, calib=None, dist=None):
+        """Frame::computeImageBoundaries (deftri_image_bounds): float32 [4] = min_col, min_row, max_col, max_row; no
+        distortion coefficients give 0, 0, cols, rows."""
+        calib, dist, n_dist = self._camera(calib, dist)
+        b = np.zeros(4, np.float32)
+        self._check(self.lib.deftri_image_bounds(self.h, int(cols), int(rows), None if calib is None else _fp(calib), _fp(dist),
+                                                 n_dist, _fp(b)))
+        return b
+
+    def distribute_features(self, grid_cols, grid_rows, n_scales, scale_factor, cols, rows, calib, dist, uv_dis):
+        """Frame's bounds and Frame::distributeFeatures for the keypoint slots uv_dis float32 [n, 2]
+        (deftri_distribute_features) on this context: the device, or the sequential host loops on a host-only one.
+        Returns a DistributedFeatures."""
+        uv_dis = _f32(uv_dis).reshape(-1, 2)
+        calib, dist, n_dist = self._camera(calib, dist)
+        n, ncell = len(uv_dis), max(int(grid_cols), 0) * max(int(grid_rows), 0)
+        uv = np.zeros_like(uv_dis); g = _abi.FeatureGrid()
+        start = np.zeros((ncell if ncell <= 1 << 24 else 0) + 1, np.int32); items = np.zeros(n, np.int32)
+        in_grid = np.zeros(n, np.uint8)
+        self._check(self.lib.deftri_distribute_features(self.h, int(grid_cols), int(grid_rows), int(n_scales), float(scale_factor),
+                                                        int(cols), int(rows), None if calib is None else _fp(calib), _fp(dist),
+                                                        n_dist, n, _fp(uv_dis), _fp(uv), C.byref(g), _ip(start), _ip(items),
+                                                        _u8p(in_grid)))
+        grid = {k: getattr(g, k) for k, _ in _abi.FeatureGrid._fields_}
+        return DistributedFeatures(uv, grid, start, items, in_grid.astype(bool))
 
     @staticmethod
     def _fast_params(params):

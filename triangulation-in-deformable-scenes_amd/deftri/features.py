@@ -1,10 +1,12 @@
-"""From an image to keypoints and their descriptors: Mapping::extractFeatures' two halves (reference
-Modules/Mapping/Mapping.cc:120-129).
+"""From an image to keypoints, their descriptors and the frame's grid: Mapping::extractFeatures' three lines
+(reference Modules/Mapping/Mapping.cc:120-129).
 
 FAST::extract (Modules/Features/FAST.cc:81-118) through deftri_fast_extract — the pyramid, cv::FAST per cell,
 distributeOctTree, the reflection / border mask and IC_Angle — and ORB::describe (Modules/Features/
 ORB.cc:20-90) through deftri_orb_describe — the blurred, bordered pyramid and the 256 rotated comparisons per
-keypoint — on the device of the context or as sequential host loops on a host-only one.
+keypoint — and Frame::distributeFeatures (Modules/Mapping/Frame.cc:188-211) through deftri_distribute_features —
+cv::undistortPoints of the keypoints under Camera.k1, k2, p1, p2[, k3] and the grid over the undistorted image
+bounds — on the device of the context or as sequential host loops on a host-only one.
 
 The settings map as Mapping's constructor passes them (Mapping.cc:46): 2 * FeatureExtractor.nFeatures wanted,
 thresholds 10 and 4, and the frame's vKeys capacity nFeatures (Frame.cc:35).  FeatureExtractor.imageBoderMask
@@ -34,12 +36,31 @@ def orb_params(settings):
 
 
 def extract(ctx, image, settings, border_mask=None):
-    """Mapping::extractFeatures' first half (Mapping.cc:120-129) for one 8-bit grey image: a capi.FastResult."""
-    if settings.has_distortion:
-        raise ValueError("Camera.k1 is set: the reference undistorts the keypoints with OpenCV, which is not restated")
+    """Mapping::extractFeatures' first half (Mapping.cc:120-129) for one 8-bit grey image: a capi.FastResult.
+    FAST runs on the distorted image whatever Camera.k1 says, as in the reference: the result's uv are distorted
+    pixels (vKeysDis_), which ORB::describe reads; distribute() undistorts them."""
     if settings.border_mask_path and border_mask is None:
         raise ValueError(f"FeatureExtractor.imageBoderMask names {settings.border_mask_path!r}: decode it and pass border_mask")
     return ctx.fast_extract(np.asarray(image), fast_params(settings), border_mask)
+
+
+def distribute(ctx, keys, settings, n_slots=None):
+    """Mapping::extractFeatures' third line, currFrame_.distributeFeatures() (Frame.cc:188-211), with the bounds
+    Frame's constructor computes (:221-250), on `ctx`: `keys` (a capi.FastResult or float32 [n, 2] distorted pixels)
+    are undistorted when Camera.k1 is set and copied when it is not, and every keypoint whose own posInGrid is true
+    goes into its grid cell.  n_slots: the frame's capacity (FeatureExtractor.nFeatures in the reference); the slots
+    behind the keypoints are zeros and are undistorted and distributed like any other, as the reference's loop over
+    all of vKeysDis_ does.  Default: the keypoints alone.  Returns a capi.DistributedFeatures: the undistorted
+    keys, the grid (what the matchers take) and the cell lists."""
+    from . import matching
+    uv = np.ascontiguousarray(keys.uv if hasattr(keys, "uv") else keys, np.float32).reshape(-1, 2)
+    if n_slots is not None:
+        if len(uv) > n_slots:
+            raise ValueError(f"{len(uv)} keypoints for {n_slots} slots")
+        uv = np.concatenate([uv, np.zeros((n_slots - len(uv), 2), np.float32)])
+    calib, dist = matching.camera_of(settings, "distribute")
+    return ctx.distribute_features(settings.grid_cols, settings.grid_rows, settings.n_scales, settings.scale_factor,
+                                   int(settings.cols), int(settings.rows), calib, dist, uv)
 
 
 def describe(ctx, image, keys, settings, pattern):

@@ -141,6 +141,9 @@ class KeyFrame:
         self.descriptors = None if descriptors is None else np.ascontiguousarray(descriptors, np.uint8).reshape(n_slots, 32)
         # cv::KeyPoint::angle of FAST::extract (degrees), float32 [n_slots]; what ORB::describe steers by
         self.angles = None if angles is None else np.ascontiguousarray(angles, np.float32).reshape(n_slots)
+        # Frame::vKeysDis_: the distorted pixels FAST::extract found, float32 [n_slots, 2], where `keypoints` holds the
+        # undistorted ones (mapping.set_keypoints_from_features with distribute's result); None otherwise
+        self.keypoints_dis = None
 
     def set_depth_image(self, image, image_depth_scale=1.0, ph=None):
         """Frame::setDepthIm + the image's scale and pinhole calibration."""

@@ -237,9 +237,11 @@ def monocular_map_initialization_from_features(ctx, kf_ref, kf_cur, settings):
       — fewer than 8 matches raise, as cv::kmeans does there; a score of 0 leaves nothing to triangulate:
       (None, report);
       then monocular_map_initialization on the surviving matches.
-    Settings with Camera.k1 (OpenCV undistortion of keys and bounds) raise ValueError.  report["n_matches"]
-    is the match count; with checks report["n_inliers"] the score."""
-    grid = matching.feature_grid(settings)
+    The grid is matching.frame_grid's: with Camera.k1 its bounds are the undistorted image corners, and the
+    keyframes' keypoints are expected undistorted (set_keypoints_from_features with distribute's result).  Camera.k1
+    with a Camera.fx or Camera.fy that is 0 or missing raises ValueError before the context is touched.
+    report["n_matches"] is the match count; with checks report["n_inliers"] the score."""
+    grid = matching.frame_grid(ctx, settings)
     if kf_ref.descriptors is None or kf_cur.descriptors is None:
         raise ValueError("both keyframes need descriptors")
     matches, _best, _second, n_matches = ctx.match_for_initialization(
@@ -314,7 +316,10 @@ def reconstruct_environment(ctx, kf_ref, kf_cur, matches, settings, samples=None
       monocular_map_initialization on the matches masked to the inliers.
     Returns (Map, report): report["n_inliers"] the best score, ["best"], ["n_hypotheses"], ["n_degenerate"], ["away"]
     next to monocular_map_initialization's.  The Map is None and kf_cur.pose is restored when every score is 0 or
-    reconstructPoints does not accept the pair.  Fewer than 8 matches raise, as cv::kmeans does in the reference."""
+    reconstructPoints does not accept the pair.  Fewer than 8 matches raise, as cv::kmeans does in the reference.
+    The keypoints are the keyframes' undistorted ones; Camera.k1 with a Camera.fx or Camera.fy that is 0 or missing
+    raises ValueError before the context is touched, as it does for matching.frame_grid."""
+    matching.camera_of(settings, "reconstruct_environment")
     matches = np.asarray(matches, np.int64).copy()
     idx = np.flatnonzero(matches >= 0)
     uv1 = np.ascontiguousarray(kf_ref.keypoints[idx], np.float32)
@@ -341,26 +346,41 @@ def reconstruct_environment(ctx, kf_ref, kf_cur, matches, settings, samples=None
     return m, dict(rep, **{k: v for k, v in report.items() if k != "accepted"})
 
 
-def extract_features(ctx, image, settings, pattern, border_mask=None):
+def extract_features(ctx, image, settings, pattern, border_mask=None, distribute=False, n_slots=None):
     """Mapping::extractFeatures (Mapping.cc:120-129) for one 8-bit grey image on `ctx`: features.extract, then
-    features.describe of its keypoints with the caller's sampling pattern.  Returns (capi.FastResult,
-    capi.OrbResult)."""
+    features.describe of its (distorted) keypoints with the caller's sampling pattern.  Returns (capi.FastResult,
+    capi.OrbResult).  With distribute=True the third line runs too, features.distribute of the keypoints over
+    n_slots slots (the frame's capacity; default the keypoints alone), and its capi.DistributedFeatures is the
+    third element returned."""
     from . import features
     keys = features.extract(ctx, image, settings, border_mask)
-    return keys, features.describe(ctx, image, keys, settings, pattern)
+    described = features.describe(ctx, image, keys, settings, pattern)
+    if not distribute:
+        return keys, described
+    return keys, described, features.distribute(ctx, keys, settings, n_slots)
 
 
-def set_keypoints_from_features(kf, result, described=None):
+def extract_and_distribute_features(ctx, image, settings, pattern, border_mask=None, n_slots=None):
+    """extract_features with its third line: (capi.FastResult, capi.OrbResult, capi.DistributedFeatures)."""
+    return extract_features(ctx, image, settings, pattern, border_mask, distribute=True, n_slots=n_slots)
+
+
+def set_keypoints_from_features(kf, result, described=None, distributed=None):
     """Frame::vKeys_ of a keyframe from FAST::extract's result (a capi.FastResult): keypoints, octaves and
     angles of the first len(result) slots; the slots behind them keep zeros, as the reference's vectors of
     nFeatures elements do.  More keypoints than slots raise ValueError (extract stops at the capacity it is
     given, max_keys).  described: ORB::describe's result for the same keypoints (a capi.OrbResult), which
     also fills KeyFrame.descriptors (uint8 [n_slots, 32], zeros behind the keypoints, as the reference's
-    cv::Mat of nFeatures rows); without it the descriptors stay as they are.  Returns the number of
-    keypoints set."""
+    cv::Mat of nFeatures rows); without it the descriptors stay as they are.  distributed: features.distribute's
+    result for the same keypoints (a capi.DistributedFeatures over len(result) or kf.n_slots slots): kf.keypoints
+    then holds its undistorted keys (vKeys_, what every matcher and the graph build read; over n_slots slots also
+    the undistorted zeros behind the keypoints, as in the reference) and kf.keypoints_dis the distorted ones
+    (vKeysDis_).  Returns the number of keypoints set."""
     n = len(result)
     if n > kf.n_slots:
         raise ValueError(f"{n} keypoints for a keyframe of {kf.n_slots} slots: pass max_keys = n_slots to the extraction")
+    if distributed is not None and len(distributed) not in (n, kf.n_slots):
+        raise ValueError(f"undistorted keys of {len(distributed)} slots for {n} keypoints in {kf.n_slots} slots")
     if described is not None:
         if len(described) != n:
             raise ValueError(f"{len(described)} descriptors for {n} keypoints")
@@ -372,4 +392,7 @@ def set_keypoints_from_features(kf, result, described=None):
     kf.keypoints[:n] = result.uv
     kf.octaves[:n] = result.octave
     kf.angles[:n] = result.angle
+    if distributed is not None:
+        kf.keypoints_dis = kf.keypoints.copy()
+        kf.keypoints[:len(distributed)] = distributed.uv
     return n

@@ -2,7 +2,9 @@
 for the library's entries; written from the reference, not from the library's host loops):
 
   feature_grid(settings)          the Frame's grid and scale pyramid as a dict of deftri_feature_grid's fields
-                                  (Frame.cc:213-250, :65-70)
+                                  (Frame.cc:213-250, :65-70), for settings without Camera.k1
+  frame_grid(ctx, settings)       the same for any settings: with Camera.k1 the bounds are the undistorted image
+                                  corners (Context.image_bounds)
   hamming(desc_a, desc_b)         HammingDistance (Modules/Matching/DescriptorMatching.cc:21-36)
   pos_in_grid / build_grid        Frame::posInGrid (Frame.cc:277-286) and the grid distributeFeatures fills (:204-210)
   features_in_area(...)           Frame::getFeaturesInArea (Frame.cc:288-323)
@@ -51,6 +53,31 @@ def feature_grid(settings):
     return {"cols": int(settings.grid_cols), "rows": int(settings.grid_rows), "min_col": 0.0, "min_row": 0.0,
             "max_col": float(int(settings.cols)), "max_row": float(int(settings.rows)),
             "n_scales": int(settings.n_scales), "scale_factor": float(settings.scale_factor)}
+
+
+def camera_of(settings, what="frame_grid"):
+    """(calib, dist) Frame passes to cv::undistortPoints: Camera.fx, fy, cx, cy as float32 [4] and
+    Settings.distortion.  With Camera.k1 set, a Camera.fx or Camera.fy that is 0 or missing raises ValueError: the
+    undistortion divides by them."""
+    dist = np.asarray(getattr(settings, "distortion", ()), F).reshape(-1)
+    calib = np.array([settings.fx, settings.fy, settings.cx, settings.cy], F)
+    if len(dist) and (calib[0] == 0 or calib[1] == 0):
+        raise ValueError(f"{what}: Camera.k1 is set but Camera.fx or Camera.fy is 0 or missing: the reference's "
+                         "undistortion (Frame.cc:228-275) divides by them")
+    return calib, dist
+
+
+def frame_grid(ctx, settings):
+    """The grid of a Frame built from `settings` (Frame.cc:213-250), for any settings: the dict feature_grid
+    returns, with the bounds of Context.image_bounds — 0, 0, Camera.cols, Camera.rows without Camera.k1, the
+    undistorted image corners with it (computeImageBoundaries)."""
+    calib, dist = camera_of(settings)
+    if not len(dist):
+        return feature_grid(settings)
+    b = ctx.image_bounds(int(settings.cols), int(settings.rows), calib, dist)
+    return {"cols": int(settings.grid_cols), "rows": int(settings.grid_rows), "min_col": float(b[0]), "min_row": float(b[1]),
+            "max_col": float(b[2]), "max_row": float(b[3]), "n_scales": int(settings.n_scales),
+            "scale_factor": float(settings.scale_factor)}
 
 
 def scale_factors(grid):

@@ -69,11 +69,24 @@ class Settings:
         self.trian_checks = kv.get("Triangulation.checks", "") == "true"
         # Camera.k1 present: the reference undistorts keys and image bounds with OpenCV (Settings.cc:54-66)
         self.has_distortion = "Camera.k1" in kv
+        # vDistortion_ (Settings.cc:54-67): Camera.k1, k2, p1, p2 and, only where Camera.k3 is present, k3 — float32,
+        # empty without Camera.k1.  Not the attributes k0..k3 above, which are Camera.d0..d3 (the KB8 coefficients).
+        import numpy as np
+        names = ["Camera.k1", "Camera.k2", "Camera.p1", "Camera.p2"] + (["Camera.k3"] if "Camera.k3" in kv else [])
+        self.distortion = np.array([self._number(kv.get(k)) for k in names] if self.has_distortion else [], np.float32)
         self.n_scales = int(self.n_scales)
         for attr in ("grid_cols", "grid_rows", "n_features", "matching_init_th"):     # ints in Settings.h
             setattr(self, attr, int(getattr(self, attr)))
         self.n_optimizations = int(self.n_optimizations)
         self.n_iterations = int(self.n_iterations)
+
+    @staticmethod
+    def _number(v):
+        """A numeric node as the loop above reads it: 0 when missing or not a number."""
+        try:
+            return float(v) if v is not None and re.match(r"^[-+0-9.eE]+$", v) else 0.0
+        except ValueError:
+            return 0.0
 
     @property
     def depth_sigma(self):

@@ -1223,6 +1223,50 @@ int deftri_graph_stats(const deftri_ctx *ctx, int64_t *memo_hits, int64_t *struc
    structure memo — so the mesh equals a new Delaunay triangulation triangle for triangle) instead of
    triangulated anew, and the flips they took, over this context's life. */
 int deftri_graph_repairs(const deftri_ctx *ctx, int64_t *meshes, int64_t *flips);
+
+/* ---- the Delaunay mesh on the device: one star per wave (delaunay_dev.hip) -------------- */
+typedef struct deftri_delaunay_report {
+    int32_t n_tris;                      /* triangles written to tris */
+    int32_t hull_size;                   /* convex-hull vertices */
+    int32_t skipped;                     /* duplicate points the triangulation left out (a fallback's) */
+    int32_t path;                        /* 0 the host sweep (delaunay.cpp), 1 stars on the host, 2 stars on the device */
+    int32_t host_stars;                  /* stars the device marked (an uncertain predicate, more than 64
+                                            triangles) and the host rebuilt with exact predicates; n on path 1 */
+    int32_t fallback;                    /* why the host sweep ran: 0 it did not, 1 a tie (a zero predicate), 2 a
+                                            duplicate point, 3 more than max(64, n / 64) marked stars, 4 n < 3 */
+    int32_t max_degree;                  /* the largest star (neighbours of one point); 0 after a fallback */
+    int32_t round_trips;                 /* blocking device synchronisations of the call (1 on the device path) */
+    double ms_grid, ms_stars, ms_host, ms_total;   /* device grid and star kernels (events), host resolution, the call */
+} deftri_delaunay_report;                /* deftri_sizeof(24) */
+
+/* The Delaunay triangulation of n points xy [2 * n] (x, y interleaved, double): tris [3 * n_tris], counter-
+   clockwise, each triangle starting at its smallest vertex, sorted by (first, second, third) — the order and
+   the triangles of the library's host sweep (delaunay2d), triangle for triangle, on every input.  Every point
+   builds its own star from a uniform grid of about n cells: the nearest neighbour first, then the next
+   neighbour counter-clockwise by the in-circle order, until the sweep closes or meets the hull; a point emits
+   the triangles in which it is the smallest vertex.  On a device context one wave builds a star with the
+   floating-point filters of the host's predicates; a star with a predicate inside its filter bound, or more than
+   64 neighbours, is marked and rebuilt on the host with the exact predicates.  A host-only context builds every
+   star with the exact predicates in a sequential loop.  A tie (a predicate that is exactly zero: cocircular or
+   collinear points), a duplicate point, more than max(64, n / 64) marked stars or n < 3 run the host sweep
+   instead, whose result (skipped included) is then returned; report->fallback says why.
+   tris_cap: the triangles tris has room for; 2 * n is always enough.  One upload and one blocking download.
+   DEFTRI_E_ARG with a message, outputs untouched: a null pointer, n < 0, a coordinate that is not finite,
+   tris_cap below the number of triangles (the message names it).  DEFTRI_E_GRAPH: all points on a line (n >= 3);
+   *report is written (fallback), tris is not.  n < 3 returns 0 with n_tris 0 and fallback 4. */
+int deftri_delaunay2d(deftri_ctx *ctx, int32_t n, const double *xy, int32_t tris_cap, int32_t *tris /* out */,
+        deftri_delaunay_report *report /* out */);
+/* Who triangulates a keyframe's positions in deftri_arap_build_graph / _optimization when neither the graph
+   memo nor the structure memo supplies the mesh: 0 (default) the host sweep, 1 deftri_delaunay2d's path on this
+   context (the same triangles, so the same graph bit for bit).  deftri_graph_stats / _repairs keep their meaning. */
+int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode);
+/* TEST ONLY: 1 when tris [3 * n_tris] is THE Delaunay triangulation of xy (delaunay_still_valid, the structure
+   memo's exact certificate), else 0. */
+int deftri_debug_delaunay_still_valid(int32_t n, const double *xy, int32_t n_tris, const int32_t *tris);
+/* TEST ONLY: the host sweep itself (delaunay2d): returns n_tris, or DEFTRI_E_GRAPH for collinear input /
+   n < 3, or DEFTRI_E_ARG when tris_cap is too small. */
+int deftri_debug_delaunay_sweep(int32_t n, const double *xy, int32_t tris_cap, int32_t *tris, int32_t *hull_size,
+        int32_t *skipped);
 /* Keyframe pairs of the graphs this context builds (deftri_arap_build_graph / _optimization): 0
    (default) every pair (a, b > a) in map order, as the reference's loop (g2oBundleAdjustment.cc:
    640-645); w > 0 only pairs with b - a <= w (a sliding window: the documented deviation used for

@@ -2,7 +2,9 @@
 N_CORR correspondences: run with DEFTRI_CALL_TIMING=1 DEFTRI_PLAN_TIMING=1 DEFTRI_GRAPH_TIMING=1
 DEFTRI_UPLOAD_TIMING=1 to get the library's per-stage lines on stderr.
 
-usage: python tools/e2e_timing.py [N_CORR]"""
+MESH_BUILDER (deftri_set_mesh_builder): 0 the host sweep (default), 1 the Delaunay stars on the device.
+
+usage: python tools/e2e_timing.py [N_CORR] [MESH_BUILDER]"""
 import json
 import pathlib
 import sys
@@ -14,5 +16,15 @@ import torch  # noqa: F401,E402
 import bench  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
+mesh_builder = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 p, m = bench.build_problem(n, 1)
-print(json.dumps(bench.end_to_end(0, m, lambda c: c.set_plan("auto"))), flush=True)
+
+
+def configure(c):
+    c.set_plan("auto")
+    c.set_mesh_builder(mesh_builder)
+
+
+out = bench.end_to_end(0, m, configure)
+out["mesh_builder"] = mesh_builder
+print(json.dumps(out), flush=True)

@@ -569,6 +569,11 @@ bool delaunay_repair(const double *xy, int n, const std::vector<int32_t> &prev, 
 }
 
 int orient2d_sign(const double *a, const double *b, const double *c) { return orient2d(a, b, c); }
+// the sign of |a - p|^2 - |b - p|^2, exact (the star builder's nearest neighbour, delaunay_star.h)
+int dist2_cmp_sign(const double *p, const double *a, const double *b) {
+    Exp ax = diff(a[0], p[0]), ay = diff(a[1], p[1]), bx = diff(b[0], p[0]), by = diff(b[1], p[1]);
+    return sign(add(add(mul(ax, ax), mul(ay, ay)), neg(add(mul(bx, bx), mul(by, by)))));
+}
 int incircle_sign(const double *a, const double *b, const double *c, const double *d) { return incircle(a, b, c, d); }
 
 }  // namespace deftri

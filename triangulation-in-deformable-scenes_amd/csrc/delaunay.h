@@ -12,6 +12,8 @@ bool delaunay2d(const double *xy, int n, std::vector<int32_t> &tris, int &hull_s
 
 int orient2d_sign(const double *a, const double *b, const double *c);
 int incircle_sign(const double *a, const double *b, const double *c, const double *d);
+// the exact sign of |a - p|^2 - |b - p|^2 (< 0: a is the nearer)
+int dist2_cmp_sign(const double *p, const double *a, const double *b);
 
 // Is the triangle list `tris` (canonical, counter-clockwise) still THE Delaunay triangulation of the
 // n points xy — the one delaunay2d would return, triangle for triangle?  True when every triangle is

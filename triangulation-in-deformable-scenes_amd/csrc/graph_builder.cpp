@@ -87,7 +87,7 @@ void mesh_cot_weights(const std::vector<double> &pos, Mesh &M);
 // prev (optional): the previous round's triangulation of the same vertices — repaired by flips when
 // that gives THE Delaunay triangulation (delaunay_repair: then identical to a new one), else unused
 bool build_mesh(const std::vector<double> &pos, int n, Mesh &M, std::string &err, bool host_weights = true,
-                const std::vector<int32_t> *prev = nullptr) {
+                const std::vector<int32_t> *prev = nullptr, const MeshSource *mesh_src = nullptr) {
     if (n < 3) { err = "Not enough points to create a triangular mesh."; return false; }
     std::vector<double> xy(2 * (size_t)n);
     for (int i = 0; i < n; i++) { xy[2 * i] = pos[3 * i]; xy[2 * i + 1] = pos[3 * i + 1]; }
@@ -100,6 +100,11 @@ bool build_mesh(const std::vector<double> &pos, int n, Mesh &M, std::string &err
     int flips = 0;
     if (prev && rep_env && std::atoi(rep_env) != 0 && delaunay_repair(xy.data(), n, *prev, M.tris, M.hull, flips)) {
         M.flips = flips;
+    } else if (mesh_src) {
+        if (!(*mesh_src)(xy.data(), n, M.tris, M.hull, skipped, err)) {
+            if (err.empty()) err = "Delaunay triangulation failed (collinear input)";
+            return false;
+        }
     } else if (!delaunay2d(xy.data(), n, M.tris, M.hull, skipped)) {
         err = "Delaunay triangulation failed (collinear input)";
         return false;
@@ -554,7 +559,8 @@ void emit_pair_edges(const deftri_map &map, const PairEmit &pe, int chunk, const
 }
 
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
-                      GraphResult &g, std::string &err, int pair_window, GraphDevice *gdev, DepthImages *images) {
+                      GraphResult &g, std::string &err, int pair_window, GraphDevice *gdev, DepthImages *images,
+                      const MeshSource *mesh_src) {
     g.err_code = 0;
     // the keyframes with a depth image on the context: their depth measurements come from the image
     std::vector<DepthView> dv((size_t)std::max(map.n_keyframes, 0));
@@ -674,7 +680,7 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
         Mesh M;
         const std::vector<int32_t> *hint =
             prev_mesh[b] && prev_mesh[b]->n1 == md->n1 ? &prev_mesh[b]->tris : nullptr;
-        if (!build_mesh(md->pos1, md->n1, M, e, gdev == nullptr, hint)) return nullptr;   // device: weights in the device pass
+        if (!build_mesh(md->pos1, md->n1, M, e, gdev == nullptr, hint, mesh_src)) return nullptr;   // device: weights in the device pass
         md->tris = std::move(M.tris); md->off = std::move(M.off); md->adj = std::move(M.adj);
         md->w = std::move(M.w);
         md->T = M.T; md->hull = M.hull; md->area = M.area;

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -91,11 +92,17 @@ class GraphDevice {
     size_t cap_ = 0;
 };
 
+// Who triangulates a keyframe's (x, y): xy [2 * n] -> canonical tris, hull_size, skipped, as delaunay2d does and
+// with its result (deftri_set_mesh_builder: the star path of delaunay_dev.hip).  Called from parallel host
+// threads.  False: no triangulation exists (collinear input) or err.
+using MeshSource = std::function<bool(const double *xy, int n, std::vector<int32_t> &tris, int &hull_size, int &skipped,
+                                      std::string &err)>;
+
 // pair_window > 0: only keyframe pairs (a, b) with b - a <= pair_window in map order (the
 // sliding-window deviation of BASELINE C5; 0 = every pair, the reference's loop :640-645)
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
                       GraphResult &g, std::string &err, int pair_window = 0, GraphDevice *gdev = nullptr,
-                      DepthImages *images = nullptr);
+                      DepthImages *images = nullptr, const MeshSource *mesh_src = nullptr);
 
 void writeback_arap(deftri_map &map, const GraphResult &g, const std::vector<double> &points,
                     const std::vector<double> &scales, const std::vector<double> &tg, double *optimization_update);

@@ -43,6 +43,8 @@
 #include "triangulate.h"
 #include "triangulation_matching.h"
 #include "undistort.h"
+#include "delaunay.h"
+#include "delaunay_dev.h"
 
 using namespace deftri;
 
@@ -121,6 +123,9 @@ struct deftri_ctx {
     // map-level graph (deftri_arap_build_graph)
     GraphResult graph;
     std::unique_ptr<GraphDevice> gdev;      // computeR on this context's device (graph_dev.hip)
+    std::unique_ptr<DelaunayDevice> ddev;   // the star path's device arena and pinned staging (delaunay_dev.hip)
+    int mesh_builder = 0;                   // deftri_set_mesh_builder
+    MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
     OrbState orb;                           // ORB::describe's pattern, device arena and events (orb.hip)
     // speculative lambda lanes (see Lane)
@@ -187,6 +192,8 @@ int fail(deftri_ctx *c, int code, const std::string &m) {
     if (c) c->err = m;
     return code;
 }
+
+DelaunayDevice *delaunay_device(deftri_ctx *ctx);   // with the map-level helpers below
 
 #define HIPOK(expr)                                                                          \
     do {                                                                                     \
@@ -1105,6 +1112,7 @@ int deftri_ctx_destroy(deftri_ctx *ctx) {
     hipSetDevice(ctx->device);
     free_device(ctx);
     ctx->gdev.reset();
+    ctx->ddev.reset();
     { std::string e; ctx->images.set(0, nullptr, e); }
     delete ctx->sp_tr;
     ctx->sp_tr = nullptr;
@@ -1513,6 +1521,7 @@ int64_t deftri_sizeof(int32_t which) {
         case 20: return (int64_t)sizeof(deftri_projection_report);
         case 22: return (int64_t)sizeof(deftri_essential_report);
         case 23: return (int64_t)sizeof(deftri_triangulation_match_report);
+        case 24: return (int64_t)sizeof(deftri_delaunay_report);
         default: return -1;
     }
 }
@@ -2231,6 +2240,55 @@ int deftri_fuse_search(deftri_ctx *ctx, const deftri_feature_grid *grid, const f
     return rc ? fail(ctx, rc, err) : 0;
 }
 
+// ---- the Delaunay mesh star by star (delaunay_dev.hip) ----
+int deftri_delaunay2d(deftri_ctx *ctx, int32_t n, const double *xy, int32_t tris_cap, int32_t *tris, deftri_delaunay_report *report) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (n < 0 || n > (1 << 24)) return fail(ctx, DEFTRI_E_ARG, "delaunay2d: n is negative or above 2^24");
+    if (!report || !tris || (n > 0 && !xy) || tris_cap < 0) return fail(ctx, DEFTRI_E_ARG, "delaunay2d: null array or negative tris_cap");
+    for (int64_t i = 0; i < 2 * (int64_t)n; i++)
+        if (!std::isfinite(xy[i])) return fail(ctx, DEFTRI_E_ARG, "delaunay2d: coordinate " + std::to_string(i) + " is not finite");
+    std::vector<int32_t> out;
+    deftri_delaunay_report rep;
+    std::string err;
+    const int rc = delaunay_stars(ctx->device < 0 ? nullptr : delaunay_device(ctx), n, xy, out, rep, err);
+    if (rc == DEFTRI_E_GRAPH) {
+        *report = rep;
+        return fail(ctx, rc, "delaunay2d: no triangle exists (all points on a line)");
+    }
+    if (rc) return fail(ctx, rc, err);
+    if ((int64_t)out.size() > 3 * (int64_t)tris_cap)
+        return fail(ctx, DEFTRI_E_ARG, "delaunay2d: tris_cap " + std::to_string(tris_cap) + " is too small, " +
+                                           std::to_string(out.size() / 3) + " triangles are needed (2 n always suffices)");
+    if (!out.empty()) std::memcpy(tris, out.data(), sizeof(int32_t) * out.size());
+    *report = rep;
+    return 0;
+}
+
+int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_mesh_builder: mode is 0 (host sweep) or 1 (stars)");
+    ctx->mesh_builder = mode;
+    return 0;
+}
+
+int deftri_debug_delaunay_still_valid(int32_t n, const double *xy, int32_t n_tris, const int32_t *tris) {
+    if (n < 0 || n_tris < 0 || !xy || !tris) return DEFTRI_E_ARG;
+    const std::vector<int32_t> t(tris, tris + 3 * (size_t)n_tris);
+    return delaunay_still_valid(xy, n, t) ? 1 : 0;
+}
+
+int deftri_debug_delaunay_sweep(int32_t n, const double *xy, int32_t tris_cap, int32_t *tris, int32_t *hull_size, int32_t *skipped) {
+    if (n < 0 || (n > 0 && !xy) || !tris || !hull_size || !skipped) return DEFTRI_E_ARG;
+    std::vector<int32_t> out;
+    int hull = 0, skip = 0;
+    if (!delaunay2d(xy, n, out, hull, skip)) return DEFTRI_E_GRAPH;
+    if ((int64_t)out.size() > 3 * (int64_t)tris_cap) return DEFTRI_E_ARG;
+    std::memcpy(tris, out.data(), sizeof(int32_t) * out.size());
+    *hull_size = hull;
+    *skipped = skip;
+    return (int)(out.size() / 3);
+}
+
 // ---- Frame::undistortKeys, computeImageBoundaries and distributeFeatures (undistort.hip) ----
 int deftri_undistort_points(deftri_ctx *ctx, int32_t n, const float *uv_in, const float *calib, const float *dist, int32_t n_dist,
                             float *uv_out) {
@@ -2480,6 +2538,29 @@ GraphDevice *graph_device(deftri_ctx *ctx) {
     if (!ctx->gdev) ctx->gdev.reset(new GraphDevice(ctx->device, ctx->st));
     return ctx->gdev.get();
 }
+// the star path's buffers: nullptr on a host-only context (every star on the host)
+DelaunayDevice *delaunay_device(deftri_ctx *ctx) {
+    if (ctx->device < 0) return nullptr;
+    if (!ctx->ddev) ctx->ddev.reset(new DelaunayDevice(ctx->device, ctx->st));
+    return ctx->ddev.get();
+}
+// deftri_set_mesh_builder(1): the graph builder's meshes from delaunay_stars
+const MeshSource *mesh_source(deftri_ctx *ctx) {
+    if (ctx->mesh_builder == 0) return nullptr;
+    if (!ctx->mesh_src) {
+        DelaunayDevice *dd = delaunay_device(ctx);
+        ctx->mesh_src = [dd](const double *xy, int n, std::vector<int32_t> &tris, int &hull, int &skipped, std::string &err) {
+            deftri_delaunay_report rep;
+            for (int64_t i = 0; i < 2 * (int64_t)n; i++)             // the grid needs finite coordinates: the sweep's answer
+                if (!std::isfinite(xy[i])) return delaunay2d(xy, n, tris, hull, skipped);
+            const int rc = delaunay_stars(dd, n, xy, tris, rep, err);
+            hull = rep.hull_size;
+            skipped = rep.skipped;
+            return rc == 0 && rep.n_tris > 0;
+        };
+    }
+    return &ctx->mesh_src;
+}
 }  // namespace
 extern "C" {
 
@@ -2487,7 +2568,8 @@ int deftri_arap_build_graph(deftri_ctx *ctx, const deftri_map *map, double rep_w
                             float depth_error, const deftri_problem_desc **desc_out) {
     if (!ctx || !map || !desc_out) return DEFTRI_E_ARG;
     std::string err;
-    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images))
+    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images,
+                          mesh_source(ctx)))
         return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     *desc_out = &ctx->graph.desc;
     return 0;
@@ -2566,7 +2648,8 @@ int deftri_arap_optimization(deftri_ctx *ctx, deftri_map *map, double rep_weight
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
     };
     std::string err;
-    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images))
+    if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images,
+                          mesh_source(ctx)))
         return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     const double ms_graph = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();

@@ -236,6 +236,15 @@ class TriangulationMatchReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class DelaunayReport(C.Structure):
+    _fields_ = [("n_tris", i32), ("hull_size", i32), ("skipped", i32), ("path", i32), ("host_stars", i32), ("fallback", i32),
+                ("max_degree", i32), ("round_trips", i32), ("ms_grid", f64), ("ms_stars", f64), ("ms_host", f64), ("ms_total", f64)]
+
+    def as_dict(self):
+        """The counters; the times (ms_*) are measurements, not results."""
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

@@ -91,6 +91,10 @@ def load():
         "deftri_distribute_features": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32,
                                                  P(C.c_float), P(C.c_float), C.c_int32, C.c_int32, P(C.c_float), P(C.c_float),
                                                  P(_abi.FeatureGrid), P(C.c_int32), P(C.c_int32), P(C.c_uint8)]),
+        "deftri_delaunay2d": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(_abi.DelaunayReport)]),
+        "deftri_set_mesh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_debug_delaunay_still_valid": (C.c_int, [C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32)]),
+        "deftri_debug_delaunay_sweep": (C.c_int, [C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
         "deftri_search_with_projection": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
                                                     P(C.c_float), P(C.c_int32), P(C.c_uint8), P(C.c_int32), C.c_int32,
                                                     P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_float), P(C.c_uint8),
@@ -231,6 +235,7 @@ EXPORTED = [
     "deftri_fast_extract", "deftri_debug_fast_pyramid", "deftri_debug_fast_candidates", "deftri_debug_fast_mask",
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
     "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
+    "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
 ]
 
 
@@ -674,6 +679,24 @@ class Context:
         self._check(self.lib.deftri_arap_graph_point_ids(self.h, ids.ctypes.data_as(C.POINTER(C.c_int64)), p.n_points))
         p.point_ids = ids
         return p
+
+    def set_mesh_builder(self, mode):
+        """Who triangulates a keyframe in the graph builds of this context (deftri_set_mesh_builder): 0 the host
+        sweep (the default), 1 the star path of Context.delaunay.  The graph is the same bit for bit."""
+        self._check(self.lib.deftri_set_mesh_builder(self.h, int(mode)))
+
+    def delaunay(self, xy, tris_cap=None):
+        """The Delaunay triangulation of xy [n, 2] (deftri_delaunay2d) on this context: stars on the device, or on
+        the host with exact predicates on a host-only one.  Returns (tris int32 [T, 3], counter-clockwise, each
+        starting at its smallest vertex, sorted; report dict): the library's host sweep, triangle for triangle.
+        All points on a line raise DeftriError (DEFTRI_E_GRAPH)."""
+        xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        n = len(xy)
+        cap = 2 * n + 1 if tris_cap is None else int(tris_cap)
+        tris = np.zeros((max(cap, 1), 3), np.int32)
+        rep = _abi.DelaunayReport()
+        self._check(self.lib.deftri_delaunay2d(self.h, n, _dp(xy), cap, tris.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
+        return tris[:rep.n_tris].copy(), rep.as_dict()
 
     def graph_repairs(self):
         """(keyframe meshes of full graph builds repaired from the previous build's triangulation, their

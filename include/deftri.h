@@ -1260,6 +1260,31 @@ int deftri_delaunay2d(deftri_ctx *ctx, int32_t n, const double *xy, int32_t tris
    memo nor the structure memo supplies the mesh: 0 (default) the host sweep, 1 deftri_delaunay2d's path on this
    context (the same triangles, so the same graph bit for bit).  deftri_graph_stats / _repairs keep their meaning. */
 int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode);
+/* Who builds the iterative plan at the next deftri_problem_upload (and in the uploads inside
+   deftri_arap_optimization / deftri_deformation_optimization): 0 (default) the host passes of
+   csrc/spcg_plan.cpp; 1 the device stages of csrc/plan_dev.hip where they apply, the host passes elsewhere.
+   The device stages apply on a device context of one rank to a problem of one keyframe pair, at most two depth
+   scales and at least one ARAP edge whose upload asks for the tile layout (from 50,000 unknowns).  The plan is
+   equal array for array.  DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the
+   upload with DEFTRI_E_HIP. */
+int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode);
+/* What the last iterative plan build of this context did: builder_used 0 / 1; stages = bit mask of
+   the stages that ran on the device (bit 0 groups, 1 Morton order, 2 rows, 3 rotation numbering,
+   4 rep/depth by row, 5 incidences; bits 0-2 alone: the tile layout was refused after them and the build
+   went on on the host); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
+   2 a bounded loop reached its bound); ms = wall time of the build.  All zero before the first build. */
+int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
+                           int32_t *reason, double *ms);
+/* TEST: build the plan of `desc` as an upload of this context would, with builder `mode` and with
+   the tile layout requested (tile = 1) or not, allocate no solver, and return one FNV-1a digest
+   per plan array in the order of the DEFTRI_PLAN_DIGEST block of build_sp_plan (32: row_of_point,
+   point_of_row, rank_row_begin, arap_ids, rep_ids, dep_ids, rot_ids, arap_rot_local, blk, hv_blk, hv_blk_off,
+   dperm, inc_off, inc, rep_off, dep_off, rowmap, woff, wsplit, pmap, pidx, tile_tab, tile_m0, tile_m1,
+   tile_chunk, tile_rs, tile_halo, tile_xoff, tile_xdst, send_rows, recv_rows, the scalars), then the combined
+   digest that block prints.  *n receives the count (33); cap too small: DEFTRI_E_ARG.  Works on a host-only
+   context (mode 1 is then not applicable).  deftri_plan_build_info afterwards describes this build. */
+int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode,
+                             int32_t tile, uint64_t *digests, int32_t cap, int32_t *n);
 /* TEST ONLY: 1 when tris [3 * n_tris] is THE Delaunay triangulation of xy (delaunay_still_valid, the structure
    memo's exact certificate), else 0. */
 int deftri_debug_delaunay_still_valid(int32_t n, const double *xy, int32_t n_tris, const int32_t *tris);

@@ -3,8 +3,9 @@ N_CORR correspondences: run with DEFTRI_CALL_TIMING=1 DEFTRI_PLAN_TIMING=1 DEFTR
 DEFTRI_UPLOAD_TIMING=1 to get the library's per-stage lines on stderr.
 
 MESH_BUILDER (deftri_set_mesh_builder): 0 the host sweep (default), 1 the Delaunay stars on the device.
+PLAN_BUILDER (deftri_set_plan_builder): 0 the host passes (default), 1 the plan's sorts and scans on the device.
 
-usage: python tools/e2e_timing.py [N_CORR] [MESH_BUILDER]"""
+usage: python tools/e2e_timing.py [N_CORR] [MESH_BUILDER] [PLAN_BUILDER]"""
 import json
 import pathlib
 import sys
@@ -17,14 +18,18 @@ import bench  # noqa: E402
 
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 100000
 mesh_builder = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+plan_builder = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 p, m = bench.build_problem(n, 1)
 
 
 def configure(c):
     c.set_plan("auto")
     c.set_mesh_builder(mesh_builder)
+    if plan_builder:                       # (an older library under DEFTRI_LIB has no such entry)
+        c.set_plan_builder(plan_builder)
 
 
 out = bench.end_to_end(0, m, configure)
 out["mesh_builder"] = mesh_builder
+out["plan_builder"] = plan_builder
 print(json.dumps(out), flush=True)

@@ -1,0 +1,70 @@
+// plan_dev.h — the sorts, scans and first-occurrence numberings of the one-pair tile plan (spcg_plan.cpp
+// stages 1-3, 5, 6 and 8) on the device (plan_dev.hip).  Every stage has a unique output — a stable sort from
+// ascending ids, component roots that are the smallest id, a first-encounter numbering — so the arrays are the
+// host's bit for bit.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "../../include/deftri.h"
+
+namespace deftri {
+
+struct SpPlanHost;
+
+constexpr int kPlanScanTile = 2048;      // elements per workgroup of the multi-block scan (256 threads x 8)
+constexpr int kPlanRadixTile = 256;      // keys per workgroup of the radix sort (one per thread)
+constexpr int kPlanRadixBits = 7;        // digit width: 6 passes over the 42-bit curve key
+constexpr int kPlanRunMax = 256;         // longest run (a row's incidences, a group's points) the per-run sort orders
+constexpr int kPlanHookRetries = 1024;   // compare-and-swap retries of one union before the build is marked
+
+// deftri_plan_build_info
+struct PlanBuildInfo {
+    int32_t builder_used = 0, stages = 0, reason = 0;
+    double ms = 0;
+};
+
+// the device arena and the pinned staging of the plan builder, kept across builds (grow-only) on the context
+class PlanDevice {
+ public:
+    PlanDevice(int device, hipStream_t st) : dev_(device), st_(st) {}
+    ~PlanDevice();
+    PlanDevice(const PlanDevice &) = delete;
+    PlanDevice &operator=(const PlanDevice &) = delete;
+
+    // Both return 0, 1 when a bounded loop reached its bound (the caller builds on the host), or -1 with err
+    // after a HIP error.
+    // stages 1-3 (groups, Morton order, rows) of a validated one-pair problem: one upload of the inputs, the
+    // kernels, one download.  before_alloc: called (and cleared) before the arena grows
+    int rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
+             std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
+             std::string &err);
+    // stages 4-6 (rotation numbering, rep / depth edges by row, incidences) for H.arap_ids on the rows of the
+    // last rows() call: one upload of arap_ids, the kernels, one download into H
+    int edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &err);
+
+ private:
+    bool reserve(size_t dev_bytes, size_t pin_bytes, std::function<void()> *before_alloc);
+    void scan(int *data, int64_t n);
+    void sort_by_row(int64_t n, const int *key, int32_t nkeys, int *off, int *out, int *hdr);
+    void report(int first, int last, const char *const *names) const;
+    int dev_;
+    hipStream_t st_;
+    char *buf_ = nullptr, *pin_ = nullptr;
+    size_t cap_ = 0, pin_cap_ = 0;
+    hipEvent_t ev_[12] = {};
+    // the arena's pieces (byte offsets), laid out by rows()
+    struct Layout {
+        size_t ap, rot, rep_point, dep_point, xy, par, root, flag, gid, grep, mm, lohi, key[2], id[2], hist, gpos, cur,
+            part, dl1, hdr, por, rop, gp, dl1_end, aid, rv, first, rflag, kr, kd, ki, ioff, dl2, hdr2, rot_ids, arl, rep_ids,
+            rep_off, dep_ids, dep_off, inc, inc_off, dl2_end, total;
+    } L_{};
+    int32_t P_ = 0;
+    int64_t E_ = 0;
+};
+
+}  // namespace deftri

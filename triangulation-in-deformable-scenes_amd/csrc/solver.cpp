@@ -125,6 +125,9 @@ struct deftri_ctx {
     std::unique_ptr<GraphDevice> gdev;      // computeR on this context's device (graph_dev.hip)
     std::unique_ptr<DelaunayDevice> ddev;   // the star path's device arena and pinned staging (delaunay_dev.hip)
     int mesh_builder = 0;                   // deftri_set_mesh_builder
+    std::unique_ptr<PlanDevice> pdev;       // the plan builder's device arena and pinned staging (plan_dev.hip)
+    int plan_builder = 0;                   // deftri_set_plan_builder
+    PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
     OrbState orb;                           // ORB::describe's pattern, device arena and events (orb.hip)
@@ -194,6 +197,13 @@ int fail(deftri_ctx *c, int code, const std::string &m) {
 }
 
 DelaunayDevice *delaunay_device(deftri_ctx *ctx);   // with the map-level helpers below
+
+// the plan builder's arena of a device context (null on a host-only one)
+PlanDevice *plan_device(deftri_ctx *ctx) {
+    if (ctx->device < 0) return nullptr;
+    if (!ctx->pdev) ctx->pdev.reset(new PlanDevice(ctx->device, ctx->st));
+    return ctx->pdev.get();
+}
 
 #define HIPOK(expr)                                                                          \
     do {                                                                                     \
@@ -1209,6 +1219,44 @@ int deftri_debug_sp_product(deftri_ctx *ctx, const deftri_problem_desc *desc, co
     return 0;
 }
 
+int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_plan_builder: mode is 0 (host passes) or 1 (device stages)");
+    ctx->plan_builder = mode;
+    return 0;
+}
+
+int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages, int32_t *reason, double *ms) {
+    if (!ctx || !builder_used || !stages || !reason || !ms) return DEFTRI_E_ARG;
+    *builder_used = ctx->plan_build.builder_used;
+    *stages = ctx->plan_build.stages;
+    *reason = ctx->plan_build.reason;
+    *ms = ctx->plan_build.ms;
+    return 0;
+}
+
+int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile, uint64_t *digests,
+                             int32_t cap, int32_t *n) {
+    if (!ctx || !desc || !digests || !n) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_digest: mode is 0 or 1");
+    if (cap < kPlanDigestCount + 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_digest: room for " + std::to_string(kPlanDigestCount + 1) + " digests needed");
+    int rc = validate(ctx, desc);
+    if (rc) return rc;
+    if (ctx->device >= 0) hipSetDevice(ctx->device);
+    SpPlanHost H;
+    std::string err;
+    rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
+                            mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build);
+    if (rc) return fail(ctx, rc, err);
+    std::vector<uint64_t> each;
+    const uint64_t all = plan_digests(H, &each);
+    if ((int)each.size() != kPlanDigestCount) return fail(ctx, DEFTRI_E_INTERNAL, "debug_plan_digest: digest count");
+    std::copy(each.begin(), each.end(), digests);
+    digests[kPlanDigestCount] = all;
+    *n = kPlanDigestCount + 1;
+    return 0;
+}
+
 int deftri_set_pair_window(deftri_ctx *ctx, int32_t window) {
     if (!ctx || window < 0) return DEFTRI_E_ARG;
     ctx->pair_window = window;
@@ -1571,6 +1619,9 @@ int deftri_problem_upload(deftri_ctx *ctx, const deftri_problem_desc *desc) {
         ctx->sp->max_it = ctx->pcg_max_it;
         ctx->sp->fp32_jac = ctx->jac_fp32;
         ctx->sp->before_alloc = [ctx] { join_reaper(ctx); };
+        ctx->sp->plan_builder = ctx->plan_builder;
+        ctx->sp->plan_dev = ctx->plan_builder ? plan_device(ctx) : nullptr;
+        ctx->sp->plan_build = &ctx->plan_build;
         rc = ctx->sp->upload(*desc);
         if (rc) { ctx->err = ctx->sp->err; ctx->sp.reset(); return rc; }
         ctx->sp_on = true;

@@ -35,6 +35,7 @@
 
 #include "../../include/deftri.h"
 #include "kernels.h"
+#include "plan_dev.h"
 
 namespace deftri {
 
@@ -144,7 +145,8 @@ struct SpPlanHost {
 // the groups and rows build_tiles needs (spcg_plan.cpp step 5)
 // the Z-order (Morton) key of a point from its (x, y) in a bounding box, 21 bits per coordinate — the
 // plans' point orders (a Hilbert curve measured no better: C2 and C5 slower, 500k and C3 1-3 % faster)
-inline uint64_t curve_key(double x, double y, const double lo[2], const double hi[2]) {
+// (host and device: the plan builder's kernel computes the same key, plan_dev.hip)
+__host__ __device__ inline uint64_t curve_key(double x, double y, const double lo[2], const double hi[2]) {
     uint32_t k[2];
     const double v[2] = {x, y};
     for (int c = 0; c < 2; c++) {
@@ -188,6 +190,18 @@ int sp_emulate_tile_product(const deftri_problem_desc &d, const SpPlanHost &H, c
 // tile: try the tile layout (one rank, one pair; spcg_tile.cpp) — out.tile says whether it was built
 bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out,
                    std::string &err, bool tile = false);
+// The same plan with the builder deftri_set_plan_builder chose: mode 1 runs stages 1-3, 5, 6 and 8 on `pd`
+// where they apply (one rank, one pair, at most two scales, ARAP edges, the tile layout requested, pd not null)
+// and the host passes elsewhere; info says what ran.  Returns 0, DEFTRI_E_ARG (err) when the problem cannot be
+// planned, DEFTRI_E_HIP (err) after a HIP error in the builder.  before_alloc (may be null): called and cleared
+// before the builder's arena grows
+int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
+                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info);
+// FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
+// not null one digest per array in that block's order (names: kPlanDigestNames)
+uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
+extern const char *const kPlanDigestNames[];
+extern const int kPlanDigestCount;
 // host emulation of one sharded product on the plan (tests; spcg_plan.cpp)
 int sp_emulate_product(const deftri_problem_desc &d, const SpPlanHost &H, const double *Ja, const double *Wa,
                        const double *Jr, const double *Wr, const double *Jd, const double *Wd, double lambda,
@@ -354,6 +368,11 @@ class SpSolver {
     ~SpSolver();
     int upload(const deftri_problem_desc &d);
     std::function<void()> before_alloc;            // upload: called once after the host plan build
+    // deftri_set_plan_builder: the mode, the context's builder arena (null: no device stages) and where the
+    // build reports what it did (deftri_plan_build_info; may be null)
+    int plan_builder = 0;
+    PlanDevice *plan_dev = nullptr;
+    PlanBuildInfo *plan_build = nullptr;
     int refresh(const deftri_problem_desc &d);     // same structure: values only, plan kept
     int solve_lm(const deftri_lm_params &prm, deftri_report &R);
     int download(double *points, double *scales, double *tg);

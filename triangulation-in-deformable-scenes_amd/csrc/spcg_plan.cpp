@@ -110,10 +110,56 @@ void radix_sort_by_key(std::vector<int32_t> &ids, const std::vector<uint64_t> &k
     }
 }
 
+// every plan array in the order of the digest, then the scalars
+template <class F>
+void for_each_plan_array(const SpPlanHost &H, F f) {
+    auto vec = [&](const auto &x) { f(x.data(), x.size() * sizeof(x[0]), true); };
+    vec(H.row_of_point); vec(H.point_of_row); vec(H.rank_row_begin); vec(H.arap_ids); vec(H.rep_ids);
+    vec(H.dep_ids); vec(H.rot_ids); vec(H.arap_rot_local); vec(H.blk); vec(H.hv_blk); vec(H.hv_blk_off);
+    vec(H.dperm); vec(H.inc_off); vec(H.inc); vec(H.rep_off); vec(H.dep_off); vec(H.rowmap); vec(H.woff);
+    vec(H.wsplit); vec(H.pmap); vec(H.pidx);
+    vec(H.tile_tab); vec(H.tile_m0); vec(H.tile_m1); vec(H.tile_chunk); vec(H.tile_rs); vec(H.tile_halo);
+    vec(H.tile_xoff); vec(H.tile_xdst);
+    f(nullptr, 0, true);                               // send_rows: its lists follow, one array
+    for (const auto &x : H.send_rows) f(x.data(), x.size() * sizeof(x[0]), false);
+    f(nullptr, 0, true);                               // recv_rows
+    for (const auto &x : H.recv_rows) f(x.data(), x.size() * sizeof(x[0]), false);
+    const int64_t sc[4] = {H.lo, H.hi, H.n_arap_owned, H.halo_rows};
+    f(sc, sizeof(sc), true);
+}
+
+enum { kPlanOk = 0, kPlanBad = 1, kPlanBound = 2, kPlanHip = 3 };
+
 }  // namespace
 
-bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H,
-                   std::string &err, bool tile) {
+const char *const kPlanDigestNames[] = {
+    "row_of_point", "point_of_row", "rank_row_begin", "arap_ids", "rep_ids", "dep_ids", "rot_ids", "arap_rot_local",
+    "blk", "hv_blk", "hv_blk_off", "dperm", "inc_off", "inc", "rep_off", "dep_off", "rowmap", "woff", "wsplit", "pmap",
+    "pidx", "tile_tab", "tile_m0", "tile_m1", "tile_chunk", "tile_rs", "tile_halo", "tile_xoff", "tile_xdst",
+    "send_rows", "recv_rows", "scalars"};
+const int kPlanDigestCount = (int)(sizeof(kPlanDigestNames) / sizeof(kPlanDigestNames[0]));
+
+uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
+    constexpr uint64_t kBasis = 1469598103934665603ULL, kPrime = 1099511628211ULL;
+    uint64_t h = kBasis;
+    if (each) each->clear();
+    for_each_plan_array(H, [&](const void *v, size_t n, bool starts) {
+        if (each && starts) each->push_back(kBasis);
+        const unsigned char *c = (const unsigned char *)v;
+        uint64_t a = each ? each->back() : 0;
+        for (size_t i = 0; i < n; i++) {
+            h ^= c[i]; h *= kPrime;
+            a ^= c[i]; a *= kPrime;
+        }
+        if (each) each->back() = a;
+    });
+    return h;
+}
+
+// pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
+// stages: the bit mask of the stages it ran
+static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
+                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages) {
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
     auto stage = [&](const char *name) {
@@ -123,123 +169,135 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
         t_prev = t;
     };
     H = SpPlanHost();
-    if (nranks < 1 || rank < 0 || rank >= nranks) { err = "bad rank"; return false; }
+    if (nranks < 1 || rank < 0 || rank >= nranks) { err = "bad rank"; return kPlanBad; }
     H.rank = rank;
     H.nranks = nranks;
     const int32_t P = d.n_points, Q = d.n_pairs, S = d.n_scales;
     const int64_t E = d.n_arap, R = d.n_rep, D = d.n_depth;
     H.P = P; H.Q = Q; H.S = S;
     H.hd = 6 * (int64_t)Q + S;
-    if (E >= (1LL << 29)) { err = "more than 2^29 ARAP edges"; return false; }
+    if (E >= (1LL << 29)) { err = "more than 2^29 ARAP edges"; return kPlanBad; }
     const int32_t *ap = d.arap_pts;
 
-    // 1. keyframe-copy groups: union-find over the ARAP edges' (p1_i, p2_i) and (p1_j, p2_j)
-    //    on host threads: a root is only ever linked under a smaller root (compare-and-swap), so every
-    //    tree's root is its smallest point id and the partition and roots do not depend on the order
-    std::vector<int32_t> par(P);
-    std::iota(par.begin(), par.end(), 0);
-    auto ld = [&](int32_t a) { return __atomic_load_n(&par[a], __ATOMIC_RELAXED); };
-    auto find = [&](int32_t a) {
-        for (;;) {
-            const int32_t p = ld(a);
-            if (p == a) return a;
-            const int32_t gp = ld(p);
-            if (gp != p) { int32_t exp = p; __atomic_compare_exchange_n(&par[a], &exp, gp, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED); }
-            a = p;
+    std::vector<int32_t> gid, gpos, gp_dev;   // group of each point; the groups' Morton positions; gpos[gid[p]]
+    int32_t ng = 0;
+    if (pd) {
+        // stages 1-3 on the device (plan_dev.hip): the same groups, order and rows
+        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err);
+        if (rc) return rc > 0 ? kPlanBound : kPlanHip;
+        *stages |= 7;
+        stage("1-3 on the device (wall)");
+    } else {
+        // 1. keyframe-copy groups: union-find over the ARAP edges' (p1_i, p2_i) and (p1_j, p2_j)
+        //    on host threads: a root is only ever linked under a smaller root (compare-and-swap), so every
+        //    tree's root is its smallest point id and the partition and roots do not depend on the order
+        std::vector<int32_t> par(P);
+        std::iota(par.begin(), par.end(), 0);
+        auto ld = [&](int32_t a) { return __atomic_load_n(&par[a], __ATOMIC_RELAXED); };
+        auto find = [&](int32_t a) {
+            for (;;) {
+                const int32_t p = ld(a);
+                if (p == a) return a;
+                const int32_t gp = ld(p);
+                if (gp != p) { int32_t exp = p; __atomic_compare_exchange_n(&par[a], &exp, gp, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED); }
+                a = p;
+            }
+        };
+        auto unite = [&](int32_t a, int32_t b) {
+            for (;;) {
+                a = find(a); b = find(b);
+                if (a == b) return;
+                if (a > b) std::swap(a, b);
+                int32_t exp = b;                     // b still a root: link it under the smaller a
+                if (__atomic_compare_exchange_n(&par[b], &exp, a, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return;
+            }
+        };
+        chunked(E, 1 << 18, [&](int, int64_t e0, int64_t e1) {
+            for (int64_t e = e0; e < e1; e++) {
+                unite(ap[4 * e], ap[4 * e + 1]);
+                unite(ap[4 * e + 2], ap[4 * e + 3]);
+            }
+        });
+        std::vector<int32_t> root(P);
+        chunked(P, 1 << 16, [&](int, int64_t p0, int64_t p1) {
+            for (int64_t p = p0; p < p1; p++) root[p] = find((int32_t)p);
+        });
+        std::vector<int32_t> grep;               // representative (smallest id) per group
+        gid.assign(P, -1);
+        for (int32_t p = 0; p < P; p++) {
+            const int32_t r = root[p];
+            if (gid[r] < 0) { gid[r] = (int32_t)grep.size(); grep.push_back(r); }
+            gid[p] = gid[r];
         }
-    };
-    auto unite = [&](int32_t a, int32_t b) {
-        for (;;) {
-            a = find(a); b = find(b);
-            if (a == b) return;
-            if (a > b) std::swap(a, b);
-            int32_t exp = b;                     // b still a root: link it under the smaller a
-            if (__atomic_compare_exchange_n(&par[b], &exp, a, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) return;
-        }
-    };
-    chunked(E, 1 << 18, [&](int, int64_t e0, int64_t e1) {
-        for (int64_t e = e0; e < e1; e++) {
-            unite(ap[4 * e], ap[4 * e + 1]);
-            unite(ap[4 * e + 2], ap[4 * e + 3]);
-        }
-    });
-    std::vector<int32_t> root(P);
-    chunked(P, 1 << 16, [&](int, int64_t p0, int64_t p1) {
-        for (int64_t p = p0; p < p1; p++) root[p] = find((int32_t)p);
-    });
-    std::vector<int32_t> gid(P, -1), grep;   // group of each point; representative (smallest id) per group
-    for (int32_t p = 0; p < P; p++) {
-        const int32_t r = root[p];
-        if (gid[r] < 0) { gid[r] = (int32_t)grep.size(); grep.push_back(r); }
-        gid[p] = gid[r];
-    }
-    const int32_t ng = (int32_t)grep.size();
+        ng = (int32_t)grep.size();
 
-    stage("1 groups (union-find)");
-    // 2. groups in Morton order of the representative's mesh-plane position
-    auto xy = [&](int32_t p, int c) { return d.order_xy ? d.order_xy[2 * (int64_t)p + c] : d.points[3 * (int64_t)p + c]; };
-    double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
-    for (int32_t g = 0; g < ng; g++)
-        for (int c = 0; c < 2; c++) {
-            const double v = xy(grep[g], c);
-            if (std::isfinite(v)) { lo[c] = std::min(lo[c], v); hi[c] = std::max(hi[c], v); }
-        }
-    std::vector<uint64_t> key(ng);
-    for (int32_t g = 0; g < ng; g++) key[g] = curve_key(xy(grep[g], 0), xy(grep[g], 1), lo, hi);
-    std::vector<int32_t> gorder(ng);
-    std::iota(gorder.begin(), gorder.end(), 0);
-    // by (key, representative): the representatives ascend with the group number (each group is met
-    // first at its smallest point), so a stable sort by key from the identity is that order
-    radix_sort_by_key(gorder, key);
-    std::vector<int32_t> gpos(ng);
-    for (int32_t k = 0; k < ng; k++) gpos[gorder[k]] = k;
+        stage("1 groups (union-find)");
+        // 2. groups in Morton order of the representative's mesh-plane position
+        auto xy = [&](int32_t p, int c) { return d.order_xy ? d.order_xy[2 * (int64_t)p + c] : d.points[3 * (int64_t)p + c]; };
+        double lo[2] = {1e300, 1e300}, hi[2] = {-1e300, -1e300};
+        for (int32_t g = 0; g < ng; g++)
+            for (int c = 0; c < 2; c++) {
+                const double v = xy(grep[g], c);
+                if (std::isfinite(v)) { lo[c] = std::min(lo[c], v); hi[c] = std::max(hi[c], v); }
+            }
+        std::vector<uint64_t> key(ng);
+        for (int32_t g = 0; g < ng; g++) key[g] = curve_key(xy(grep[g], 0), xy(grep[g], 1), lo, hi);
+        std::vector<int32_t> gorder(ng);
+        std::iota(gorder.begin(), gorder.end(), 0);
+        // by (key, representative): the representatives ascend with the group number (each group is met
+        // first at its smallest point), so a stable sort by key from the identity is that order
+        radix_sort_by_key(gorder, key);
+        gpos.assign(ng, 0);
+        for (int32_t k = 0; k < ng; k++) gpos[gorder[k]] = k;
 
-    stage("2 Morton order");
-    // 3. rows: groups in that order, points of a group by id.  A tile plan of several pairs (one rank)
-    //    numbers them keyframe-major instead — by the camera of the point's reprojection edges, then
-    //    the Morton order of the point's own position — so a tile of pair (a, b), consecutive units of
-    //    that pair in the Morton order of keyframe b's positions, owns runs of keyframe b's rows
-    std::vector<int32_t> pts(P);
-    std::iota(pts.begin(), pts.end(), 0);
-    counting_sort(pts, ng, [&](int32_t p) { return gpos[gid[p]]; });
-    if (tile && Q > 1 && nranks == 1) {
-        std::vector<int32_t> pcam(P, -1);
-        bool one_cam = true;
-        for (int64_t e = 0; e < R; e++) {
-            int32_t &c = pcam[d.rep_point[e]];
-            if (c < 0) c = d.rep_cam[e];
-            else if (c != d.rep_cam[e]) one_cam = false;
-        }
-        if (one_cam) {
-            const int32_t C = std::max(d.n_cams, 1);
-            {
-                // inside a keyframe, its points in the Morton order of their own positions: the order in
-                // which the pairs whose mesh is that keyframe's (it is their keyframe 1) cut their tiles
-                // (spcg_tile.cpp), so those tiles' keyframe-1 rows are runs (C5's CG iteration -3 %)
-                std::vector<double> blo(2 * (size_t)(C + 1), 1e300), bhi(2 * (size_t)(C + 1), -1e300);
-                auto cam = [&](int32_t p) { return pcam[p] < 0 ? C : pcam[p]; };
-                for (int32_t p = 0; p < P; p++)
-                    for (int c = 0; c < 2; c++) {
-                        const double v = d.points[3 * (int64_t)p + c];
-                        if (std::isfinite(v)) {
-                            blo[2 * cam(p) + c] = std::min(blo[2 * cam(p) + c], v);
-                            bhi[2 * cam(p) + c] = std::max(bhi[2 * cam(p) + c], v);
+        stage("2 Morton order");
+        // 3. rows: groups in that order, points of a group by id.  A tile plan of several pairs (one rank)
+        //    numbers them keyframe-major instead — by the camera of the point's reprojection edges, then
+        //    the Morton order of the point's own position — so a tile of pair (a, b), consecutive units of
+        //    that pair in the Morton order of keyframe b's positions, owns runs of keyframe b's rows
+        std::vector<int32_t> pts(P);
+        std::iota(pts.begin(), pts.end(), 0);
+        counting_sort(pts, ng, [&](int32_t p) { return gpos[gid[p]]; });
+        if (tile && Q > 1 && nranks == 1) {
+            std::vector<int32_t> pcam(P, -1);
+            bool one_cam = true;
+            for (int64_t e = 0; e < R; e++) {
+                int32_t &c = pcam[d.rep_point[e]];
+                if (c < 0) c = d.rep_cam[e];
+                else if (c != d.rep_cam[e]) one_cam = false;
+            }
+            if (one_cam) {
+                const int32_t C = std::max(d.n_cams, 1);
+                {
+                    // inside a keyframe, its points in the Morton order of their own positions: the order in
+                    // which the pairs whose mesh is that keyframe's (it is their keyframe 1) cut their tiles
+                    // (spcg_tile.cpp), so those tiles' keyframe-1 rows are runs (C5's CG iteration -3 %)
+                    std::vector<double> blo(2 * (size_t)(C + 1), 1e300), bhi(2 * (size_t)(C + 1), -1e300);
+                    auto cam = [&](int32_t p) { return pcam[p] < 0 ? C : pcam[p]; };
+                    for (int32_t p = 0; p < P; p++)
+                        for (int c = 0; c < 2; c++) {
+                            const double v = d.points[3 * (int64_t)p + c];
+                            if (std::isfinite(v)) {
+                                blo[2 * cam(p) + c] = std::min(blo[2 * cam(p) + c], v);
+                                bhi[2 * cam(p) + c] = std::max(bhi[2 * cam(p) + c], v);
+                            }
                         }
-                    }
-                std::vector<uint64_t> pk(P);
-                            for (int32_t p = 0; p < P; p++)
-                    pk[p] = curve_key(d.points[3 * (int64_t)p], d.points[3 * (int64_t)p + 1], &blo[2 * cam(p)],
-                                      &bhi[2 * cam(p)]);
-                // by (camera, key, point): stable by key from ascending points, then stable by camera
-                std::iota(pts.begin(), pts.end(), 0);
-                radix_sort_by_key(pts, pk);
-                counting_sort(pts, C + 1, [&](int32_t p) { return cam(p); });
+                    std::vector<uint64_t> pk(P);
+                                for (int32_t p = 0; p < P; p++)
+                        pk[p] = curve_key(d.points[3 * (int64_t)p], d.points[3 * (int64_t)p + 1], &blo[2 * cam(p)],
+                                          &bhi[2 * cam(p)]);
+                    // by (camera, key, point): stable by key from ascending points, then stable by camera
+                    std::iota(pts.begin(), pts.end(), 0);
+                    radix_sort_by_key(pts, pk);
+                    counting_sort(pts, C + 1, [&](int32_t p) { return cam(p); });
+                }
             }
         }
+        H.point_of_row = pts;
+        H.row_of_point.assign(P, 0);
+        for (int32_t r = 0; r < P; r++) H.row_of_point[pts[r]] = r;
     }
-    H.point_of_row = pts;
-    H.row_of_point.assign(P, 0);
-    for (int32_t r = 0; r < P; r++) H.row_of_point[pts[r]] = r;
+    const std::vector<int32_t> &pts = H.point_of_row;
     const std::vector<int32_t> &row = H.row_of_point;
 
     stage("3 rows");
@@ -271,8 +329,12 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
     if (tile && Q == 1 && S <= 2 && E > 0) {
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
-        std::vector<int32_t> gp(P);
-        for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
+        std::vector<int32_t> gp;
+        if (pd) gp.swap(gp_dev);
+        else {
+            gp.resize(P);
+            for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
+        }
         TileInput ti;
         ti.P = P; ti.ng = ng; ti.E = E; ti.ap = ap; ti.gpos = gp.data(); ti.row_of_point = H.row_of_point.data();
         std::string why;
@@ -386,8 +448,17 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
     halo_e.clear(); halo_e.shrink_to_fit();
     const int64_t nloc = (int64_t)H.arap_ids.size();
 
+    // the device builder goes on only with the tile layout: a refused layout (tile_why) continues on the host
+    // from the same rows
+    const bool dev_edges = pd && H.tile;
+    if (dev_edges) {
+        // stages 5 (rotation numbering), 6 and 8 on the device (plan_dev.hip), into H
+        const int rc = pd->edges(d, H, err);
+        if (rc) return rc > 0 ? kPlanBound : kPlanHip;
+        *stages |= 0x38;
+    }
     // rotation rows used by the local edges, compacted
-    {
+    if (!dev_edges) {
         // numbered in first-encounter order over the positions 2 le + k: each row's first position
         // (an atomic minimum over host threads), the first positions flagged and prefix-summed
         const int64_t npos = 2 * nloc;
@@ -433,24 +504,26 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
         });
     }
 
-    stage("5 local ARAP edges");
+    stage(dev_edges ? "5, 6, 8 on the device (wall)" : "5 local ARAP edges");
     // 6. the own rows' reprojection / depth edges, by row
-    if (nranks == 1) {
-        H.rep_ids.resize((size_t)R);
-        std::iota(H.rep_ids.begin(), H.rep_ids.end(), 0);
-        H.dep_ids.resize((size_t)D);
-        std::iota(H.dep_ids.begin(), H.dep_ids.end(), 0);
-    } else {
-        for (int64_t e = 0; e < R; e++) if (own(row[d.rep_point[e]])) H.rep_ids.push_back((int32_t)e);
-        for (int64_t e = 0; e < D; e++) if (own(row[d.dep_point[e]])) H.dep_ids.push_back((int32_t)e);
+    if (!dev_edges) {
+        if (nranks == 1) {
+            H.rep_ids.resize((size_t)R);
+            std::iota(H.rep_ids.begin(), H.rep_ids.end(), 0);
+            H.dep_ids.resize((size_t)D);
+            std::iota(H.dep_ids.begin(), H.dep_ids.end(), 0);
+        } else {
+            for (int64_t e = 0; e < R; e++) if (own(row[d.rep_point[e]])) H.rep_ids.push_back((int32_t)e);
+            for (int64_t e = 0; e < D; e++) if (own(row[d.dep_point[e]])) H.dep_ids.push_back((int32_t)e);
+        }
+        par_counting_sort(H.rep_ids, P, [&](int32_t e) { return row[d.rep_point[e]]; });
+        par_counting_sort(H.dep_ids, P, [&](int32_t e) { return row[d.dep_point[e]]; });
+        H.rep_off.assign(nown + 1, 0);
+        H.dep_off.assign(nown + 1, 0);
+        for (int32_t e : H.rep_ids) H.rep_off[row[d.rep_point[e]] - lo_r + 1]++;
+        for (int32_t e : H.dep_ids) H.dep_off[row[d.dep_point[e]] - lo_r + 1]++;
+        for (int32_t l = 0; l < nown; l++) { H.rep_off[l + 1] += H.rep_off[l]; H.dep_off[l + 1] += H.dep_off[l]; }
     }
-    par_counting_sort(H.rep_ids, P, [&](int32_t e) { return row[d.rep_point[e]]; });
-    par_counting_sort(H.dep_ids, P, [&](int32_t e) { return row[d.dep_point[e]]; });
-    H.rep_off.assign(nown + 1, 0);
-    H.dep_off.assign(nown + 1, 0);
-    for (int32_t e : H.rep_ids) H.rep_off[row[d.rep_point[e]] - lo_r + 1]++;
-    for (int32_t e : H.dep_ids) H.dep_off[row[d.dep_point[e]] - lo_r + 1]++;
-    for (int32_t l = 0; l < nown; l++) { H.rep_off[l + 1] += H.rep_off[l]; H.dep_off[l + 1] += H.dep_off[l]; }
 
     stage("6 rep / depth by row");
     // 7. phase-1 blocks: ARAP (owned, then halo-only) per pair in runs of kSpBlock; depth edges by
@@ -523,8 +596,8 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
     // 8. own rows' ARAP incidences (local edge << 2 | role), each row's in local-edge order
     //    (a counting sort over chunks of local edges: per-chunk row counts, chunk-ordered offsets,
     //    every chunk scatters its edges in order — the sequential order)
-    H.inc_off.assign(nown + 1, 0);
-    {
+    if (!dev_edges) {
+        H.inc_off.assign(nown + 1, 0);
         constexpr int64_t kMin = 1 << 16;
         const int64_t nch = std::max<int64_t>(1, std::min<int64_t>(16, nloc / kMin));
         std::vector<std::vector<int32_t>> ccnt((size_t)nch);
@@ -685,27 +758,41 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
         // fused (one launch): q stays in registers, p in LDS — no q out / in, no (z, p) reload
     }
     static const bool digest = std::getenv("DEFTRI_PLAN_DIGEST") != nullptr;
-    if (digest) {
-        // FNV-1a over every plan array: a rewrite of the build is checked against the previous one
-        uint64_t h = 1469598103934665603ULL;
-        auto mix = [&](const void *v, size_t n) {
-            const unsigned char *c = (const unsigned char *)v;
-            for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ULL; }
-        };
-        auto vec = [&](const auto &x) { mix(x.data(), x.size() * sizeof(x[0])); };
-        vec(H.row_of_point); vec(H.point_of_row); vec(H.rank_row_begin); vec(H.arap_ids); vec(H.rep_ids);
-        vec(H.dep_ids); vec(H.rot_ids); vec(H.arap_rot_local); vec(H.blk); vec(H.hv_blk); vec(H.hv_blk_off);
-        vec(H.dperm); vec(H.inc_off); vec(H.inc); vec(H.rep_off); vec(H.dep_off); vec(H.rowmap); vec(H.woff);
-        vec(H.wsplit); vec(H.pmap); vec(H.pidx);
-        vec(H.tile_tab); vec(H.tile_m0); vec(H.tile_m1); vec(H.tile_chunk); vec(H.tile_rs); vec(H.tile_halo);
-        vec(H.tile_xoff); vec(H.tile_xdst);
-        for (const auto &x : H.send_rows) vec(x);
-        for (const auto &x : H.recv_rows) vec(x);
-        const int64_t sc[4] = {H.lo, H.hi, H.n_arap_owned, H.halo_rows};
-        mix(sc, sizeof(sc));
-        std::fprintf(stderr, "[deftri plan] digest %016llx\n", (unsigned long long)h);
+    // FNV-1a over every plan array (plan_digests): a rewrite of the build is checked against the previous one
+    if (digest) std::fprintf(stderr, "[deftri plan] digest %016llx\n", (unsigned long long)plan_digests(H, nullptr));
+    return kPlanOk;
+}
+
+bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
+                   bool tile) {
+    return build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr) == kPlanOk;
+}
+
+int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
+                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info) {
+    const auto t0 = std::chrono::steady_clock::now();
+    info = PlanBuildInfo();
+    auto done = [&](int rc) {
+        info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return rc;
+    };
+    // the condition of stage 4a's one-pair tile branch, and a device
+    const bool applies = mode == 1 && pd && nranks == 1 && d.n_pairs == 1 && d.n_scales <= 2 && d.n_arap > 0 &&
+                         d.n_arap < (1LL << 29) && tile;
+    if (mode == 1 && !applies) info.reason = 1;
+    if (applies) {
+        int32_t stages = 0;
+        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages);
+        if (rc == kPlanOk) {
+            info.builder_used = 1;
+            info.stages = stages;
+            return done(0);
+        }
+        if (rc == kPlanHip) return done(DEFTRI_E_HIP);
+        if (rc == kPlanBad) return done(DEFTRI_E_ARG);
+        info.reason = 2;                               // a bounded loop reached its bound: the whole build on the host
     }
-    return true;
+    return done(build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr) == kPlanOk ? 0 : DEFTRI_E_ARG);
 }
 
 // Host emulation of one sharded product q = (H + lambda I) p on this rank's plan, with the device

@@ -242,12 +242,17 @@ int SpSolver::upload(const deftri_problem_desc &d) {
                            (shard_ ? !sd_no_tile
                                    : !std::getenv("DEFTRI_SP_NO_FUSE") && !std::getenv("DEFTRI_SP_NO_MERGE") &&
                                          (ndof_ >= kSpMergeMinDof || std::getenv("DEFTRI_SP_MERGE")));
-    const bool planned = build_sp_plan(d, rank_, nranks_, fp32_jac != 0, H, err, want_tile);
+    // deftri_set_plan_builder: the sorts and scans of the one-pair tile plan on the device (plan_dev.hip) where
+    // they apply; its arena is the context's, so only its growth joins the old solver's release
+    PlanBuildInfo pbi;
+    const int plan_rc = build_sp_plan_with(d, rank_, nranks_, fp32_jac != 0, H, err, want_tile, plan_builder, plan_dev,
+                                           &before_alloc, pbi);
+    if (plan_build) *plan_build = pbi;
     if (before_alloc) {
         before_alloc();
         before_alloc = nullptr;
     }
-    if (!planned) return DEFTRI_E_ARG;
+    if (plan_rc) return plan_rc;
     const auto tu1 = std::chrono::steady_clock::now();
     struct Report {                 // DEFTRI_UPLOAD_TIMING=1: plan build vs the rest of the upload
         bool on; std::chrono::steady_clock::time_point a, b;

@@ -93,6 +93,10 @@ def load():
                                                  P(_abi.FeatureGrid), P(C.c_int32), P(C.c_int32), P(C.c_uint8)]),
         "deftri_delaunay2d": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(_abi.DelaunayReport)]),
         "deftri_set_mesh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_set_plan_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
+        "deftri_debug_plan_digest": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_uint64), C.c_int32,
+                                               P(C.c_int32)]),
         "deftri_debug_delaunay_still_valid": (C.c_int, [C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32)]),
         "deftri_debug_delaunay_sweep": (C.c_int, [C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(C.c_int32), P(C.c_int32)]),
         "deftri_search_with_projection": (C.c_int, [C.c_void_p, P(_abi.FeatureGrid), P(C.c_float), P(C.c_float), C.c_int32,
@@ -236,7 +240,15 @@ EXPORTED = [
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
     "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
+    "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest",
 ]
+
+# the arrays of deftri_debug_plan_digest, in its order; the combined digest follows them
+PLAN_DIGEST_NAMES = (
+    "row_of_point", "point_of_row", "rank_row_begin", "arap_ids", "rep_ids", "dep_ids", "rot_ids", "arap_rot_local",
+    "blk", "hv_blk", "hv_blk_off", "dperm", "inc_off", "inc", "rep_off", "dep_off", "rowmap", "woff", "wsplit", "pmap",
+    "pidx", "tile_tab", "tile_m0", "tile_m1", "tile_chunk", "tile_rs", "tile_halo", "tile_xoff", "tile_xdst",
+    "send_rows", "recv_rows", "scalars", "combined")
 
 
 def trian_method_code(method):
@@ -684,6 +696,29 @@ class Context:
         """Who triangulates a keyframe in the graph builds of this context (deftri_set_mesh_builder): 0 the host
         sweep (the default), 1 the star path of Context.delaunay.  The graph is the same bit for bit."""
         self._check(self.lib.deftri_set_mesh_builder(self.h, int(mode)))
+
+    def set_plan_builder(self, mode):
+        """Who builds the iterative plan at the next upload of this context (deftri_set_plan_builder): 0 the host
+        passes (default), 1 the device stages where they apply (one rank, one pair, the tile layout)."""
+        self._check(self.lib.deftri_set_plan_builder(self.h, int(mode)))
+
+    def plan_build_info(self):
+        """What the last iterative plan build did (deftri_plan_build_info): builder_used, stages (bit mask),
+        reason (0 none, 1 not applicable, 2 a bounded loop reached its bound), ms."""
+        used, stages, reason, ms = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.deftri_plan_build_info(self.h, C.byref(used), C.byref(stages), C.byref(reason), C.byref(ms)))
+        return dict(builder_used=used.value, stages=stages.value, reason=reason.value, ms=ms.value)
+
+    def debug_plan_digest(self, prob, mode, tile):
+        """(names, digests) of the plan an upload would build with builder `mode`, the tile layout requested or
+        not (deftri_debug_plan_digest): one FNV-1a digest per plan array, the combined digest last."""
+        d = prob.to_desc()
+        out = np.zeros(len(PLAN_DIGEST_NAMES), np.uint64)
+        n = C.c_int32()
+        self._check(self.lib.deftri_debug_plan_digest(self.h, C.byref(d), int(mode), int(tile),
+                                                      out.ctypes.data_as(C.POINTER(C.c_uint64)), len(out), C.byref(n)))
+        assert n.value == len(PLAN_DIGEST_NAMES), n.value
+        return PLAN_DIGEST_NAMES, [int(x) for x in out]
 
     def delaunay(self, xy, tris_cap=None):
         """The Delaunay triangulation of xy [n, 2] (deftri_delaunay2d) on this context: stars on the device, or on

@@ -1268,10 +1268,20 @@ int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode);
    equal array for array.  DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the
    upload with DEFTRI_E_HIP. */
 int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode);
+/* Who cuts the one-pair tile layout (build_tiles, csrc/spcg_tile.cpp) wherever plan builder 1's device stages
+   apply: 0 (default) the host; 1 the device stages of csrc/plan_dev.hip (groups and edges by group, the partition,
+   entries and slots, cross slots), which also keep the groups and the tile-entry edge order on the device between
+   the plan builder's stages.  The plan is equal array for array.  A graph build_tiles refuses (a keyframe-copy
+   group of more than 2 rows, an edge whose copies lie in two groups or inside one group, a vertex with more than
+   64 ARAP edges) is handed to the host's build_tiles after the device's rows, as with mode 0.  With plan
+   builder 0, on a host-only context or where the plan builder does not apply it has no effect.  DEFTRI_E_ARG: a
+   mode other than 0 or 1.  deftri_debug_plan_digest with mode 1 honours this setting. */
+int deftri_set_tile_builder(deftri_ctx *ctx, int32_t mode);
 /* What the last iterative plan build of this context did: builder_used 0 / 1; stages = bit mask of
    the stages that ran on the device (bit 0 groups, 1 Morton order, 2 rows, 3 rotation numbering,
-   4 rep/depth by row, 5 incidences; bits 0-2 alone: the tile layout was refused after them and the build
-   went on on the host); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
+   4 rep/depth by row, 5 incidences; with deftri_set_tile_builder(1) also 6 groups and edges by group,
+   7 partition, 8 entries and slots, 9 cross slots: 0x3ff for a full device build; bits 0-2 alone: the tile
+   layout was refused after them and the build went on on the host); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
    2 a bounded loop reached its bound); ms = wall time of the build.  All zero before the first build. */
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
                            int32_t *reason, double *ms);

@@ -1,7 +1,8 @@
 // plan_dev.h — the sorts, scans and first-occurrence numberings of the one-pair tile plan (spcg_plan.cpp
 // stages 1-3, 5, 6 and 8) on the device (plan_dev.hip).  Every stage has a unique output — a stable sort from
 // ascending ids, component roots that are the smallest id, a first-encounter numbering — so the arrays are the
-// host's bit for bit.
+// host's bit for bit.  With deftri_set_tile_builder the tile layout (spcg_tile.cpp build_tiles, stage 4a)
+// is built there too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -42,10 +43,19 @@ class PlanDevice {
     // kernels, one download.  before_alloc: called (and cleared) before the arena grows
     int rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
              std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-             std::string &err);
+             std::string &err, bool with_tiles = false);
     // stages 4-6 (rotation numbering, rep / depth edges by row, incidences) for H.arap_ids on the rows of the
     // last rows() call: one upload of arap_ids, the kernels, one download into H
     int edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &err);
+    // deftri_set_tile_builder: rows() with with_tiles lays out the tile stages' scratch and leaves gp on
+    // the device (gp comes back empty).  tiles() is build_tiles (spcg_tile.cpp) of one rank on the rows of the last
+    // rows() call: groups and edges by group, the partition, entries and slots, cross slots, then one download of
+    // the tile arrays and scalars into H and of the tile-entry order of the ARAP edges into `order`; edges() then
+    // takes arap_ids from the device.  units_max / lds_budget: the host's values (sp_tile_units, sp_tile_lds_budget).
+    // Returns 0, 1 (bound), -1 (err), or 2: build_tiles would refuse this graph — nothing of H is written and gp
+    // is downloaded for the host's build_tiles
+    int tiles(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
+              SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err);
 
  private:
     bool reserve(size_t dev_bytes, size_t pin_bytes, std::function<void()> *before_alloc);
@@ -54,15 +64,18 @@ class PlanDevice {
     void report(int first, int last, const char *const *names) const;
     int dev_;
     hipStream_t st_;
-    char *buf_ = nullptr, *pin_ = nullptr;
-    size_t cap_ = 0, pin_cap_ = 0;
-    hipEvent_t ev_[12] = {};
+    char *buf_ = nullptr, *pin_ = nullptr, *tbuf_ = nullptr;     // tbuf_: the tile arrays (sized after the counts)
+    size_t cap_ = 0, pin_cap_ = 0, tcap_ = 0;
+    hipEvent_t ev_[24] = {};
     // the arena's pieces (byte offsets), laid out by rows()
     struct Layout {
         size_t ap, rot, rep_point, dep_point, xy, par, root, flag, gid, grep, mm, lohi, key[2], id[2], hist, gpos, cur,
             part, dl1, hdr, por, rop, gp, dl1_end, aid, rv, first, rflag, kr, kd, ki, ioff, dl2, hdr2, rot_ids, arl, rep_ids,
-            rep_off, dep_ids, dep_off, inc, inc_off, dl2_end, total;
+            rep_off, dep_ids, dep_off, inc, inc_off, dl2_end,
+            // the tile stages' scratch (with_tiles)
+            egi, egj, erow, ooff, oe, okj, pred, tioff, ie, tend, ja, jb, mark, midx, tstart, tne, tnh, tcut, thdr, total;
     } L_{};
+    bool with_tiles_ = false, order_on_dev_ = false;           // order_on_dev_: tiles() left arap_ids in L_.oe
     int32_t P_ = 0;
     int64_t E_ = 0;
 };

@@ -1,4 +1,5 @@
-// plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h).
+// plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h), and
+// its tile layout (build_tiles of one rank).
 //
 // No workgroup waits on another: a scan over more than one workgroup's elements is three launches (tile sums,
 // the scan of the sums by one workgroup, the tiles' own scans), a sort by a dense key (a row, a group) is count,
@@ -28,7 +29,9 @@ constexpr int kRadixDigits = 1 << kPlanRadixBits;
 constexpr int kRadixPasses = 42 / kPlanRadixBits;
 static_assert(kRadixPasses * kPlanRadixBits == 42, "the passes cover the curve key exactly");
 static_assert(kPlanScanTile == 8 * kBlk && kPlanRadixTile == kBlk, "one workgroup per tile");
-enum { kHdrBound = 0, kHdrNg = 1, kHdrNrot = 2, kHdrWords = 16 };
+enum { kHdrBound = 0, kHdrNg = 1, kHdrNrot = 2, kHdrWords = 16,
+       // the tile stages' header: a condition build_tiles refuses, tiles, padded entries, halo rows, cut entries
+       kHdrRefuse = 3, kHdrNt = 4, kHdrEntries = 5, kHdrHalo = 6, kHdrCut = 7, kHdrSegmax = 8, kHdrLds = 9 };
 
 namespace dev {
 
@@ -336,6 +339,324 @@ __global__ __launch_bounds__(kBlk) void k_widen(int64_t n, const int *in, int64_
     PLAN_FOR(i, n) out[i] = in[i];
 }
 
+// ---- the tile layout (build_tiles of one rank, spcg_tile.cpp) ----------------------------
+// hdr: the tile stages' header.  A kernel that finds a condition build_tiles refuses sets kHdrRefuse; every later
+// kernel returns at once when the header holds a refusal or a reached bound, so none of them sees a group of more
+// than 2 rows, an edge inside one group, more than 64 out-edges or more than kPlanRunMax in-edges of a group.
+// start: the groups' first rows (stage 3's offsets; the rows of a group are consecutive), P for the keys past ng
+__device__ inline bool tile_stop(const int *hdr) { return (hdr[kHdrBound] | hdr[kHdrRefuse]) != 0; }
+
+__global__ __launch_bounds__(kBlk) void k_tile_groups(int ng, const int *start, int *hdr) {
+    PLAN_FOR(g, ng) if (start[g + 1] - start[g] > 2) hdr[kHdrRefuse] = 1;
+}
+
+__global__ __launch_bounds__(kBlk) void k_tile_edges(int64_t E, const int4 *ap, const int *gp, const int *rop, int *egi, int *egj,
+                                                    int4 *erow, int *hdr) {
+    PLAN_FOR(e, E) {
+        const int4 v = ap[e];
+        const int gi = gp[v.x], gj = gp[v.z];
+        egi[e] = gi;
+        egj[e] = gj;
+        erow[e] = make_int4(rop[v.x], rop[v.y], rop[v.z], rop[v.w]);
+        if (gi != gp[v.y] || gj != gp[v.w] || gi == gj) hdr[kHdrRefuse] = 1;
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void k_tile_deg(int ng, const int *ooff, int *hdr) {
+    PLAN_FOR(g, ng) if (ooff[g + 1] - ooff[g] > 64) hdr[kHdrRefuse] = 1;
+}
+
+// per out-edge k (the order (gi, e)): its j group, and pred: the largest group below gi with an out-edge to the
+// same gj, gi itself when an earlier edge of gi goes there, else -1.  An edge is the first of the groups [a, gi]
+// to reach gj exactly when pred < a.  ie: the in-edges of a group, by (gj, e)
+__global__ __launch_bounds__(kBlk) void k_tile_pred(int64_t E, const int *oe, const int *egi, const int *egj, const int *ioff,
+                                                   const int *ie, int *okj, int *pred, const int *hdr) {
+    if (tile_stop(hdr)) return;
+    PLAN_FOR(k, E) {
+        const int e = oe[k], gi = egi[e], gj = egj[e];
+        int p = -1;
+        const int a = ioff[gj], b = min(ioff[gj + 1], a + kPlanRunMax);
+        for (int x = a; x < b; x++) {
+            const int f = ie[x], gf = egi[f];
+            if (gf < gi) p = max(p, gf);
+            else if (gf == gi && f < e) p = gi;
+        }
+        okj[k] = gj;
+        pred[k] = p;
+    }
+}
+
+// the greedy cut from every start: tend[gs] = the first group the tile begun at gs does not take (build_tiles'
+// loop; whether [gs, g] fits is a function of that set of groups alone).  At most umax + 1 steps
+__global__ __launch_bounds__(kBlk) void k_tile_end(int ng, const int *start, const int *ooff, const int *okj, const int *pred,
+                                                  const int *ioff, const int *ie, const int *egi, int umax, int budget, int fixed,
+                                                  int *tend, const int *hdr) {
+    if (tile_stop(hdr)) return;
+    PLAN_FOR(gs64, (int64_t)ng + 1) {
+        const int gs = (int)gs64;
+        if (gs == ng) { tend[gs] = ng; continue; }
+        int nr = 0, nh = 0, ns = 0, units = 0, g = gs;
+        for (int step = 0; step <= umax && g < ng; step++) {
+            const int sz = start[g + 1] - start[g];
+            int dnh = 0, dns = 0;
+            bool was_halo = false;
+            for (int k = ooff[g]; k < ooff[g + 1]; k++) {
+                const int gj = okj[k];
+                if (gj >= gs && gj < g) dns += 2;
+                else if (pred[k] < gs) dnh += start[gj + 1] - start[gj];
+            }
+            for (int x = ioff[g]; x < ioff[g + 1]; x++) {
+                const int gi = egi[ie[x]];
+                if (gi >= gs && gi < g) { dns += 2; was_halo = true; }
+            }
+            if (was_halo) dnh -= sz;
+            const bool fits = units + 1 <= umax && 24 * (nr + sz + nh + dnh) + 24 * (nr + sz) + 24 * (ns + dns) + fixed <= budget &&
+                              nr + sz + nh + dnh < 4096 && ns + dns < 4096;
+            if (!fits && units > 0) break;
+            nr += sz; nh += dnh; ns += dns;
+            units++;
+            g++;
+        }
+        tend[gs] = g;
+    }
+}
+
+// one round of pointer doubling over the nodes 0 .. ng: jin = end^(2^r).  A marked node marks its jin; every mark
+// is on the chain 0, end(0), end(end(0)), ... whichever round's marks a thread happens to see
+__global__ __launch_bounds__(kBlk) void k_tile_jump(int64_t n, const int *jin, int *jout, int *mark, const int *hdr) {
+    if (tile_stop(hdr)) return;
+    PLAN_FOR(g, n) {
+        const int j = jin[g];
+        if (mark[g]) mark[j] = 1;
+        jout[g] = jin[j];
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void k_tile_midx(int ng, const int *mark, int *midx) {
+    PLAN_FOR(g, (int64_t)ng + 1) midx[g] = g < ng ? mark[g] : 0;
+}
+
+// midx: the exclusive scan of the marks (ng + 1 entries)
+__global__ __launch_bounds__(kBlk) void k_tile_tstart(int ng, const int *mark, const int *midx, int *tstart, int *hdr) {
+    if (tile_stop(hdr)) return;
+    PLAN_FOR(g, (int64_t)ng + 1) {
+        if (g == ng) { tstart[midx[ng]] = ng; hdr[kHdrNt] = midx[ng]; }
+        else if (mark[g]) tstart[midx[g]] = (int)g;
+    }
+}
+
+// the entries of a tile's groups under the chunk rule (a unit never straddles a 64-entry chunk), by one thread:
+// gst[i] = the first entry of group g0 + i inside the tile; returns the padded entry count, *segmax the longest unit
+__device__ inline int tile_entry_layout(int g0, int g1, const int *ooff, int *gst, int *segmax) {
+    int fill = 0, sm = 1;
+    for (int g = g0; g < g1 && g - g0 < 128; g++) {
+        const int cnt = ooff[g + 1] - ooff[g];
+        if (cnt > 0 && fill % 64 + cnt > 64) fill = (fill + 63) & ~63;
+        if (gst) gst[g - g0] = fill;
+        fill += cnt;
+        sm = max(sm, cnt);
+    }
+    *segmax = sm;
+    return fill == 0 ? 64 : (fill + 63) & ~63;
+}
+
+// per tile: padded entries, halo rows, cut entries; segmax and the LDS maximum
+__global__ __launch_bounds__(kBlk) void k_tile_count(const int *tstart, const int *start, const int *ooff, const int *okj,
+                                                    const int *pred, int fixed, int *tne, int *tnh, int *tcut, int *hdr) {
+    __shared__ int s_cut, s_nh;
+    if (tile_stop(hdr)) return;
+    const int nt = hdr[kHdrNt];
+    for (int t = blockIdx.x; t < nt; t += gridDim.x) {
+        const int g0 = tstart[t], g1 = tstart[t + 1], k0 = ooff[g0], k1 = ooff[g1];
+        if (threadIdx.x == 0) { s_cut = 0; s_nh = 0; }
+        __syncthreads();
+        int cut = 0, nh = 0;
+        for (int k = k0 + threadIdx.x; k < k1; k += blockDim.x) {
+            const int gj = okj[k];
+            if (gj < g0 || gj >= g1) {
+                cut++;
+                if (pred[k] < g0) nh += start[gj + 1] - start[gj];
+            }
+        }
+        if (cut) atomicAdd(&s_cut, cut);
+        if (nh) atomicAdd(&s_nh, nh);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int segmax;
+            const int ne = tile_entry_layout(g0, g1, ooff, nullptr, &segmax);
+            const int nr = start[g1] - start[g0], ns = 2 * (k1 - k0 - s_cut);
+            tne[t] = ne;
+            tnh[t] = s_nh;
+            tcut[t] = s_cut;
+            atomicMax(&hdr[kHdrSegmax], segmax);
+            atomicMax(&hdr[kHdrLds], 24 * (nr + s_nh) + 24 * nr + 24 * ns + fixed);
+            if (g1 - g0 > 128 || nr > 256) hdr[kHdrBound] = 1;      // (never: the cut takes at most 128 groups of 2 rows)
+        }
+        __syncthreads();
+    }
+}
+
+// tne, tnh, tcut: exclusive scans over ng + 1 entries (zeros past nt), so entry ng holds the total
+__global__ void k_tile_totals(int ng, const int *tne, const int *tnh, const int *tcut, int *hdr) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hdr[kHdrEntries] = tne[ng];
+        hdr[kHdrHalo] = tnh[ng];
+        hdr[kHdrCut] = tcut[ng];
+    }
+}
+
+constexpr int kTileHaloMax = 4096;      // halo groups of one tile at most (rows + halo rows < 4096)
+
+struct TileOut {
+    int *tab, *chunk, *rs, *halo, *xrow;
+    uint32_t *m0, *m1;
+};
+
+// one workgroup per tile: build_tiles' second stage as :338-468 writes it.  tne, tnh, tcut: the tiles' bases
+__global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int *start, const int *gp, const int *por,
+                                                   const int *ooff, const int *oe, const int *okj, const int *pred, const int *ioff,
+                                                   const int *ie, const int *egi, const int4 *erow, const int *tne, const int *tnh,
+                                                   const int *tcut, TileOut o, int *hdr, const int *hdr_in) {
+    __shared__ int hl[kTileHaloMax], hs[kTileHaloMax], ho[kTileHaloMax];   // halo groups << 2 | rows: found, sorted; row offsets
+    __shared__ int gst[128], rsb[kBlk], sc[kBlk];
+    __shared__ int s_hn, s_ne;
+    if (tile_stop(hdr_in)) return;
+    const int nt = hdr_in[kHdrNt];
+    const int tid = threadIdx.x;
+    for (int t = blockIdx.x; t < nt; t += gridDim.x) {
+        const int g0 = tstart[t], g1 = tstart[t + 1], k0 = ooff[g0], k1 = ooff[g1];
+        const int r0 = start[g0], nr = start[g1] - r0;
+        const int e0 = tne[t], h0 = tnh[t], x0 = 2 * tcut[t];
+        if (tid == 0) {
+            int segmax;
+            s_ne = tile_entry_layout(g0, g1, ooff, gst, &segmax);
+            s_hn = 0;
+        }
+        __syncthreads();
+        const int ne = s_ne;
+        // every entry a padding entry first (its own empty segment); the valid ones are written after the barrier
+        for (int i = tid; i < ne; i += kBlk) { o.m0[e0 + i] = kTmHead; o.m1[e0 + i] = 0; }
+        // the halo groups: the first out-edge of the tile to each group outside it
+        for (int k = k0 + tid; k < k1; k += kBlk) {
+            const int gj = okj[k];
+            if ((gj < g0 || gj >= g1) && pred[k] < g0) {
+                const int i = atomicAdd(&s_hn, 1);
+                if (i < kTileHaloMax) hl[i] = gj << 2 | (start[gj + 1] - start[gj]);
+            }
+        }
+        __syncthreads();
+        const int hn = s_hn;
+        if (hn > kTileHaloMax) {                          // (never: the partition keeps rows + halo rows below 4096)
+            if (tid == 0) hdr[kHdrBound] = 1;
+            __syncthreads();
+            continue;
+        }
+        // ascending and unique: a group's place is the number of smaller ones, its first LDS row their rows
+        for (int i = tid; i < hn; i += kBlk) {
+            const int v = hl[i];
+            int r = 0, rows = 0;
+            for (int j = 0; j < hn; j++) {
+                const int u = hl[j];
+                if (u < v) { r++; rows += u & 3; }
+            }
+            hs[r] = v;
+            ho[r] = rows;
+        }
+        // the own rows' slot counts: the in-edges of the row's group from the tile's groups that aim at the row
+        int cnt = 0;
+        if (tid < nr) {
+            const int R = r0 + tid, g = gp[por[R]];
+            for (int x = ioff[g]; x < ioff[g + 1]; x++) {
+                const int f = ie[x], gf = egi[f];
+                if (gf >= g0 && gf < g1) {
+                    const int4 w = erow[f];
+                    cnt += (w.z == R) + (w.w == R);
+                }
+            }
+        }
+        int ns;
+        const int sb = block_excl_scan(cnt, sc, &ns);     // (its barriers order hs / ho and the padding stores too)
+        rsb[tid] = sb;
+        if (tid < nr) {
+            o.rs[r0 + tid] = sb | cnt << 16;
+            if (cnt > 0xffff) hdr[kHdrRefuse] = 1;        // (never: a group has at most kPlanRunMax in-edges)
+        }
+        __syncthreads();
+        int nh = 0;
+        if (hn > 0) nh = ho[hn - 1] + (hs[hn - 1] & 3);
+        for (int r = tid; r < hn; r += kBlk) {
+            const int gj = hs[r] >> 2, sz = hs[r] & 3;
+            for (int c = 0; c < sz; c++) o.halo[h0 + ho[r] + c] = start[gj] + c;
+        }
+        // the entries, 256 consecutive out-edges at a time: the cut entries before each are a scan with a carry
+        int carry = 0;
+        for (int kb = k0; kb < k1; kb += kBlk) {
+            const int k = kb + tid;
+            const bool valid = k < k1;
+            int gj = 0;
+            bool cut = false;
+            if (valid) { gj = okj[k]; cut = gj < g0 || gj >= g1; }
+            int tot;
+            const int before = carry + block_excl_scan(cut ? 1 : 0, sc, &tot);
+            carry += tot;
+            if (!valid) continue;
+            const int e = oe[k], g = egi[e];
+            const int4 w = erow[e];
+            const int pos = gst[g - g0] + (k - ooff[g]);
+            const int ub = start[g] - r0;
+            uint32_t w0 = kTmValid, w1 = (uint32_t)ub << 24;
+            if (w.x - r0 == ub + 1) w0 |= kTmSwap;
+            if (k == ooff[g]) w0 |= kTmHead;
+            if (k == ooff[g + 1] - 1) w0 |= kTmLast;
+            if (cut) {
+                int lo = 0, hi = hn;                      // the place of gj among the halo groups
+                const int key = gj << 2;
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if ((hs[mid] & ~3) < key) lo = mid + 1; else hi = mid;
+                }
+                lo = min(lo, hn - 1);                     // (gj is among them: some edge of the tile was the first to reach it)
+                const int lrow = nr + ho[lo] - start[gj];
+                w0 |= (uint32_t)(lrow + w.z) | (uint32_t)(lrow + w.w) << 12 | kTmCut;
+                const int x = x0 + 2 * before;
+                o.xrow[x] = w.z;
+                o.xrow[x + 1] = w.w;
+            } else {
+                // the slot an in-tile entry takes on a row of j: its rank among the (entry, which) aimed at that
+                // row in entry order — the order (gi, e), then p1_j before p2_j
+                int rk0 = 0, rk1 = 0;
+                for (int x = ioff[gj]; x < ioff[gj + 1]; x++) {
+                    const int f = ie[x], gf = egi[f];
+                    if (gf < g0 || gf >= g1) continue;
+                    const int4 v = erow[f];
+                    const bool earlier = gf < g || (gf == g && f < e);
+                    if (earlier) {
+                        rk0 += (v.z == w.z) + (v.w == w.z);
+                        rk1 += (v.z == w.w) + (v.w == w.w);
+                    } else if (f == e) {
+                        rk1 += w.z == w.w;
+                    }
+                }
+                const int s0 = rsb[w.z - r0] + rk0, s1 = rsb[w.w - r0] + rk1;
+                w0 |= (uint32_t)(w.z - r0) | (uint32_t)(w.w - r0) << 12;
+                w1 |= (uint32_t)s0 | (uint32_t)s1 << 12;
+            }
+            o.m0[e0 + pos] = w0;
+            o.m1[e0 + pos] = w1;
+            if (pos % 64 == 0) {
+                o.chunk[2 * ((e0 + pos) / 64)] = k;
+                o.chunk[2 * ((e0 + pos) / 64) + 1] = x0 + 2 * before;
+            }
+        }
+        if (tid == 0) {
+            if (k0 == k1) { o.chunk[2 * (e0 / 64)] = k0; o.chunk[2 * (e0 / 64) + 1] = x0; }
+            int *T = o.tab + 8 * (int64_t)t;
+            T[0] = r0; T[1] = nr; T[2] = nh; T[3] = e0; T[4] = ne; T[5] = h0; T[6] = ns; T[7] = 0;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace dev
 
 unsigned grid_for(int64_t n, int per_block = kBlk) {
@@ -358,9 +679,10 @@ const bool g_timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     } while (0)
 
 PlanDevice::~PlanDevice() {
-    if (!buf_ && !pin_ && !ev_[0]) return;
+    if (!buf_ && !pin_ && !tbuf_ && !ev_[0]) return;
     hipSetDevice(dev_);
     if (buf_) hipFree(buf_);
+    if (tbuf_) hipFree(tbuf_);
     if (pin_) hipHostFree(pin_);
     for (hipEvent_t e : ev_) if (e) hipEventDestroy(e);
 }
@@ -425,8 +747,10 @@ void PlanDevice::report(int first, int last, const char *const *names) const {
 
 int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
                      std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-                     std::string &err) {
+                     std::string &err, bool with_tiles) {
     hipSetDevice(dev_);
+    with_tiles_ = with_tiles;
+    order_on_dev_ = false;
     const int32_t P = d.n_points, NR = std::max(d.n_rot, 1);
     const int64_t E = d.n_arap, R = d.n_rep, D = d.n_depth;
     const size_t Pz = (size_t)P, Ez = (size_t)E;
@@ -457,6 +781,13 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         L.rep_ids = piece(4 * (size_t)R); L.rep_off = piece(4 * (Pz + 1)); L.dep_ids = piece(4 * (size_t)D);
         L.dep_off = piece(4 * (Pz + 1)); L.inc = piece(16 * Ez); L.inc_off = piece(8 * (Pz + 1));
         L.dl2_end = o;
+        if (with_tiles) {
+            L.egi = piece(4 * Ez); L.egj = piece(4 * Ez); L.erow = piece(16 * Ez); L.ooff = piece(4 * (Pz + 1)); L.oe = piece(4 * Ez);
+            L.okj = piece(4 * Ez); L.pred = piece(4 * Ez); L.tioff = piece(4 * (Pz + 1)); L.ie = piece(4 * Ez);
+            L.tend = piece(4 * (Pz + 1)); L.ja = piece(4 * (Pz + 1)); L.jb = piece(4 * (Pz + 1)); L.mark = piece(4 * (Pz + 2));
+            L.midx = piece(4 * (Pz + 2)); L.tstart = piece(4 * (Pz + 2)); L.tne = piece(4 * (Pz + 2)); L.tnh = piece(4 * (Pz + 2));
+            L.tcut = piece(4 * (Pz + 2)); L.thdr = piece(4 * kHdrWords);
+        }
         L.total = o;
     }
     const Layout &L = L_;
@@ -514,7 +845,8 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     sort_by_row(P, d_gp, P, d_start, d_por, d_hdr);
     LAUNCH(k_inverse, P, (int64_t)P, (const int *)d_por, d_rop);
     hipEventRecord(ev_[4], st_);
-    hipMemcpyAsync(pin_, B + L.dl1, L.dl1_end - L.dl1, hipMemcpyDeviceToHost, st_);
+    // (gp is the region's last piece: the tile stages read it on the device, so it stays there)
+    hipMemcpyAsync(pin_, B + L.dl1, (with_tiles ? L.gp : L.dl1_end) - L.dl1, hipMemcpyDeviceToHost, st_);
     hipEventRecord(ev_[5], st_);
     hipError_t e = hipStreamSynchronize(st_);
     if (e == hipSuccess) e = hipGetLastError();
@@ -536,7 +868,8 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
                   *gpp = (const int32_t *)(pin_ + (L.gp - L.dl1));
     point_of_row.assign(por, por + P);
     row_of_point.assign(rop, rop + P);
-    gp.assign(gpp, gpp + P);
+    if (with_tiles) gp.clear();
+    else gp.assign(gpp, gpp + P);
     return 0;
 }
 
@@ -562,7 +895,8 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
     int64_t *d_inc_off = (int64_t *)(B + L.inc_off);
 
     hipEventRecord(ev_[6], st_);
-    hipMemcpyAsync(d_aid, H.arap_ids.data(), 4 * (size_t)nloc, hipMemcpyHostToDevice, st_);
+    if (order_on_dev_ && nloc == E) hipMemcpyAsync(d_aid, B + L.oe, 4 * (size_t)nloc, hipMemcpyDeviceToDevice, st_);
+    else hipMemcpyAsync(d_aid, H.arap_ids.data(), 4 * (size_t)nloc, hipMemcpyHostToDevice, st_);
     hipEventRecord(ev_[7], st_);
     // 4. rotation rows numbered in first-encounter order over the positions 2 le + k
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
@@ -619,6 +953,178 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
     take(H.inc, L.inc, (size_t)n4);
     take(H.inc_off, L.inc_off, (size_t)P + 1);
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> plan arrays", ms_since(t0));
+    return 0;
+}
+
+int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
+                      SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err) {
+    hipSetDevice(dev_);
+    const Layout &L = L_;
+    const int32_t P = P_;
+    const int64_t E = E_;
+    if (!buf_ || !with_tiles_ || P != d.n_points || E != d.n_arap || ng < 1 || ng > P) {
+        err = "plan builder: tiles() without the rows of this problem";
+        return -1;
+    }
+    char *B = buf_;
+    const int *d_ap = (const int *)(B + L.ap), *d_start = (const int *)(B + L.flag), *d_gp = (const int *)(B + L.gp),
+              *d_rop = (const int *)(B + L.rop), *d_por = (const int *)(B + L.por);
+    int *d_egi = (int *)(B + L.egi), *d_egj = (int *)(B + L.egj), *d_erow = (int *)(B + L.erow), *d_ooff = (int *)(B + L.ooff),
+        *d_oe = (int *)(B + L.oe), *d_okj = (int *)(B + L.okj), *d_pred = (int *)(B + L.pred), *d_ioff = (int *)(B + L.tioff),
+        *d_ie = (int *)(B + L.ie), *d_tend = (int *)(B + L.tend), *d_ja = (int *)(B + L.ja), *d_jb = (int *)(B + L.jb),
+        *d_mark = (int *)(B + L.mark), *d_midx = (int *)(B + L.midx), *d_tstart = (int *)(B + L.tstart), *d_tne = (int *)(B + L.tne),
+        *d_tnh = (int *)(B + L.tnh), *d_tcut = (int *)(B + L.tcut), *d_hdr = (int *)(B + L.thdr);
+    const int64_t nodes = (int64_t)ng + 1;
+    const dim3 tgrid((unsigned)std::min(ng, kGridMax));
+
+    hipEventRecord(ev_[12], st_);
+    // a. groups and edges by group: the out-edges by (gi, e), the in-edges by (gj, e)
+    hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
+    LAUNCH(k_tile_groups, ng, ng, d_start, d_hdr);
+    LAUNCH(k_tile_edges, E, E, (const int4 *)d_ap, d_gp, d_rop, d_egi, d_egj, (int4 *)d_erow, d_hdr);
+    sort_by_row(E, d_egi, ng, d_ooff, d_oe, d_hdr);
+    LAUNCH(k_tile_deg, ng, ng, (const int *)d_ooff, d_hdr);
+    sort_by_row(E, d_egj, ng, d_ioff, d_ie, d_hdr);
+    LAUNCH(k_tile_pred, E, E, (const int *)d_oe, (const int *)d_egi, (const int *)d_egj, (const int *)d_ioff, (const int *)d_ie, d_okj,
+           d_pred, (const int *)d_hdr);
+    hipEventRecord(ev_[13], st_);
+    // b. partition: the cut from every start, the chain from group 0 marked by pointer doubling and compacted
+    LAUNCH(k_tile_end, nodes, ng, d_start, (const int *)d_ooff, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
+           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr);
+    hipMemsetAsync(d_mark, 0, 4 * ((size_t)ng + 2), st_);
+    LAUNCH(k_fill, 1, (int64_t)1, d_mark, 1);
+    {
+        int rounds = 1;
+        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
+        const int *jin = d_tend;
+        int *jout = d_ja;
+        for (int r = 0; r < rounds; r++) {
+            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, d_mark, (const int *)d_hdr);
+            jin = jout;
+            jout = jout == d_ja ? d_jb : d_ja;
+        }
+    }
+    LAUNCH(k_tile_midx, nodes, ng, (const int *)d_mark, d_midx);
+    scan(d_midx, nodes);
+    LAUNCH(k_tile_tstart, nodes, ng, (const int *)d_mark, (const int *)d_midx, d_tstart, d_hdr);
+    hipEventRecord(ev_[14], st_);
+    // c (counts). per tile its padded entries, halo rows and cut entries; their scans are the tiles' bases
+    hipMemsetAsync(d_tne, 0, 4 * ((size_t)ng + 1), st_);
+    hipMemsetAsync(d_tnh, 0, 4 * ((size_t)ng + 1), st_);
+    hipMemsetAsync(d_tcut, 0, 4 * ((size_t)ng + 1), st_);
+    hipLaunchKernelGGL(dev::k_tile_count, tgrid, dim3(kBlk), 0, st_, (const int *)d_tstart, d_start, (const int *)d_ooff,
+                       (const int *)d_okj, (const int *)d_pred, (int)kSpTileLdsFixed, d_tne, d_tnh, d_tcut, d_hdr);
+    scan(d_tne, nodes);
+    scan(d_tnh, nodes);
+    scan(d_tcut, nodes);
+    hipLaunchKernelGGL(dev::k_tile_totals, dim3(1), dim3(64), 0, st_, ng, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut,
+                       d_hdr);
+    hipEventRecord(ev_[15], st_);
+    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[16], st_);
+    hipError_t e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names1[] = {"dev 4a groups, edges by group", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
+    report(12, 16, names1);
+    int hdr[kHdrWords];
+    std::memcpy(hdr, pin_, sizeof(hdr));
+    if (hdr[kHdrRefuse]) {
+        // build_tiles refuses this graph (with its own reason): it runs on the host from these rows, and needs gp
+        hipMemcpyAsync(pin_, d_gp, 4 * (size_t)P, hipMemcpyDeviceToHost, st_);
+        e = hipStreamSynchronize(st_);
+        if (e != hipSuccess) {
+            err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
+            return -1;
+        }
+        gp.assign((const int32_t *)pin_, (const int32_t *)pin_ + P);
+        return 2;
+    }
+    if (hdr[kHdrBound]) return 1;
+    const int32_t nt = hdr[kHdrNt];
+    const int64_t ne = hdr[kHdrEntries], nhr = hdr[kHdrHalo], nx = 2 * (int64_t)hdr[kHdrCut];
+    if (nt < 1 || nt > ng || ne < 64 * (int64_t)nt || ne % 64 || ne > 2 * E + 64 * (int64_t)nt || nhr < 0 || nhr > 2 * E || nx < 0 ||
+        nx > 2 * E) {
+        err = "plan builder: the device wrote impossible tile counts";
+        return -1;
+    }
+    // the tile arrays: one download region (header, tile arrays, the edge order), then the cross slots' scratch
+    const size_t Pz = (size_t)P;
+    size_t o = 0;
+    auto piece = [&](size_t bytes) { const size_t at = o; o += pad(bytes); return at; };
+    const size_t o_hdr = piece(4 * kHdrWords), o_tab = piece(32 * (size_t)nt), o_m0 = piece(4 * (size_t)ne), o_m1 = piece(4 * (size_t)ne),
+                 o_chunk = piece(8 * (size_t)(ne / 64)), o_rs = piece(4 * Pz), o_halo = piece(4 * (size_t)nhr),
+                 o_xoff = piece(4 * (Pz + 1)), o_xdst = piece(4 * (size_t)nx), o_order = piece(4 * (size_t)E);
+    const size_t dl = o;
+    const size_t o_xrow = piece(4 * (size_t)nx), o_xs = piece(4 * (size_t)nx);
+    if ((o > tcap_ || dl > pin_cap_) && before_alloc && *before_alloc) {
+        (*before_alloc)();
+        *before_alloc = nullptr;
+    }
+    if (o > tcap_) {
+        if (tbuf_) hipFree(tbuf_);
+        tbuf_ = nullptr; tcap_ = 0;
+        const size_t want = o + o / 4;
+        if (hipMalloc((void **)&tbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
+        tcap_ = want;
+    }
+    if (!reserve(cap_, dl, nullptr)) { err = "plan builder: allocation failed"; return -1; }
+    char *T = tbuf_;
+    int *d_hdr3 = (int *)(T + o_hdr), *d_xoff = (int *)(T + o_xoff), *d_xdst = (int *)(T + o_xdst), *d_xs = (int *)(T + o_xs);
+    dev::TileOut out;
+    out.tab = (int *)(T + o_tab); out.chunk = (int *)(T + o_chunk); out.rs = (int *)(T + o_rs); out.halo = (int *)(T + o_halo);
+    out.xrow = (int *)(T + o_xrow); out.m0 = (uint32_t *)(T + o_m0); out.m1 = (uint32_t *)(T + o_m1);
+    hipEventRecord(ev_[17], st_);
+    // c. entries and slots, one workgroup per tile
+    hipMemsetAsync(d_hdr3, 0, 4 * kHdrWords, st_);
+    hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)d_tstart, d_start, d_gp,
+                       d_por, (const int *)d_ooff, (const int *)d_oe, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
+                       (const int *)d_ie, (const int *)d_egi, (const int4 *)d_erow, (const int *)d_tne, (const int *)d_tnh,
+                       (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr);
+    hipEventRecord(ev_[18], st_);
+    // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
+    sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3);
+    LAUNCH(k_inverse, nx, nx, (const int *)d_xs, d_xdst);
+    hipMemcpyAsync(T + o_order, d_oe, 4 * (size_t)E, hipMemcpyDeviceToDevice, st_);
+    hipEventRecord(ev_[19], st_);
+    hipMemcpyAsync(pin_, T, dl, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[20], st_);
+    e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names2[] = {"dev 4a entries, slots", "dev 4a cross slots", "dev download tiles"};
+    report(17, 20, names2);
+    const int *hdr3 = (const int *)(pin_ + o_hdr);
+    if (hdr3[kHdrBound] || hdr3[kHdrRefuse]) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto take = [&](auto &v, size_t off, size_t n) {
+        using V = typename std::remove_reference<decltype(v)>::type::value_type;
+        const V *p = (const V *)(pin_ + off);
+        v.assign(p, p + n);
+    };
+    take(H.tile_tab, o_tab, 8 * (size_t)nt);
+    take(H.tile_m0, o_m0, (size_t)ne);
+    take(H.tile_m1, o_m1, (size_t)ne);
+    take(H.tile_chunk, o_chunk, 2 * (size_t)(ne / 64));
+    take(H.tile_rs, o_rs, Pz);
+    take(H.tile_halo, o_halo, (size_t)nhr);
+    take(H.tile_xoff, o_xoff, Pz + 1);
+    take(H.tile_xdst, o_xdst, (size_t)nx);
+    take(order, o_order, (size_t)E);
+    H.ntile = nt;
+    H.tile_entries = ne;
+    H.tile_cross = nx;
+    H.tile_segmax = std::max(1, hdr[kHdrSegmax]);
+    H.tile_lds = hdr[kHdrLds];
+    H.tile_halo_rows = nhr;
+    order_on_dev_ = true;
+    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
     return 0;
 }
 

@@ -127,6 +127,7 @@ struct deftri_ctx {
     int mesh_builder = 0;                   // deftri_set_mesh_builder
     std::unique_ptr<PlanDevice> pdev;       // the plan builder's device arena and pinned staging (plan_dev.hip)
     int plan_builder = 0;                   // deftri_set_plan_builder
+    int tile_builder = 0;                   // deftri_set_tile_builder
     PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
@@ -1226,6 +1227,13 @@ int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode) {
     return 0;
 }
 
+int deftri_set_tile_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_tile_builder: mode is 0 (build_tiles on the host) or 1 (device stages)");
+    ctx->tile_builder = mode;
+    return 0;
+}
+
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages, int32_t *reason, double *ms) {
     if (!ctx || !builder_used || !stages || !reason || !ms) return DEFTRI_E_ARG;
     *builder_used = ctx->plan_build.builder_used;
@@ -1246,7 +1254,7 @@ int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, i
     SpPlanHost H;
     std::string err;
     rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
-                            mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build);
+                            mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build, ctx->tile_builder);
     if (rc) return fail(ctx, rc, err);
     std::vector<uint64_t> each;
     const uint64_t all = plan_digests(H, &each);
@@ -1620,6 +1628,7 @@ int deftri_problem_upload(deftri_ctx *ctx, const deftri_problem_desc *desc) {
         ctx->sp->fp32_jac = ctx->jac_fp32;
         ctx->sp->before_alloc = [ctx] { join_reaper(ctx); };
         ctx->sp->plan_builder = ctx->plan_builder;
+        ctx->sp->tile_builder = ctx->tile_builder;
         ctx->sp->plan_dev = ctx->plan_builder ? plan_device(ctx) : nullptr;
         ctx->sp->plan_build = &ctx->plan_build;
         rc = ctx->sp->upload(*desc);

@@ -160,6 +160,11 @@ __host__ __device__ inline uint64_t curve_key(double x, double y, const double l
     return m;
 }
 
+// the tile cut's limits, read once: units per tile (DEFTRI_SP_TILE_UNITS, 8 .. 128) and the LDS budget
+// (DEFTRI_SP_TILE_LDS) — one place for the host's build_tiles and the device's (plan_dev.hip)
+int sp_tile_units();
+int64_t sp_tile_lds_budget();
+
 struct TileInput {
     int32_t P = 0, ng = 0;
     int64_t E = 0;
@@ -194,9 +199,11 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // where they apply (one rank, one pair, at most two scales, ARAP edges, the tile layout requested, pd not null)
 // and the host passes elsewhere; info says what ran.  Returns 0, DEFTRI_E_ARG (err) when the problem cannot be
 // planned, DEFTRI_E_HIP (err) after a HIP error in the builder.  before_alloc (may be null): called and cleared
-// before the builder's arena grows
+// before the builder's arena grows.  tile_mode (deftri_set_tile_builder) 1: where mode 1 applies, build_tiles on
+// `pd` as well (PlanDevice::tiles; stages bits 6-9)
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
-                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info);
+                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
+                       int tile_mode = 0);
 // FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
 // not null one digest per array in that block's order (names: kPlanDigestNames)
 uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
@@ -370,7 +377,7 @@ class SpSolver {
     std::function<void()> before_alloc;            // upload: called once after the host plan build
     // deftri_set_plan_builder: the mode, the context's builder arena (null: no device stages) and where the
     // build reports what it did (deftri_plan_build_info; may be null)
-    int plan_builder = 0;
+    int plan_builder = 0, tile_builder = 0;          // (tile_builder: deftri_set_tile_builder)
     PlanDevice *plan_dev = nullptr;
     PlanBuildInfo *plan_build = nullptr;
     int refresh(const deftri_problem_desc &d);     // same structure: values only, plan kept

@@ -159,7 +159,7 @@ uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
 // pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
 // stages: the bit mask of the stages it ran
 static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
-                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages) {
+                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false) {
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
     auto stage = [&](const char *name) {
@@ -183,7 +183,10 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     int32_t ng = 0;
     if (pd) {
         // stages 1-3 on the device (plan_dev.hip): the same groups, order and rows
-        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err);
+        // (the tile stages' int counts: padded entries <= 2 E + 64 ng, and a group id shifted by 2 bits)
+        tiles_dev = tiles_dev && tile && Q == 1 && S <= 2 && E > 0 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31) &&
+                    sp_tile_lds_budget() < (1LL << 30);
+        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         *stages |= 7;
         stage("1-3 on the device (wall)");
@@ -330,7 +333,18 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
         std::vector<int32_t> gp;
-        if (pd) gp.swap(gp_dev);
+        bool built = false;
+        if (pd && tiles_dev) {
+            // build_tiles on the device (plan_dev.hip); 2: a graph build_tiles refuses — the host's
+            // build_tiles below then says why, from the device's rows and groups
+            const int rc = pd->tiles(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err);
+            if (rc == 1 || rc < 0) return rc > 0 ? kPlanBound : kPlanHip;
+            built = rc == 0;
+            if (built) {
+                H.tile = true;
+                *stages |= 0x3c0;
+            }
+        } else if (pd) gp.swap(gp_dev);
         else {
             gp.resize(P);
             for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
@@ -338,7 +352,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         TileInput ti;
         ti.P = P; ti.ng = ng; ti.E = E; ti.ap = ap; ti.gpos = gp.data(); ti.row_of_point = H.row_of_point.data();
         std::string why;
-        H.tile = build_tiles(ti, H, tile_order, tile_foreign, why);
+        if (!built) H.tile = build_tiles(ti, H, tile_order, tile_foreign, why);
         if (!H.tile) {
             H.tile_why = why;
             tile_order.clear();
@@ -769,7 +783,8 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 }
 
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
-                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info) {
+                       bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
+                       int tile_mode) {
     const auto t0 = std::chrono::steady_clock::now();
     info = PlanBuildInfo();
     auto done = [&](int rc) {
@@ -782,7 +797,7 @@ int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool 
     if (mode == 1 && !applies) info.reason = 1;
     if (applies) {
         int32_t stages = 0;
-        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages);
+        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, tile_mode == 1);
         if (rc == kPlanOk) {
             info.builder_used = 1;
             info.stages = stages;

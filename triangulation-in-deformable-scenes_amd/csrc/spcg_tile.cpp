@@ -127,21 +127,31 @@ bool merge_tile_bufs(std::vector<TileBuf> &B, int nb, SpPlanHost &H, std::vector
 
 }  // namespace
 
+int sp_tile_units() {
+    static const int umax = [] {
+        const char *e = std::getenv("DEFTRI_SP_TILE_UNITS");
+        const int v = e ? std::atoi(e) : kSpTileUnits;
+        return std::max(8, std::min(v, 128));
+    }();
+    return umax;
+}
+
+int64_t sp_tile_lds_budget() {
+    static const int64_t lds_budget = [] {
+        const char *e = std::getenv("DEFTRI_SP_TILE_LDS");
+        return (int64_t)(e ? std::atoi(e) : kSpTileLds);
+    }();
+    return lds_budget;
+}
+
 bool build_tiles(const TileInput &in, SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &order_foreign,
                  std::string &why) {
     const int32_t ng = in.ng;
     const int64_t E = in.E;
     const int32_t *ap = in.ap;
     const int32_t lo = H.lo, hi = H.hi;
-    static const int umax = [] {
-        const char *e = std::getenv("DEFTRI_SP_TILE_UNITS");
-        const int v = e ? std::atoi(e) : kSpTileUnits;
-        return std::max(8, std::min(v, 128));
-    }();
-    static const int64_t lds_budget = [] {
-        const char *e = std::getenv("DEFTRI_SP_TILE_LDS");
-        return (int64_t)(e ? std::atoi(e) : kSpTileLds);
-    }();
+    const int umax = sp_tile_units();
+    const int64_t lds_budget = sp_tile_lds_budget();
     // DEFTRI_PLAN_TIMING: the stages of this build too
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
@@ -507,15 +517,8 @@ bool build_tiles_multi(const TileInput &in, SpPlanHost &H, std::vector<int32_t> 
     const int32_t P = in.P, ng = in.ng, Q = in.Q;
     const int64_t E = in.E;
     const int32_t *ap = in.ap, *row = in.row_of_point;
-    static const int umax = [] {
-        const char *e = std::getenv("DEFTRI_SP_TILE_UNITS");
-        const int v = e ? std::atoi(e) : kSpTileUnits;
-        return std::max(8, std::min(v, 128));
-    }();
-    static const int64_t lds_budget = [] {
-        const char *e = std::getenv("DEFTRI_SP_TILE_LDS");
-        return (int64_t)(e ? std::atoi(e) : kSpTileLds);
-    }();
+    const int umax = sp_tile_units();
+    const int64_t lds_budget = sp_tile_lds_budget();
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
     auto lap = [&](const char *w) {

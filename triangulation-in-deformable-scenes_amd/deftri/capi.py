@@ -94,6 +94,7 @@ def load():
         "deftri_delaunay2d": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(_abi.DelaunayReport)]),
         "deftri_set_mesh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_plan_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_set_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "deftri_debug_plan_digest": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_uint64), C.c_int32,
                                                P(C.c_int32)]),
@@ -240,7 +241,7 @@ EXPORTED = [
     "deftri_orb_set_pattern", "deftri_orb_describe", "deftri_debug_orb_pyramid", "deftri_debug_orb_blur_kernel",
     "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
-    "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest",
+    "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
 ]
 
 # the arrays of deftri_debug_plan_digest, in its order; the combined digest follows them
@@ -701,6 +702,12 @@ class Context:
         """Who builds the iterative plan at the next upload of this context (deftri_set_plan_builder): 0 the host
         passes (default), 1 the device stages where they apply (one rank, one pair, the tile layout)."""
         self._check(self.lib.deftri_set_plan_builder(self.h, int(mode)))
+
+    def set_tile_builder(self, mode):
+        """Who cuts the one-pair tile layout where plan builder 1's device stages apply (deftri_set_tile_builder):
+        0 build_tiles on the host (default), 1 the device stages (plan_build_info stages bits 6-9).  No effect with
+        plan builder 0."""
+        self._check(self.lib.deftri_set_tile_builder(self.h, int(mode)))
 
     def plan_build_info(self):
         """What the last iterative plan build did (deftri_plan_build_info): builder_used, stages (bit mask),

@@ -45,7 +45,8 @@ def test_device_equals_host(ctxs, name):
         assert ref.still_valid(xy, tris) == 1
 
 
-@pytest.mark.parametrize("n", [3, 4, 63, 64, 65, 129])
+# 1023 .. 2500: the chunk boundaries of the rows' scan, one workgroup of 1024 threads (3 is its one-thread case)
+@pytest.mark.parametrize("n", [3, 4, 63, 64, 65, 129, 1023, 1024, 1025, 2500])
 def test_wave_and_tournament_boundaries(ctxs, n):
     xy = ref.gaussian(n, 20 + n)
     tris, rep = both(ctxs, xy)

@@ -87,12 +87,19 @@ def test_unsearched_and_empty_on_device(gpu_ctx):
 
 
 @gpu
-@pytest.mark.parametrize("n", [1, 257, 2048])
-def test_cell_lists(gpu_ctx, host, n):
+@pytest.mark.parametrize("n,cells", [
+    pytest.param(1, None, id="1"), pytest.param(257, None, id="257"), pytest.param(2048, None, id="2048"),
+    # the scan's chunk boundaries: 1, 255, 256, 257 and 1000 cells against the 256 threads of its one workgroup
+    pytest.param(300, (1, 1), id="300-1cell"), pytest.param(300, (15, 17), id="300-255cells"),
+    pytest.param(300, (16, 16), id="300-256cells"), pytest.param(300, (257, 1), id="300-257cells"),
+    pytest.param(300, (40, 25), id="300-1000cells")])
+def test_cell_lists(gpu_ctx, host, n, cells):
     """Every in-grid key exactly once, in its own cell; out-of-grid keys nowhere."""
-    s = ms.random_scene(n, ms.REALCOLON, 25.0, seed=8)
+    grid = ms.REALCOLON if cells is None else dict(ms.REALCOLON, cols=cells[0], rows=cells[1])
+    s = ms.random_scene(n, grid, 25.0, seed=8)
     g, uv = s["grid"], s["uv2"]
-    uv[0] = [1429.0, 500.0]                                   # the last half cell: in no cell
+    uv[0] = [1429.0 if cells is None else 1439.5, 500.0]      # the last half cell: in no cell
+    assert not matching.pos_in_grid(g, *uv[0])[0]
     start, keys = gpu_ctx.debug_feature_grid_cells(g, uv)
     hstart, hkeys = host.debug_feature_grid_cells(g, uv)
     np.testing.assert_array_equal(start, hstart)

@@ -1,4 +1,4 @@
-"""searchForTriangulation (k_tri_rays, k_tri_candidates, k_tri_scan and the loop over the candidate lists) and the
+"""searchForTriangulation (k_tri_rays, k_tri_candidates, k_excl_scan and the loop over the candidate lists) and the
 search of fuse (k_prepare_points' fuse mode, one k_match_round) on the device, against the library's sequential
 host loops and the restatements of deftri.matching, and the chain search_for_triangulation -> triangulate -> fuse
 -> localBundleAdjustment end to end.
@@ -61,6 +61,22 @@ def test_cloud_scenes(gpu_ctx, host, n1, n2, flag_quirk):
         assert got.report["n_occupied"] > 0 and got.report["n_unmatched"] > 0
     elif got.report["flag_row"] >= 0:
         assert (got.status[got.report["flag_row"] + 1:][~s["has1"][got.report["flag_row"] + 1:]] == 4).all()
+
+
+@gpu
+@pytest.mark.parametrize("n1", [1, 255, 256, 257, 600])
+def test_row_offsets_at_the_scan_chunk_boundaries(gpu_ctx, host, n1):
+    """The rows' counts are scanned by one workgroup of 256 threads, a contiguous chunk each: one row, one row
+    below, at and above 256, and 600 rows in chunks of 3 that leave threads idle.  The rows cycle over six lines
+    against 40 keypoints on five of them, so the counts differ from row to row, every sixth row (no keypoint on its
+    line) and every seventh (it holds a map point) lists nothing, and rows rob each other throughout."""
+    rows = [(i % 6, 3 + (5 * i) % 47, i % 7 == 3) for i in range(n1)]
+    keys = [(j % 5, 2 + (7 * j) % 53, j % 11 == 5) for j in range(40)]
+    s = tm.line_scene(rows, keys)
+    got = three_way(gpu_ctx, host, s, False)
+    r = tm.ref(s, False)
+    listed = (~s["has1"][:, None] & ~s["has2"][None, :] & (r["dist"] <= 49) & (r["err"] < s["epipolar_th"])).sum(1)
+    assert got.report["n_listed"] == listed.sum() and (n1 == 1 or len(set(listed.tolist())) > 3)
 
 
 @gpu

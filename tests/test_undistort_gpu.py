@@ -1,5 +1,5 @@
 """deftri_undistort_points and deftri_distribute_features on the device (k_undistort, k_undistort_cells, then the
-matchers' k_grid_scan / k_grid_fill and k_grid_order) against the library's sequential host loops and
+matchers' k_excl_scan / k_grid_fill and k_grid_order) against the library's sequential host loops and
 undistort_ref.py, every output array bit for bit: both sides evaluate the same double operations with one rounding
 each, posInGrid in float, and the cell lists are integers in keypoint order.
 

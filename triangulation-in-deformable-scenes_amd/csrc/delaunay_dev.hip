@@ -4,7 +4,7 @@
 //                  order kernels (matching.hip), so every cell is in point order
 //   k_stars<false> one wave per point builds its star and counts the triangles in which the point is the smallest
 //                  vertex; a star with an uncertain predicate or more than 64 triangles is marked and counts none
-//   k_dl_scan      the rows' offsets
+//   k_excl_scan    the rows' offsets (dev_scan.h)
 //   k_stars<true>  the same stars again, each writing its row, sorted by the second vertex, where the scan put it
 // Counting first and building twice, not a fixed slab per point: the rows land in the canonical order at their
 // exact sizes, no capacity decides which stars are marked, and a point of degree 60 that is the smallest of all
@@ -22,6 +22,8 @@
 
 #include "delaunay.h"
 #include "delaunay_star.h"
+#include "dev_arena.h"
+#include "dev_scan.h"
 #include "matching_grid.h"
 
 namespace deftri {
@@ -61,25 +63,6 @@ __global__ void k_dl_cells(int n, Grid G, const double *__restrict__ xy, int *__
     const int id = dstar::cell_x(G, xy[2 * (size_t)i]) * G.gy + dstar::cell_y(G, xy[2 * (size_t)i + 1]);
     cell[i] = id;
     atomicAdd(&count[id], 1);
-}
-
-// exclusive scan of count [n] by one workgroup: off [n + 1]
-__global__ void __launch_bounds__(1024) k_dl_scan(int n, const int *__restrict__ count, int *__restrict__ off) {
-    __shared__ int sums[1024];
-    const int chunk = (n + 1023) / 1024;
-    const int lo = min((int)threadIdx.x * chunk, n), hi = min(lo + chunk, n);
-    int s = 0;
-    for (int c = lo; c < hi; c++) s += count[c];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int t = 0; t < 1024; t++) { const int v = sums[t]; sums[t] = run; run += v; }
-        off[n] = run;
-    }
-    __syncthreads();
-    int run = sums[threadIdx.x];
-    for (int c = lo; c < hi; c++) { off[c] = run; run += count[c]; }
 }
 
 // status [p] = mark | hull << 8 | degree << 16.  tris has room for tri_cap triangles.
@@ -161,10 +144,6 @@ Star host_star(const Grid &G, const double *xy, const int *start, const int *ite
         for (size_t j = i; j > 0 && rows[at + 3 * (j - 1) + 1] > rows[at + 3 * j + 1]; j--)
             for (int c = 1; c < 3; c++) std::swap(rows[at + 3 * (j - 1) + c], rows[at + 3 * j + c]);
     return S;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
 }
 
 // the whole-call fallback: delaunay2d's triangles, hull_size, skipped and return value
@@ -300,7 +279,7 @@ int delaunay_stars(DelaunayDevice *dd, int32_t n, const double *xy, std::vector<
     const dim3 sgrid((unsigned)((N + 3) / 4));
     hipLaunchKernelGGL(dev::k_stars<false>, sgrid, dim3(256), 0, st, n, G, d_xy, d_start, d_items, d_status, d_tcount, d_toff, d_tris,
                        tri_cap);
-    hipLaunchKernelGGL(dev::k_dl_scan, dim3(1), dim3(1024), 0, st, n, d_tcount, d_toff);
+    dev::launch_excl_scan<int, 1024>(n, d_tcount, d_toff, nullptr, st);
     hipLaunchKernelGGL(dev::k_stars<true>, sgrid, dim3(256), 0, st, n, G, d_xy, d_start, d_items, d_status, d_tcount, d_toff, d_tris,
                        tri_cap);
     hipEventRecord(dd->ev_[2], st);

@@ -344,15 +344,6 @@ k_camera_vote(int n, const float *__restrict__ uv1, const float *__restrict__ uv
 using namespace dev;
 
 namespace {
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // decomposeE (:264-279) and the choice of Rgood (:253) in fp64 from the float E: R [9] row-major and the
@@ -473,11 +464,15 @@ int find_essential_ransac(int device, hipStream_t st, int32_t n, const float *uv
     const size_t in_uv2 = align16(8 * N), in_samples = in_uv2 + align16(8 * N), in_bytes = in_samples + 32 * H;
     const size_t out_err = align16(sizeof(RansacHead)), out_scores = out_err + align16(4 * N), out_E = out_scores + align16(4 * H);
     const size_t out_deg = out_E + align16(36 * H), out_inl = out_deg + align16(H), out_bytes = out_inl + N;
+    std::vector<char> in(in_bytes, 0), out(out_bytes);
+    std::memcpy(in.data(), uv1, 8 * N);
+    std::memcpy(in.data() + in_uv2, uv2, 8 * N);
+    std::memcpy(in.data() + in_samples, samples, 32 * H);
     DevArena A;
     char *d_in, *d_out;
     float *d_rays;
-    A.add(&d_in, in_bytes); A.add(&d_out, out_bytes); A.add(&d_rays, 6 * N);
-    if (!A.commit()) {
+    A.in(&d_in, in.data(), in_bytes); A.add(&d_out, out_bytes); A.add(&d_rays, 6 * N);
+    if (!A.commit(st)) {
         err = "find_essential_ransac: allocation failed";
         return DEFTRI_E_HIP;
     }
@@ -487,17 +482,12 @@ int find_essential_ransac(int device, hipStream_t st, int32_t n, const float *uv
             err = "find_essential_ransac: hipEventCreate failed";
             return DEFTRI_E_HIP;
         }
-    std::vector<char> in(in_bytes, 0), out(out_bytes);
-    std::memcpy(in.data(), uv1, 8 * N);
-    std::memcpy(in.data() + in_uv2, uv2, 8 * N);
-    std::memcpy(in.data() + in_samples, samples, 32 * H);
     const float *d_uv1 = (const float *)d_in, *d_uv2 = (const float *)(d_in + in_uv2);
     const int *d_samples = (const int *)(d_in + in_samples);
     RansacHead *d_head = (RansacHead *)d_out;
     float *d_err = (float *)(d_out + out_err), *d_E = (float *)(d_out + out_E);
     int *d_scores = (int *)(d_out + out_scores);
     uint8_t *d_deg = (uint8_t *)(d_out + out_deg), *d_inl = (uint8_t *)(d_out + out_inl);
-    hipMemcpyAsync(d_in, in.data(), in_bytes, hipMemcpyHostToDevice, st);
     hipMemsetAsync(d_out, 0, out_bytes, st);                 // the scores and n_degenerate start at 0
     const unsigned nb = (unsigned)((N + 255) / 256);
     hipEventRecord(ev[0], st);
@@ -559,21 +549,20 @@ int reconstruct_cameras(int device, hipStream_t st, int32_t n, const float *uv1,
     } else {
         hipSetDevice(device);
         const size_t in_uv2 = align16(8 * N), in_use = in_uv2 + align16(8 * N), in_bytes = in_use + N;
-        DevArena A;
-        char *d_in;
-        int *d_away;
-        A.add(&d_in, in_bytes); A.add(&d_away, 1);
-        if (!A.commit()) {
-            err = "reconstruct_cameras: allocation failed";
-            return DEFTRI_E_HIP;
-        }
         std::vector<char> in(in_bytes, 0);
         std::memcpy(in.data(), uv1, 8 * N);
         std::memcpy(in.data() + in_uv2, uv2, 8 * N);
         if (use) std::memcpy(in.data() + in_use, use, N);
+        DevArena A;
+        char *d_in;
+        int *d_away;
+        A.in(&d_in, in.data(), in_bytes); A.add(&d_away, 1);
+        if (!A.commit(st)) {
+            err = "reconstruct_cameras: allocation failed";
+            return DEFTRI_E_HIP;
+        }
         Mat3 Rm;
         std::memcpy(Rm.m, R, sizeof(Rm.m));
-        hipMemcpyAsync(d_in, in.data(), in_bytes, hipMemcpyHostToDevice, st);
         hipMemsetAsync(d_away, 0, sizeof(int), st);
         hipLaunchKernelGGL(dev::k_camera_vote, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, n, (const float *)d_in,
                            (const float *)(d_in + in_uv2), use ? (const uint8_t *)(d_in + in_use) : nullptr, k1, k2, Rm,

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -17,6 +18,15 @@ struct FastImage {
     const uint8_t *px;
     int32_t rows, cols, stride;
 };
+
+// "<entry>: <why>" into err; the return value of an entry that refuses its arguments
+inline int arg_fail(std::string &err, const char *entry, const std::string &why) {
+    err = std::string(entry) + ": " + why;
+    return DEFTRI_E_ARG;
+}
+
+// cvRound: round half to even
+inline int cv_round(float v) { return (int)lrintf(v); }
 
 // device < 0: the sequential host loops; else the kernels on `st`.  The arguments are those of the C
 // entries, already checked for null pointers by the callers.  uv [max_keys * 2], the others [max_keys].

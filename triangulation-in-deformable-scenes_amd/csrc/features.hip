@@ -265,19 +265,7 @@ using namespace dev;
 namespace {
 
 using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-int arg_fail(std::string &err, const std::string &why) {
-    err = "fast_extract: " + why;
-    return DEFTRI_E_ARG;
-}
-
-int cv_round(float v) { return (int)lrintf(v); }   // round half to even
+const char *const kEntry = "fast_extract";   // what every argument error of this file starts with
 
 struct Cand { int x, y, resp; };       // relative to the 16-pixel border: vToDistributeKeys' pt
 
@@ -319,13 +307,13 @@ int mask_side(int level) {
 }
 
 int make_plan(const FastImage &im, const deftri_fast_params &p, bool with_cells, Plan &P, std::string &err) {
-    if (p.n_scales < 1 || p.n_scales > DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, "n_scales must be in [1, 16]");
-    if (!(p.scale_factor > 1.0f)) return arg_fail(err, "scale_factor must be > 1");
-    if (im.rows < 1 || im.cols < 1 || im.stride < im.cols) return arg_fail(err, "stride < cols, or an empty image");
+    if (p.n_scales < 1 || p.n_scales > DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, kEntry, "n_scales must be in [1, 16]");
+    if (!(p.scale_factor > 1.0f)) return arg_fail(err, kEntry, "scale_factor must be > 1");
+    if (im.rows < 1 || im.cols < 1 || im.stride < im.cols) return arg_fail(err, kEntry, "stride < cols, or an empty image");
     if (p.th_fast < 1 || p.th_fast > 255 || p.min_th_fast < 1 || p.min_th_fast > p.th_fast)
-        return arg_fail(err, "thresholds must satisfy 1 <= min_th_fast <= th_fast <= 255");
-    if (p.max_keys < 0) return arg_fail(err, "max_keys < 0");
-    if (p.n_max_features < 0) return arg_fail(err, "n_max_features < 0");
+        return arg_fail(err, kEntry, "thresholds must satisfy 1 <= min_th_fast <= th_fast <= 255");
+    if (p.max_keys < 0) return arg_fail(err, kEntry, "max_keys < 0");
+    if (p.n_max_features < 0) return arg_fail(err, kEntry, "n_max_features < 0");
     const int n = P.n_levels = p.n_scales;
     // FAST.h:54-78, in float as written
     P.scale[0] = 1.0f;
@@ -359,9 +347,9 @@ int make_plan(const FastImage &im, const deftri_fast_params &p, bool with_cells,
         P.key_cap[l] = 0;
         const std::string at = "level " + std::to_string(l) + " (" + std::to_string(P.cols[l]) + " x " + std::to_string(P.rows[l]) + ")";
         if (P.cols[l] < 62 || P.rows[l] < 62)
-            return arg_fail(err, at + " is below the 62 pixels a side one cell needs (the reference divides by nCols = 0)");
+            return arg_fail(err, kEntry, at + " is below the 62 pixels a side one cell needs (the reference divides by nCols = 0)");
         if (l && P.cols[l - 1] == 2 * P.cols[l] && P.rows[l - 1] == 2 * P.rows[l])
-            return arg_fail(err, at + " halves the level above it exactly: cv::resize takes its area path, which is not restated");
+            return arg_fail(err, kEntry, at + " halves the level above it exactly: cv::resize takes its area path, which is not restated");
         if (l) {
             P.xt[l] = taps(P.cols[l - 1], P.cols[l]);
             P.yt[l] = taps(P.rows[l - 1], P.rows[l]);
@@ -375,7 +363,7 @@ int make_plan(const FastImage &im, const deftri_fast_params &p, bool with_cells,
         // distributeOctTree's nIni (:246)
         P.n_ini[l] = (int)roundf((float)(max_bx - min_bx) / (max_by - min_by));
         if (P.n_ini[l] < 1)
-            return arg_fail(err, at + ": distributeOctTree starts from round(width / height) = 0 nodes and the reference divides by it");
+            return arg_fail(err, kEntry, at + ": distributeOctTree starts from round(width / height) = 0 nodes and the reference divides by it");
         if (!with_cells) continue;
         for (int i = 0; i < n_rows; i++) {                                 // :168-203
             const float ini_y = (float)(min_by + i * h_cell);
@@ -388,14 +376,14 @@ int make_plan(const FastImage &im, const deftri_fast_params &p, bool with_cells,
                 if (ini_x >= max_bx - 6) continue;
                 if (max_x > max_bx) max_x = (float)max_bx;
                 CellDesc c{l, (int)ini_x, (int)ini_y, (int)max_x - (int)ini_x, (int)max_y - (int)ini_y, j * w_cell, i * h_cell, 0};
-                if (c.w > kTile || c.h > kTile || c.w < 1 || c.h < 1) return arg_fail(err, at + ": a cell larger than 64 pixels a side");
+                if (c.w > kTile || c.h > kTile || c.w < 1 || c.h < 1) return arg_fail(err, kEntry, at + ": a cell larger than 64 pixels a side");
                 P.cells.push_back(c);
                 if (c.w > 6 && c.h > 6) P.key_cap[l] += (size_t)((c.w - 5) / 2) * ((c.h - 5) / 2);
             }
         }
     }
     P.cell_begin[n] = (int)P.cells.size();
-    if (P.cells.size() >= ((size_t)1 << 24)) return arg_fail(err, "more than 2^24 cells");
+    if (P.cells.size() >= ((size_t)1 << 24)) return arg_fail(err, kEntry, "more than 2^24 cells");
     return 0;
 }
 
@@ -626,7 +614,7 @@ int run(int device, hipStream_t st, const FastImage &im, const FastImage &bm, co
     if (const int rc = make_plan(im, p, probe.pyramid_level < 0, P, err)) return rc;
     if (full && !mask_size_ok(im, bm, err)) return DEFTRI_E_ARG;
     const int nl = P.n_levels;
-    if (probe.pyramid_level >= nl || probe.cand_level >= nl) return arg_fail(err, "level outside [0, n_scales)");
+    if (probe.pyramid_level >= nl || probe.cand_level >= nl) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     deftri_fast_report R{};
     R.n_levels = nl;
     for (int l = 0; l < nl; l++) { R.level_cols[l] = P.cols[l]; R.level_rows[l] = P.rows[l]; R.features_per_level[l] = P.features[l]; }
@@ -861,10 +849,10 @@ int fast_extract(int device, hipStream_t st, const FastImage &image, const FastI
 
 int fast_pyramid_level(int device, hipStream_t st, const FastImage &image, const deftri_fast_params &p, int32_t level, uint8_t *out,
                        int32_t *out_rows, int32_t *out_cols, std::string &err) {
-    if (level < 0) return arg_fail(err, "level outside [0, n_scales)");
+    if (level < 0) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     Plan P;
     if (const int rc = make_plan(image, p, false, P, err)) return rc;
-    if (level >= P.n_levels) return arg_fail(err, "level outside [0, n_scales)");
+    if (level >= P.n_levels) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     *out_rows = P.rows[level];
     *out_cols = P.cols[level];
     Probe probe;
@@ -875,7 +863,7 @@ int fast_pyramid_level(int device, hipStream_t st, const FastImage &image, const
 
 int fast_candidates(int device, hipStream_t st, const FastImage &image, const deftri_fast_params &p, int32_t level, int32_t max_cand,
                     int32_t *xy, float *response, int32_t *n, std::string &err) {
-    if (level < 0) return arg_fail(err, "level outside [0, n_scales)");
+    if (level < 0) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     std::vector<Cand> cand;
     Probe probe;
     probe.cand_level = level;
@@ -894,12 +882,12 @@ int fast_candidates(int device, hipStream_t st, const FastImage &image, const de
 
 int fast_mask_reads(int device, hipStream_t st, const FastImage &image, const FastImage &border_mask, int32_t level, int32_t n,
                     const int32_t *xy, uint8_t *hit, std::string &err) {
-    if (level < 0 || level >= DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, "level outside [0, 16)");
-    if (image.rows < 1 || image.cols < 1 || image.stride < image.cols) return arg_fail(err, "stride < cols, or an empty image");
+    if (level < 0 || level >= DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, kEntry, "level outside [0, 16)");
+    if (image.rows < 1 || image.cols < 1 || image.stride < image.cols) return arg_fail(err, kEntry, "stride < cols, or an empty image");
     if (!mask_size_ok(image, border_mask, err)) return DEFTRI_E_ARG;
     for (int32_t i = 0; i < n; i++)
         if (xy[2 * i] < 0 || xy[2 * i] >= image.cols || xy[2 * i + 1] < 0 || xy[2 * i + 1] >= image.rows)
-            return arg_fail(err, "a mask read outside the image");
+            return arg_fail(err, kEntry, "a mask read outside the image");
     const int half = (mask_side(level) - 1) / 2;
     if (device < 0 || n == 0) {
         const std::vector<int32_t> S = host_integral(image, border_mask);

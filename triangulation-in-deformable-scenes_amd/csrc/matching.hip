@@ -7,9 +7,9 @@
 // float(secondBestDist) * 0.9.  (best, second) are the two smallest of a multiset, so the order the
 // candidates are visited in does not change them, and an accepted best is strictly below the second:
 // its index is unique.  The device therefore reduces in any order and equals the sequential loop.
-//   k_grid_cells / k_grid_scan / k_grid_fill   the current frame's cell lists as a CSR
+//   k_grid_cells / k_excl_scan / k_grid_fill   the current frame's cell lists as a CSR (the scan: dev_scan.h)
 //   k_grid_order                               the lists in keypoint order (undistort.hip's distributeFeatures)
-//   k_match_init                               one 64-lane wave per reference keypoint
+//   k_match_init                               one 64-lane wave per reference keypoint (wave_window_best)
 //   k_count_matches                            nMatches
 // posInGrid rounds to the nearest cell index, so a keypoint in the last half cell of the image gets
 // index == size, is in no cell (Frame.cc:204-210) and is never a candidate: kept.
@@ -19,8 +19,8 @@
 // the poses (:160-163), in every iteration, so its result is one computeScoreAndInliers (:206-223):
 //   k_epipolar_inliers                         one thread per match, the score per workgroup
 //
-// The grid geometry, the acceptance test and the wave's join are in matching_grid.h, shared with
-// projection_matching.hip.
+// The grid geometry, the acceptance test and the window search of a wave and of the host loop are in
+// matching_grid.h, shared with projection_matching.hip.
 //
 // Float arithmetic without contraction on both sides; the host loops below are the sequential
 // restatements a host-only context runs and the kernels are tested against.
@@ -30,6 +30,7 @@
 #include <cstring>
 
 #include "dev_arena.h"
+#include "dev_scan.h"
 #include "device_math.h"
 #include "epipolar.h"
 #include "matching.h"
@@ -52,26 +53,7 @@ __global__ void k_grid_cells(int n, const float *__restrict__ uv, GridGeom G, in
     if (in) atomicAdd(&count[id], 1);
 }
 
-// exclusive scan of the cell sizes by one workgroup: start [ncell + 1], cursor [ncell] = start
-__global__ void __launch_bounds__(256) k_grid_scan(int ncell, const int *__restrict__ count, int *__restrict__ start,
-                                                   int *__restrict__ cursor) {
-    __shared__ int sums[256];
-    const long long chunk = ((long long)ncell + 255) / 256;
-    const long long lo = min((long long)threadIdx.x * chunk, (long long)ncell), hi = min(lo + chunk, (long long)ncell);
-    int s = 0;
-    for (long long c = lo; c < hi; c++) s += count[c];
-    sums[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int t = 0; t < 256; t++) { const int v = sums[t]; sums[t] = run; run += v; }
-        start[ncell] = run;
-    }
-    __syncthreads();
-    int run = sums[threadIdx.x];
-    for (long long c = lo; c < hi; c++) { start[c] = run; cursor[c] = run; run += count[c]; }
-}
-
+// the cell lists from the scanned sizes; cursor [ncell] = start on entry (k_excl_scan's second output)
 __global__ void k_grid_fill(int n, const int *__restrict__ cell, int *__restrict__ cursor, int *__restrict__ keys) {
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (i >= n) return;
@@ -94,8 +76,7 @@ __global__ void k_grid_order(int n, const int *__restrict__ cell, const int *__r
 }
 
 // One wave per reference keypoint (4 per workgroup).  `radius`: windowSizeFactor * 1 * getScaleFactor(0),
-// the only octave searched (:56).  A column of the cell range is one run of cell_keys (cells c * rows +
-// rmin .. rmax are adjacent); the lanes stride over it.
+// the only octave searched (:56).
 __global__ void __launch_bounds__(256)
 k_match_init(int n1, const float *__restrict__ uv1, const int *__restrict__ octave1, const uint4 *__restrict__ desc1,
              const float *__restrict__ uv2, const int *__restrict__ octave2, const uint4 *__restrict__ desc2, GridGeom G,
@@ -105,45 +86,14 @@ k_match_init(int n1, const float *__restrict__ uv1, const int *__restrict__ octa
     const int i = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (i >= n1) return;
     const int oct = octave1[i];
-    int b = 255, s = 255, idx = -1;
-    if (oct <= 0) {                                                    // :56
-        const float x = uv1[2 * i], y = uv1[2 * i + 1];
-        const int min_level = oct - 1, max_level = oct + 1;            // :72
-        int cmin, rmin, cmax, rmax;
-        cell_range(G, x, y, radius, cmin, rmin, cmax, rmax);
-        const uint4 a0 = desc1[2 * (size_t)i], a1 = desc1[2 * (size_t)i + 1];
-        for (int c = cmin; c <= cmax; c++) {
-            if (rmin > rmax) break;
-            const int k0 = cell_start[c * G.rows + rmin], k1 = cell_start[c * G.rows + rmax + 1];
-            for (int k = k0 + lane; k < k1; k += 64) {
-                const int j = cell_keys[k];
-                const int o = octave2[j];
-                if (o < min_level || o > max_level) continue;                       // Frame.cc:315
-                const float dx = uv2[2 * j] - x, dy = uv2[2 * j + 1] - y;
-                if (!(fabsf(dx) < radius && fabsf(dy) < radius)) continue;          // :317
-                const uint4 c0 = desc2[2 * (size_t)j], c1 = desc2[2 * (size_t)j + 1];
-                const unsigned long long w0 = ((unsigned long long)(a0.y ^ c0.y) << 32) | (a0.x ^ c0.x);
-                const unsigned long long w1 = ((unsigned long long)(a0.w ^ c0.w) << 32) | (a0.z ^ c0.z);
-                const unsigned long long w2 = ((unsigned long long)(a1.y ^ c1.y) << 32) | (a1.x ^ c1.x);
-                const unsigned long long w3 = ((unsigned long long)(a1.w ^ c1.w) << 32) | (a1.z ^ c1.z);
-                const int d = __popcll(w0) + __popcll(w1) + __popcll(w2) + __popcll(w3);
-                // DescriptorMatching.cc:82-89; a distance of 255 or 256 changes nothing
-                if (d < b) { s = b; b = d; idx = j; }
-                else {
-                    if (d < s) s = d;
-                    if (d == b && d < 255 && j < idx) idx = j;
-                }
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const int b2 = __shfl_xor(b, off, 64), s2 = __shfl_xor(s, off, 64), i2 = __shfl_xor(idx, off, 64);
-            join_best(b, s, idx, b2, s2, i2);
-        }
-    }
+    WindowBest w{255, 255, -1, 0};
+    if (oct <= 0)                                                      // :56
+        w = wave_window_best(G, cell_start, cell_keys, uv2, octave2, desc2, uv1[2 * i], uv1[2 * i + 1], radius, oct,
+                             desc1[2 * (size_t)i], desc1[2 * (size_t)i + 1], lane, [](int) { return false; });
     if (lane == 0) {
-        matches[i] = (oct <= 0 && accept_match(b, s, th)) ? idx : -1;   // :92-95
-        best_out[i] = b;
-        second_out[i] = s;
+        matches[i] = (oct <= 0 && accept_match(w.best, w.second, th)) ? w.idx : -1;   // :92-95
+        best_out[i] = w.best;
+        second_out[i] = w.second;
     }
 }
 
@@ -177,25 +127,6 @@ k_epipolar_inliers(int n, const float *__restrict__ uv1, const float *__restrict
 
 using namespace dev;
 
-namespace {
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-// the reference reads vScaleFactor_[octave] of the keypoint (DescriptorMatching.cc:69)
-bool octaves_ok(const deftri_feature_grid &g, int32_t n, const int32_t *octave, const char *which, std::string &err) {
-    for (int32_t i = 0; i < n; i++)
-        if (octave[i] < 0 || octave[i] >= g.n_scales) {
-            err = std::string("match_for_initialization: ") + which + " keypoint " + std::to_string(i) + " has octave " +
-                  std::to_string(octave[i]) + ", outside [0, nScales = " + std::to_string(g.n_scales) + ")";
-            return false;
-        }
-    return true;
-}
-
-}  // namespace
-
 // "" for a grid Frame could have built, else what is wrong with it
 std::string grid_error(const deftri_feature_grid &g) {
     if (g.cols <= 0 || g.rows <= 0) return "FeatureGrid.nGridCols / nGridRows must be positive";
@@ -203,6 +134,18 @@ std::string grid_error(const deftri_feature_grid &g) {
     if (!(g.max_col > g.min_col) || !(g.max_row > g.min_row)) return "feature grid bounds: max <= min";
     if (g.n_scales < 1) return "FeatureExtractor.nScales < 1";
     return "";
+}
+
+// the reference reads vScaleFactor_[octave] of the keypoint (DescriptorMatching.cc:69)
+bool octaves_ok(const char *entry, const char *what, const deftri_feature_grid &g, int32_t n, const int32_t *octave,
+                const uint8_t *has, std::string &err) {
+    for (int32_t i = 0; i < n; i++)
+        if ((!has || has[i]) && (octave[i] < 0 || octave[i] >= g.n_scales)) {
+            err = std::string(entry) + ": " + what + " " + std::to_string(i) + " has octave " + std::to_string(octave[i]) +
+                  ", outside [0, nScales = " + std::to_string(g.n_scales) + ")";
+            return false;
+        }
+    return true;
 }
 
 // getScaleFactor(octave) of Frame's table (Frame.cc:65-70): a running float product
@@ -224,7 +167,7 @@ void launch_grid(const GridGeom &G, int n, const float *d_uv, int *d_cell, int *
 // the lists from every keypoint's cell and the cells' sizes: the scan and the fill
 void launch_grid_lists(int ncell, int n, const int *d_cell, const int *d_count, int *d_start, int *d_cursor, int *d_keys,
                        hipStream_t st) {
-    hipLaunchKernelGGL(dev::k_grid_scan, dim3(1), dim3(256), 0, st, ncell, d_count, d_start, d_cursor);
+    launch_excl_scan<int, 256>(ncell, d_count, d_start, d_cursor, st);
     hipLaunchKernelGGL(dev::k_grid_fill, dim3((n + 255) / 256), dim3(256), 0, st, n, d_cell, d_cursor, d_keys);
 }
 
@@ -278,13 +221,12 @@ int feature_grid_cells(int device, hipStream_t st, const deftri_feature_grid &gr
     DevArena A;
     float *d_uv;
     int *d_cell, *d_keys, *d_count, *d_cursor, *d_start;
-    A.add(&d_uv, 2 * N);
+    A.in(&d_uv, uv, 2 * N);
     A.add(&d_cell, N); A.add(&d_keys, N); A.add(&d_count, ncell); A.add(&d_cursor, ncell); A.add(&d_start, ncell + 1);
-    if (!A.commit()) {
+    if (!A.commit(st)) {
         err = "feature_grid_cells: allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_uv, uv, 8 * N, hipMemcpyHostToDevice, st);
     launch_grid(G, n, d_uv, d_cell, d_count, d_start, d_cursor, d_keys, st);
     hipMemcpyAsync(cell_start, d_start, 4 * (ncell + 1), hipMemcpyDeviceToHost, st);
     const hipError_t e = hipStreamSynchronize(st);
@@ -300,12 +242,15 @@ int match_for_initialization(int device, hipStream_t st, const deftri_feature_gr
                              const int32_t *octave2, const uint8_t *desc2, int32_t th, float window_size_factor,
                              int32_t *matches, int32_t *best_dist, int32_t *second_dist, int32_t *n_matches,
                              std::string &err) {
+    const char *name = "match_for_initialization";
     const std::string why = grid_error(grid);
     if (!why.empty()) {
-        err = "match_for_initialization: " + why;
+        err = std::string(name) + ": " + why;
         return DEFTRI_E_ARG;
     }
-    if (!octaves_ok(grid, n1, octave1, "reference", err) || !octaves_ok(grid, n2, octave2, "current", err)) return DEFTRI_E_ARG;
+    if (!octaves_ok(name, "reference keypoint", grid, n1, octave1, nullptr, err) ||
+        !octaves_ok(name, "current keypoint", grid, n2, octave2, nullptr, err))
+        return DEFTRI_E_ARG;
     const GridGeom G = geometry(grid);
     const float radius = window_size_factor * 1 * scale_factor(grid, 0);   // :69, octave 0 (the only one searched)
     *n_matches = 0;
@@ -319,47 +264,22 @@ int match_for_initialization(int device, hipStream_t st, const deftri_feature_gr
     }
     if (device < 0) {
         const auto cells = host_grid(G, n2, uv2);
-        std::vector<int32_t> to_check;
         int nm = 0;
         for (int32_t i = 0; i < n1; i++) {
             matches[i] = -1;                                           // :40
             if (best_dist) best_dist[i] = 255;
             if (second_dist) second_dist[i] = 255;
             if (octave1[i] > 0) continue;                              // :56
-            const float x = uv1[2 * i], y = uv1[2 * i + 1];
             const int last_octave = octave1[i];
             const float rad = window_size_factor * 1 * scale_factor(grid, last_octave);
-            // getFeaturesInArea(x, y, rad, last_octave - 1, last_octave + 1) (Frame.cc:288-323)
-            to_check.clear();
-            int cmin, rmin, cmax, rmax;
-            cell_range(G, x, y, rad, cmin, rmin, cmax, rmax);
-            for (int c = cmin; c <= cmax; c++)
-                for (int r = rmin; r <= rmax; r++)
-                    for (int32_t key : cells[(size_t)c * G.rows + r]) {
-                        const int o = octave2[key];
-                        if (o >= last_octave - 1 && o <= last_octave + 1) {
-                            const float px = uv2[2 * key] - x, py = uv2[2 * key + 1] - y;
-                            if (fabsf(px) < rad && fabsf(py) < rad) to_check.push_back(key);
-                        }
-                    }
-            int best = 255, second = 255;                              // :76-90
-            int32_t best_idx = -1;
-            for (int32_t j : to_check) {
-                const int dist = hamming(desc1 + 32 * (size_t)i, desc2 + 32 * (size_t)j);
-                if (dist < best) {
-                    second = best;
-                    best = dist;
-                    best_idx = j;
-                } else if (dist < second) {
-                    second = dist;
-                }
-            }
-            if (accept_match(best, second, th)) {                      // :92-95
-                matches[i] = best_idx;
+            const WindowBest w = host_window_best(G, cells, uv2, octave2, desc2, uv1[2 * i], uv1[2 * i + 1], rad, last_octave,
+                                                  desc1 + 32 * (size_t)i, [](int32_t) { return false; });
+            if (accept_match(w.best, w.second, th)) {                  // :92-95
+                matches[i] = w.idx;
                 nm++;
             }
-            if (best_dist) best_dist[i] = best;
-            if (second_dist) second_dist[i] = second;
+            if (best_dist) best_dist[i] = w.best;
+            if (second_dist) second_dist[i] = w.second;
         }
         *n_matches = nm;
         return 0;
@@ -370,20 +290,14 @@ int match_for_initialization(int device, hipStream_t st, const deftri_feature_gr
     float *d_uv1, *d_uv2;
     int *d_oct1, *d_oct2, *d_cell, *d_keys, *d_count, *d_cursor, *d_start, *d_match, *d_best, *d_second, *d_total;
     uint4 *d_desc1, *d_desc2;
-    A.add(&d_uv1, 2 * N1); A.add(&d_oct1, N1); A.add(&d_desc1, 2 * N1);
-    A.add(&d_uv2, 2 * N2); A.add(&d_oct2, N2); A.add(&d_desc2, 2 * N2);
+    A.in(&d_uv1, uv1, 2 * N1); A.in(&d_oct1, octave1, N1); A.in(&d_desc1, desc1, 2 * N1);
+    A.in(&d_uv2, uv2, 2 * N2); A.in(&d_oct2, octave2, N2); A.in(&d_desc2, desc2, 2 * N2);
     A.add(&d_cell, N2); A.add(&d_keys, N2); A.add(&d_count, ncell); A.add(&d_cursor, ncell); A.add(&d_start, ncell + 1);
     A.add(&d_match, N1); A.add(&d_best, N1); A.add(&d_second, N1); A.add(&d_total, 1);
-    if (!A.commit()) {
+    if (!A.commit(st)) {
         err = "match_for_initialization: allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_uv1, uv1, 8 * N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_oct1, octave1, 4 * N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_desc1, desc1, 32 * N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_uv2, uv2, 8 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_oct2, octave2, 4 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_desc2, desc2, 32 * N2, hipMemcpyHostToDevice, st);
     hipMemsetAsync(d_total, 0, sizeof(int), st);
     launch_grid(G, n2, d_uv2, d_cell, d_count, d_start, d_cursor, d_keys, st);
     hipLaunchKernelGGL(dev::k_match_init, dim3((n1 + 3) / 4), dim3(256), 0, st, n1, d_uv1, d_oct1, d_desc1, d_uv2, d_oct2,
@@ -432,14 +346,12 @@ int epipolar_inliers(int device, hipStream_t st, int32_t n, const float *uv1, co
     float *d_uv1, *d_uv2, *d_err;
     uint8_t *d_in;
     int *d_part;
-    A.add(&d_uv1, 2 * N); A.add(&d_uv2, 2 * N); A.add(&d_in, N); A.add(&d_err, N); A.add(&d_part, nb);
-    if (!A.commit()) {
+    A.in(&d_uv1, uv1, 2 * N); A.in(&d_uv2, uv2, 2 * N); A.add(&d_in, N); A.add(&d_err, N); A.add(&d_part, nb);
+    if (!A.commit(st)) {
         err = "epipolar_inliers: allocation failed";
         return DEFTRI_E_HIP;
     }
     std::vector<int> part(nb);
-    hipMemcpyAsync(d_uv1, uv1, 8 * N, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_uv2, uv2, 8 * N, hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(dev::k_epipolar_inliers, dim3((unsigned)nb), dim3(256), 0, st, n, d_uv1, d_uv2, k1, k2, E, epipolar_th,
                        d_in, d_err, d_part);
     hipMemcpyAsync(inlier, d_in, N, hipMemcpyDeviceToHost, st);

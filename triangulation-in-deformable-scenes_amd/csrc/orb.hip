@@ -25,6 +25,7 @@
 #include <cstring>
 #include <vector>
 
+#include "dev_arena.h"
 #include "orb.h"
 
 namespace deftri {
@@ -171,19 +172,7 @@ OrbState::~OrbState() {
 namespace {
 
 using Clock = std::chrono::steady_clock;
-double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
-
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-int arg_fail(std::string &err, const std::string &why) {
-    err = "orb_describe: " + why;
-    return DEFTRI_E_ARG;
-}
-
-int cv_round(float v) { return (int)lrintf(v); }   // round half to even
+const char *const kEntry = "orb_describe";   // what every argument error of this file starts with
 
 // everything the image size and the parameters decide
 struct Plan {
@@ -196,9 +185,9 @@ struct Plan {
 };
 
 int make_plan(const FastImage &im, const deftri_orb_params &p, Plan &P, std::string &err) {
-    if (p.n_scales < 1 || p.n_scales > DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, "n_scales must be in [1, 16]");
-    if (!(p.scale_factor > 1.0f)) return arg_fail(err, "scale_factor must be > 1");
-    if (im.rows < 1 || im.cols < 1 || im.stride < im.cols) return arg_fail(err, "stride < cols, or an empty image");
+    if (p.n_scales < 1 || p.n_scales > DEFTRI_FAST_MAX_LEVELS) return arg_fail(err, kEntry, "n_scales must be in [1, 16]");
+    if (!(p.scale_factor > 1.0f)) return arg_fail(err, kEntry, "scale_factor must be > 1");
+    if (im.rows < 1 || im.cols < 1 || im.stride < im.cols) return arg_fail(err, kEntry, "stride < cols, or an empty image");
     const int n = P.n_levels = p.n_scales;
     float scale = 1.0f;                                                    // ORB.h:42-49
     for (int l = 0; l < n; l++) {
@@ -208,9 +197,9 @@ int make_plan(const FastImage &im, const deftri_orb_params &p, Plan &P, std::str
         P.rows[l] = cv_round((float)im.rows * P.inv_scale[l]);
         const std::string at = "level " + std::to_string(l) + " (" + std::to_string(P.cols[l]) + " x " + std::to_string(P.rows[l]) + ")";
         if (P.cols[l] < kBorder + 1 || P.rows[l] < kBorder + 1)
-            return arg_fail(err, at + " is below the 20 pixels a side the 19-pixel reflected border needs");
+            return arg_fail(err, kEntry, at + " is below the 20 pixels a side the 19-pixel reflected border needs");
         if (l && P.cols[l - 1] == 2 * P.cols[l] && P.rows[l - 1] == 2 * P.rows[l])
-            return arg_fail(err, at + " halves the level above it exactly: cv::resize takes its area path, which is not restated");
+            return arg_fail(err, kEntry, at + " halves the level above it exactly: cv::resize takes its area path, which is not restated");
         if (l) {
             P.xt[l] = resize_taps(P.cols[l - 1], P.cols[l]);
             P.yt[l] = resize_taps(P.rows[l - 1], P.rows[l]);
@@ -331,13 +320,13 @@ int run(OrbState &S, int device, hipStream_t st, const FastImage &im, const deft
     if (const int rc = make_plan(im, p, P, err)) return rc;
     const int nl = P.n_levels;
     const bool probe = probe_level >= 0;
-    if (probe_level >= nl) return arg_fail(err, "level outside [0, n_scales)");
+    if (probe_level >= nl) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     if (!probe) {
-        if (n < 0) return arg_fail(err, "n < 0");
-        if (!S.have_pattern) return arg_fail(err, "no pattern set: pass the 512 sampling points to deftri_orb_set_pattern first");
+        if (n < 0) return arg_fail(err, kEntry, "n < 0");
+        if (!S.have_pattern) return arg_fail(err, kEntry, "no pattern set: pass the 512 sampling points to deftri_orb_set_pattern first");
         for (int32_t i = 0; i < n; i++)
             if (octave[i] < 0 || octave[i] >= nl)
-                return arg_fail(err, "keypoint " + std::to_string(i) + ": octave " + std::to_string(octave[i]) + " outside [0, n_scales)");
+                return arg_fail(err, kEntry, "keypoint " + std::to_string(i) + ": octave " + std::to_string(octave[i]) + " outside [0, n_scales)");
     }
     deftri_orb_report R{};
     R.n_levels = nl;
@@ -475,10 +464,10 @@ int orb_describe(OrbState &S, int device, hipStream_t st, const FastImage &image
 
 int orb_pyramid_level(OrbState &S, int device, hipStream_t st, const FastImage &image, const deftri_orb_params &p, int32_t level,
                       uint8_t *out, int32_t *out_rows, int32_t *out_cols, std::string &err) {
-    if (level < 0) return arg_fail(err, "level outside [0, n_scales)");
+    if (level < 0) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     Plan P;
     if (const int rc = make_plan(image, p, P, err)) return rc;
-    if (level >= P.n_levels) return arg_fail(err, "level outside [0, n_scales)");
+    if (level >= P.n_levels) return arg_fail(err, kEntry, "level outside [0, n_scales)");
     *out_rows = P.rows[level] + 2 * kBorder;
     *out_cols = P.cols[level] + 2 * kBorder;
     return run(S, device, st, image, p, 0, nullptr, nullptr, nullptr, nullptr, nullptr, level, out, nullptr, err);

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <type_traits>
 
+#include "dev_arena.h"
 #include "spcg.h"
 
 namespace deftri {
@@ -664,10 +665,6 @@ unsigned grid_for(int64_t n, int per_block = kBlk) {
 }
 
 size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-double ms_since(std::chrono::steady_clock::time_point t) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-}
 
 const bool g_timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
 

@@ -155,10 +155,9 @@ __global__ void k_prepare_points(int n, int mode, ProjCam C, const float *__rest
     o.match[i] = -1; o.best[i] = 255; o.second[i] = 255;
 }
 
-// One wave per point (4 per workgroup), as k_match_init: a column of the cell range is one run of
-// cell_keys, the lanes stride over it.  claim_prev: the previous round's table; a candidate with
-// claim_prev[j] < i is skipped entirely (:138-140, :230-232) but counts as a candidate for the emptiness
-// test (:220).  match [n] holds the previous round's result on entry.
+// One wave per point (4 per workgroup), as k_match_init (wave_window_best).  claim_prev: the previous
+// round's table; a candidate with claim_prev[j] < i is skipped entirely (:138-140, :230-232) but counts as a
+// candidate for the emptiness test (:220).  match [n] holds the previous round's result on entry.
 __global__ void __launch_bounds__(256)
 k_match_round(int n, const float *__restrict__ px, const float *__restrict__ py, const float *__restrict__ pradius,
               const int *__restrict__ poctave, const uint4 *__restrict__ desc, const float *__restrict__ uv2,
@@ -171,43 +170,15 @@ k_match_round(int n, const float *__restrict__ px, const float *__restrict__ py,
     if (i >= n) return;
     const int st0 = status[i];
     if (st0 != ST_MATCHED && st0 != ST_NO_CANDIDATES && st0 != ST_REJECTED) return;   // decided by k_prepare_points
-    const float x = px[i], y = py[i], radius = pradius[i];
-    const int oct = poctave[i];
-    const int min_level = oct - 1, max_level = oct + 1;
-    int b = 255, s = 255, idx = -1, ncand = 0;
-    int cmin, rmin, cmax, rmax;
-    cell_range(G, x, y, radius, cmin, rmin, cmax, rmax);
-    const uint4 a0 = desc[2 * (size_t)i], a1 = desc[2 * (size_t)i + 1];
-    for (int c = cmin; c <= cmax; c++) {
-        if (rmin > rmax) break;
-        const int k0 = cell_start[c * G.rows + rmin], k1 = cell_start[c * G.rows + rmax + 1];
-        for (int k = k0 + lane; k < k1; k += 64) {
-            const int j = cell_keys[k];
-            const int o = octave2[j];
-            if (o < min_level || o > max_level) continue;                       // Frame.cc:315
-            const float dx = uv2[2 * j] - x, dy = uv2[2 * j + 1] - y;
-            if (!(fabsf(dx) < radius && fabsf(dy) < radius)) continue;          // :317
-            ncand++;
-            if (claim_prev[j] < i) continue;                                    // getMapPoint(j)
-            const int d = hamming256(a0, a1, desc2[2 * (size_t)j], desc2[2 * (size_t)j + 1]);
-            if (d < b) { s = b; b = d; idx = j; }
-            else {
-                if (d < s) s = d;
-                if (d == b && d < 255 && j < idx) idx = j;
-            }
-        }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-        const int b2 = __shfl_xor(b, off, 64), s2 = __shfl_xor(s, off, 64), i2 = __shfl_xor(idx, off, 64);
-        join_best(b, s, idx, b2, s2, i2);
-        ncand += __shfl_xor(ncand, off, 64);
-    }
+    const WindowBest w = wave_window_best(G, cell_start, cell_keys, uv2, octave2, desc2, px[i], py[i], pradius[i], poctave[i],
+                                          desc[2 * (size_t)i], desc[2 * (size_t)i + 1], lane,
+                                          [=](int j) { return claim_prev[j] < i; });   // getMapPoint(j)
     if (lane == 0) {
-        const bool ok = ncand > 0 && accept_match(b, s, th);
-        const int m = ok ? idx : -1;
-        status[i] = (uint8_t)(ncand == 0 ? ST_NO_CANDIDATES : ok ? ST_MATCHED : ST_REJECTED);
-        best_out[i] = b;
-        second_out[i] = s;
+        const bool ok = w.ncand > 0 && accept_match(w.best, w.second, th);
+        const int m = ok ? w.idx : -1;
+        status[i] = (uint8_t)(w.ncand == 0 ? ST_NO_CANDIDATES : ok ? ST_MATCHED : ST_REJECTED);
+        best_out[i] = w.best;
+        second_out[i] = w.second;
         if (m != match[i]) {
             match[i] = m;
             *changed = 1;
@@ -320,15 +291,6 @@ k_map_point_descriptors(int n, const float *__restrict__ pos, const int *__restr
 using namespace dev;
 
 namespace {
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // vScaleFactor_ (Frame.cc:65-70)
 std::vector<float> scale_table(int n_scales, float factor) {
     std::vector<float> s((size_t)n_scales);
@@ -387,19 +349,9 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
         err = std::string(name) + ": windowSizeFactor outside [0, 2^20]";
         return DEFTRI_E_ARG;
     }
-    for (int32_t j = 0; j < a.n2; j++)
-        if (a.octave2[j] < 0 || a.octave2[j] >= grid.n_scales) {
-            err = std::string(name) + ": current keypoint " + std::to_string(j) + " has octave " + std::to_string(a.octave2[j]) +
-                  ", outside [0, nScales = " + std::to_string(grid.n_scales) + ")";
-            return DEFTRI_E_ARG;
-        }
-    if (a.guided)
-        for (int32_t i = 0; i < a.n; i++)
-            if (a.has_point[i] && (a.octave1[i] < 0 || a.octave1[i] >= grid.n_scales)) {
-                err = std::string(name) + (a.fuse ? ": map point " : ": reference keypoint ") + std::to_string(i) + " has octave " + std::to_string(a.octave1[i]) +
-                      ", outside [0, nScales = " + std::to_string(grid.n_scales) + ")";
-                return DEFTRI_E_ARG;
-            }
+    if (!octaves_ok(name, "current keypoint", grid, a.n2, a.octave2, nullptr, err)) return DEFTRI_E_ARG;
+    if (a.guided && !octaves_ok(name, a.fuse ? "map point" : "reference keypoint", grid, a.n, a.octave1, a.has_point, err))
+        return DEFTRI_E_ARG;
     if (a.n == 0 || a.n2 == 0) {                              // nothing beyond the report
         if (a.report) {
             std::memset(a.report, 0, sizeof(*a.report));
@@ -419,7 +371,7 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
 
     if (device < 0) {
         const auto cells = host_grid(G, n2, a.uv2);
-        std::vector<int32_t> slot = slot_in, to_check;
+        std::vector<int32_t> slot = slot_in;
         for (int32_t i = 0; i < n; i++) {
             const V3 X = v3(a.pos[3 * i], a.pos[3 * i + 1], a.pos[3 * i + 2]);
             PointPrep p;
@@ -431,49 +383,26 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
                 p = prepare_projection(C, X, v3(a.normal[3 * i], a.normal[3 * i + 1], a.normal[3 * i + 2]), a.min_dist[i],
                                        a.max_dist[i], grid.n_scales, scale.data(), log_scale1);
             }
-            int best = 255, second = 255, status = p.status;
-            int32_t best_idx = -1, m = -1;
+            WindowBest w{255, 255, -1, 0};
+            int status = p.status;
+            int32_t m = -1;
             if (status == 0) {
-                // getFeaturesInArea(uv.x, uv.y, radius, octave - 1, octave + 1) (Frame.cc:288-323)
-                to_check.clear();
-                int cmin, rmin, cmax, rmax;
-                cell_range(G, p.x, p.y, p.radius, cmin, rmin, cmax, rmax);
-                for (int c = cmin; c <= cmax; c++)
-                    for (int r = rmin; r <= rmax; r++)
-                        for (int32_t key : cells[(size_t)c * G.rows + r]) {
-                            const int o = a.octave2[key];
-                            if (o >= p.octave - 1 && o <= p.octave + 1) {
-                                const float dx = a.uv2[2 * key] - p.x, dy = a.uv2[2 * key + 1] - p.y;
-                                if (fabsf(dx) < p.radius && fabsf(dy) < p.radius) to_check.push_back(key);
-                            }
-                        }
-                if (to_check.empty()) status = ST_NO_CANDIDATES;              // :220
-                else {
-                    for (int32_t j : to_check) {
-                        if (slot[j] != -1) continue;                          // :230-232
-                        const int dist = hamming(a.desc + 32 * (size_t)i, a.desc2 + 32 * (size_t)j);
-                        if (dist < best) {
-                            second = best;
-                            best = dist;
-                            best_idx = j;
-                        } else if (dist < second) {
-                            second = dist;
-                        }
-                    }
-                    if (accept_match(best, second, a.th)) {                   // :246-249
-                        if (!a.fuse) slot[best_idx] = i;                      // fuse: the slots are the caller's to edit
-                        m = best_idx;
-                        status = ST_MATCHED;
-                    } else status = ST_REJECTED;
-                }
+                w = host_window_best(G, cells, a.uv2, a.octave2, a.desc2, p.x, p.y, p.radius, p.octave, a.desc + 32 * (size_t)i,
+                                     [&](int32_t j) { return slot[j] != -1; });   // :230-232
+                if (w.ncand == 0) status = ST_NO_CANDIDATES;                  // :220
+                else if (accept_match(w.best, w.second, a.th)) {              // :246-249
+                    if (!a.fuse) slot[w.idx] = i;                             // fuse: the slots are the caller's to edit
+                    m = w.idx;
+                    status = ST_MATCHED;
+                } else status = ST_REJECTED;
             }
             a.match[i] = m;
             a.status[i] = (uint8_t)status;
             if (a.uv) { a.uv[2 * i] = p.x; a.uv[2 * i + 1] = p.y; }
             if (a.view_cos) a.view_cos[i] = p.view_cos;
             if (a.predicted_octave) a.predicted_octave[i] = p.octave;
-            if (a.best) a.best[i] = best;
-            if (a.second) a.second[i] = second;
+            if (a.best) a.best[i] = w.best;
+            if (a.second) a.second[i] = w.second;
         }
         if (a.slot_point) std::memcpy(a.slot_point, slot.data(), sizeof(int32_t) * (size_t)n2);
         const double total = ms_since(t0);
@@ -489,35 +418,25 @@ int projection_match(int device, hipStream_t st, const ProjectionMatchArgs &a, s
     int *d_base, *d_claim[2], *d_changed;
     uint8_t *d_has, *d_status;
     uint4 *d_desc, *d_desc2;
-    A.add(&d_pos, 3 * N); A.add(&d_normal, 3 * N); A.add(&d_min, N); A.add(&d_max, N); A.add(&d_has, N); A.add(&d_oct1, N);
-    A.add(&d_desc, 2 * N); A.add(&d_scale, scale.size());
-    A.add(&d_uv2, 2 * N2); A.add(&d_oct2, N2); A.add(&d_desc2, 2 * N2);
+    std::vector<int32_t> base(N2);
+    for (size_t j = 0; j < N2; j++) base[j] = slot_in[j] != -1 ? -1 : INT_MAX;
+    A.in(&d_pos, a.pos, 3 * N);
+    if (a.guided) {                                           // each mode uploads what its prepare step reads
+        A.add(&d_normal, 3 * N); A.add(&d_min, N); A.add(&d_max, N); A.in(&d_has, a.has_point, N); A.in(&d_oct1, a.octave1, N);
+    } else {
+        A.in(&d_normal, a.normal, 3 * N); A.in(&d_min, a.min_dist, N); A.in(&d_max, a.max_dist, N); A.add(&d_has, N); A.add(&d_oct1, N);
+    }
+    A.in(&d_desc, a.desc, 2 * N); A.in(&d_scale, scale.data(), scale.size());
+    A.in(&d_uv2, a.uv2, 2 * N2); A.in(&d_oct2, a.octave2, N2); A.in(&d_desc2, a.desc2, 2 * N2);
     A.add(&d_cell, N2); A.add(&d_keys, N2); A.add(&d_count, ncell); A.add(&d_cursor, ncell); A.add(&d_start, ncell + 1);
     A.add(&d_x, N); A.add(&d_y, N); A.add(&d_radius, N); A.add(&d_cos, N); A.add(&d_octave, N); A.add(&d_status, N);
     A.add(&d_match, N); A.add(&d_best, N); A.add(&d_second, N);
-    A.add(&d_base, N2); A.add(&d_claim[0], N2); A.add(&d_claim[1], N2); A.add(&d_changed, 1);
-    if (!A.commit()) {
+    A.in(&d_base, base.data(), N2); A.add(&d_claim[0], N2); A.add(&d_claim[1], N2); A.add(&d_changed, 1);
+    if (!A.commit(st)) {
         err = std::string(name) + ": allocation failed";
         return DEFTRI_E_HIP;
     }
-    std::vector<int32_t> base(N2);
-    for (size_t j = 0; j < N2; j++) base[j] = slot_in[j] != -1 ? -1 : INT_MAX;
-    hipMemcpyAsync(d_pos, a.pos, 12 * N, hipMemcpyHostToDevice, st);
-    if (a.guided) {
-        hipMemcpyAsync(d_has, a.has_point, N, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_oct1, a.octave1, 4 * N, hipMemcpyHostToDevice, st);
-    } else {
-        hipMemcpyAsync(d_normal, a.normal, 12 * N, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_min, a.min_dist, 4 * N, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_max, a.max_dist, 4 * N, hipMemcpyHostToDevice, st);
-    }
-    hipMemcpyAsync(d_desc, a.desc, 32 * N, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_scale, scale.data(), 4 * scale.size(), hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_uv2, a.uv2, 8 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_oct2, a.octave2, 4 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_desc2, a.desc2, 32 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_base, base.data(), 4 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_claim[0], d_base, 4 * N2, hipMemcpyDeviceToDevice, st);
+    hipMemcpyAsync(d_claim[0], d_base, 4 * N2, hipMemcpyDeviceToDevice, st);   // after d_base's upload
     launch_grid(G, n2, d_uv2, d_cell, d_count, d_start, d_cursor, d_keys, st);
     const PrepOut po{d_x, d_y, d_radius, d_cos, d_octave, d_match, d_best, d_second, d_status};
     hipLaunchKernelGGL(dev::k_prepare_points, dim3((n + 255) / 256), dim3(256), 0, st, n,
@@ -681,27 +600,14 @@ int map_point_descriptors(int device, hipStream_t st, int32_t n, const float *po
     int *d_obs_start, *d_obs_kf, *d_obs_slot, *d_kf_start, *d_kf_octave, *d_ref;
     uint4 *d_kf_desc, *d_desc;
     uint8_t *d_status;
-    A.add(&d_pos, 3 * N); A.add(&d_obs_start, N + 1); A.add(&d_obs_kf, NO); A.add(&d_obs_slot, NO);
-    A.add(&d_centre, 3 * NK); A.add(&d_kf_start, NK + 1); A.add(&d_kf_desc, 2 * NS); A.add(&d_kf_octave, NS);
-    A.add(&d_scale, scale.size());
+    A.in(&d_pos, pos, 3 * N); A.in(&d_obs_start, obs_start, N + 1); A.in(&d_obs_kf, obs_kf, NO); A.in(&d_obs_slot, obs_slot, NO);
+    A.in(&d_centre, centre.data(), 3 * NK); A.in(&d_kf_start, kf_slot_start, NK + 1); A.in(&d_kf_desc, kf_desc, 2 * NS);
+    A.in(&d_kf_octave, kf_octave, NS); A.in(&d_scale, scale.data(), scale.size());
     A.add(&d_normal, 3 * N); A.add(&d_max, N); A.add(&d_min, N); A.add(&d_desc, 2 * N); A.add(&d_ref, N); A.add(&d_status, N);
-    if (!A.commit()) {
+    if (!A.commit(st)) {
         err = std::string(name) + ": allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_pos, pos, 12 * N, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_obs_start, obs_start, 4 * (N + 1), hipMemcpyHostToDevice, st);
-    if (NO) {
-        hipMemcpyAsync(d_obs_kf, obs_kf, 4 * NO, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_obs_slot, obs_slot, 4 * NO, hipMemcpyHostToDevice, st);
-    }
-    if (NK) hipMemcpyAsync(d_centre, centre.data(), 12 * NK, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_kf_start, kf_slot_start, 4 * (NK + 1), hipMemcpyHostToDevice, st);
-    if (NS) {
-        hipMemcpyAsync(d_kf_desc, kf_desc, 32 * NS, hipMemcpyHostToDevice, st);
-        hipMemcpyAsync(d_kf_octave, kf_octave, 4 * NS, hipMemcpyHostToDevice, st);
-    }
-    hipMemcpyAsync(d_scale, scale.data(), 4 * scale.size(), hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(dev::k_map_point_descriptors, dim3((n + 3) / 4), dim3(256), 0, st, n, d_pos, d_obs_start, d_obs_kf, d_obs_slot,
                        d_centre, d_kf_start, d_kf_desc, d_kf_octave, (int)n_scales, d_scale, d_normal, d_max, d_min, d_desc, d_ref,
                        d_status);

@@ -12,7 +12,7 @@
 //                      ray2 = unproject(uv2).normalized()
 //   k_tri_candidates   one 64-lane wave per searched row, its descriptor in registers, the lanes striding
 //                      over j: the pairs with a free slot, dist <= min(50, th - 1) and the epipolar test
-//                      passed.  Run twice: a count pass, then k_tri_scan over the rows' counts, then a fill
+//                      passed.  Run twice: a count pass, then k_excl_scan over the rows' counts, then a fill
 //                      pass that writes (j, dist) compacted per row in ascending j — the position inside a
 //                      row comes from the wave's ballot and a prefix count, no atomics.
 //   one download of the row offsets and the lists, then the reference's loop over the lists: O(candidates).
@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "dev_arena.h"
+#include "dev_scan.h"
 #include "device_math.h"
 #include "matching_grid.h"
 #include "triangulation_matching.h"
@@ -120,48 +121,11 @@ k_tri_candidates(int n1, int n2, const uint8_t *__restrict__ has1, const uint8_t
     if (!FILL && lane == 0) count[i] = run;
 }
 
-// start [n + 1] = the exclusive prefix sums of count [n]; one workgroup, each thread a contiguous chunk
-__global__ void __launch_bounds__(256) k_tri_scan(int n, const unsigned long long *__restrict__ count,
-                                                  unsigned long long *__restrict__ start) {
-    __shared__ unsigned long long part[256];
-    const int t = threadIdx.x;
-    const long long chunk = ((long long)n + 255) / 256;
-    const long long lo = min((long long)n, t * chunk), hi = min((long long)n, lo + chunk);
-    unsigned long long s = 0;
-    for (long long k = lo; k < hi; k++) s += count[k];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        unsigned long long run = 0;
-        for (int q = 0; q < 256; q++) {
-            const unsigned long long v = part[q];
-            part[q] = run;
-            run += v;
-        }
-        start[n] = run;
-    }
-    __syncthreads();
-    unsigned long long run = part[t];
-    for (long long k = lo; k < hi; k++) {
-        start[k] = run;
-        run += count[k];
-    }
-}
-
 }  // namespace dev
 
 using namespace dev;
 
 namespace {
-int hip_fail(std::string &err, hipError_t e) {
-    err = std::string("search_for_triangulation: ") + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // what the loop keeps between rows (:269-274); vMatchedDistance and vnMatches21 sized by n2 (deftri.h)
 struct LoopState {
     std::vector<int32_t> matched_dist, match21;
@@ -288,24 +252,18 @@ int search_for_triangulation(int device, hipStream_t st, const TriangulationMatc
     float4 *d_ray1, *d_ray2;
     unsigned long long *d_count, *d_start;
     int *d_cand_j;
-    A.add(&d_uv1, 2 * N1); A.add(&d_uv2, 2 * N2); A.add(&d_desc1, 2 * N1); A.add(&d_desc2, 2 * N2);
-    A.add(&d_has1, N1); A.add(&d_has2, N2); A.add(&d_ray1, N1); A.add(&d_ray2, N2);
+    A.in(&d_uv1, a.uv1, 2 * N1); A.in(&d_uv2, a.uv2, 2 * N2); A.in(&d_desc1, a.desc1, 2 * N1); A.in(&d_desc2, a.desc2, 2 * N2);
+    A.in(&d_has1, a.has_point1, N1); A.in(&d_has2, a.has_point2, N2); A.add(&d_ray1, N1); A.add(&d_ray2, N2);
     A.add(&d_count, N1); A.add(&d_start, N1 + 1); A.add(&d_cand_j, (size_t)capacity); A.add(&d_cand_d, (size_t)capacity);
-    if (!A.commit()) {
+    if (!A.commit(st)) {
         err = "search_for_triangulation: allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_uv1, a.uv1, 8 * N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_uv2, a.uv2, 8 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_desc1, a.desc1, 32 * N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_desc2, a.desc2, 32 * N2, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_has1, a.has_point1, N1, hipMemcpyHostToDevice, st);
-    hipMemcpyAsync(d_has2, a.has_point2, N2, hipMemcpyHostToDevice, st);
     const unsigned n_ray_blocks = (unsigned)((N1 + N2 + 255) / 256), n_row_blocks = (unsigned)((N1 + 3) / 4);
     hipLaunchKernelGGL(dev::k_tri_rays, dim3(n_ray_blocks), dim3(256), 0, st, n1, n2, C, d_uv1, d_uv2, d_ray1, d_ray2);
     hipLaunchKernelGGL(dev::k_tri_candidates<false>, dim3(n_row_blocks), dim3(256), 0, st, n1, n2, d_has1, d_has2, d_desc1, d_desc2,
                        d_ray1, d_ray2, max_dist, a.epipolar_th, d_count, d_start, capacity, d_cand_j, d_cand_d);
-    hipLaunchKernelGGL(dev::k_tri_scan, dim3(1), dim3(256), 0, st, n1, d_count, d_start);
+    launch_excl_scan<unsigned long long, 256>(n1, d_count, d_start, nullptr, st);
     hipLaunchKernelGGL(dev::k_tri_candidates<true>, dim3(n_row_blocks), dim3(256), 0, st, n1, n2, d_has1, d_has2, d_desc1, d_desc2,
                        d_ray1, d_ray2, max_dist, a.epipolar_th, d_count, d_start, capacity, d_cand_j, d_cand_d);
     std::vector<unsigned long long> start(N1 + 1);
@@ -317,7 +275,7 @@ int search_for_triangulation(int device, hipStream_t st, const TriangulationMatc
         hipMemcpyAsync(cand_d.data(), d_cand_d, (size_t)capacity, hipMemcpyDeviceToHost, st);
     }
     hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return hip_fail(err, e);
+    if (e != hipSuccess) return hip_fail(err, "search_for_triangulation", e);
     int round_trips = 1;
     const unsigned long long total = start[N1];
     if (total > worst) {
@@ -341,7 +299,7 @@ int search_for_triangulation(int device, hipStream_t st, const TriangulationMatc
         hipMemcpyAsync(cand_j.data(), d_j2, 4 * (size_t)total, hipMemcpyDeviceToHost, st);
         hipMemcpyAsync(cand_d.data(), d_d2, (size_t)total, hipMemcpyDeviceToHost, st);
         e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return hip_fail(err, e);
+        if (e != hipSuccess) return hip_fail(err, "search_for_triangulation", e);
         round_trips++;
     }
     const double ms_device = ms_since(t0);

@@ -8,7 +8,7 @@
 // not been run against an OpenCV build.
 //   k_undistort            one thread per point (deftri_undistort_points)
 //   k_undistort_cells      one thread per slot: the undistorted key, its cell, in_grid and the cell's count
-//   then matching.hip's k_grid_scan / k_grid_fill / k_grid_order: the lists as a CSR in keypoint order
+//   then k_excl_scan (dev_scan.h) and matching.hip's k_grid_fill / k_grid_order: the lists as a CSR in keypoint order
 // The four corners are undistorted on the host on both contexts, by the same function: the kernels take the
 // grid geometry by value.  The keys stay on the device between undistortion and grid.
 //
@@ -58,11 +58,6 @@ __global__ void k_undistort_cells(int n, const float2 *__restrict__ uv_dis, int 
 using namespace dev;
 
 namespace {
-int hip_fail(std::string &err, const char *what, hipError_t e) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return DEFTRI_E_HIP;
-}
-
 // "" and the model, or what is wrong with the arguments
 std::string model_of(const float *calib, const float *dist, int32_t n_dist, UndistortModel &M) {
     if (n_dist != 0 && n_dist != 4 && n_dist != 5) return "n_dist = " + std::to_string(n_dist) + ", not 0, 4 or 5";
@@ -118,12 +113,11 @@ int undistort_points(int device, hipStream_t st, int32_t n, const float *uv_in, 
     const size_t N = (size_t)n;
     DevArena A;
     float2 *d_uv;
-    A.add(&d_uv, N);
-    if (!A.commit()) {
+    A.in(&d_uv, uv_in, N);
+    if (!A.commit(st)) {
         err = "undistort_points: allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_uv, uv_in, 8 * N, hipMemcpyHostToDevice, st);
     hipLaunchKernelGGL(dev::k_undistort, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, n, d_uv, M, d_uv);
     hipMemcpyAsync(uv_out, d_uv, 8 * N, hipMemcpyDeviceToHost, st);
     const hipError_t e = hipStreamSynchronize(st);
@@ -199,14 +193,13 @@ int distribute_features(int device, hipStream_t st, int32_t grid_cols, int32_t g
     float2 *d_dis, *d_uv;
     int *d_cell, *d_keys, *d_ordered, *d_count, *d_cursor, *d_start;
     uint8_t *d_in;
-    A.add(&d_dis, N); A.add(&d_uv, N);
+    A.in(&d_dis, uv_dis, N); A.add(&d_uv, N);
     A.add(&d_cell, N); A.add(&d_keys, N); A.add(&d_ordered, N); A.add(&d_count, ncell); A.add(&d_cursor, ncell);
     A.add(&d_start, ncell + 1); A.add(&d_in, N);
-    if (!A.commit()) {
+    if (!A.commit(st)) {
         err = "distribute_features: allocation failed";
         return DEFTRI_E_HIP;
     }
-    hipMemcpyAsync(d_dis, uv_dis, 8 * N, hipMemcpyHostToDevice, st);
     hipMemsetAsync(d_count, 0, sizeof(int) * ncell, st);
     hipMemsetAsync(d_ordered, 0xff, sizeof(int) * N, st);   // -1 behind the keys that are in the grid
     hipLaunchKernelGGL(dev::k_undistort_cells, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, n, d_dis, n_dist ? 1 : 0, M, G,

@@ -1277,11 +1277,23 @@ int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode);
    builder 0, on a host-only context or where the plan builder does not apply it has no effect.  DEFTRI_E_ARG: a
    mode other than 0 or 1.  deftri_debug_plan_digest with mode 1 honours this setting. */
 int deftri_set_tile_builder(deftri_ctx *ctx, int32_t mode);
+/* Who builds the plan's phase-1 blocks and phase-2 wave layout (stages 7 and 8b of csrc/spcg_plan.cpp: dperm, blk,
+   hv_blk, hv_blk_off; rowmap, woff, wsplit, pmap, pidx) wherever plan builder 1 and tile builder 1 both ran — the
+   device built the tile layout, not refused: 0 (default) the host; 1 the device stages of csrc/plan_dev.hip.  In an
+   upload the two slot arrays pmap and pidx then stay on the device and reach the solver by a device-to-device
+   copy (with DEFTRI_PLAN_DIGEST=1 they are downloaded for the digest).  The plan is equal array for array.  The
+   host builds stage 8b when 64 x its slot steps does not fit an int.  Anywhere else — plan or tile builder 0, a
+   host-only context, a refused tile layout, more than one pair, a sharded context — it has no effect.
+   DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the upload with DEFTRI_E_HIP.
+   deftri_debug_plan_digest with mode 1 honours this setting; every array then comes back to the host. */
+int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode);
 /* What the last iterative plan build of this context did: builder_used 0 / 1; stages = bit mask of
    the stages that ran on the device (bit 0 groups, 1 Morton order, 2 rows, 3 rotation numbering,
    4 rep/depth by row, 5 incidences; with deftri_set_tile_builder(1) also 6 groups and edges by group,
    7 partition, 8 entries and slots, 9 cross slots: 0x3ff for a full device build; bits 0-2 alone: the tile
-   layout was refused after them and the build went on on the host); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
+   layout was refused after them and the build went on on the host; with deftri_set_layout_builder(1) also
+   10 phase-1 blocks, 11 row sort and wave cut, 12 slot fill, set only when those stages ran: 0x1fff for a full
+   device build with all three switches); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
    2 a bounded loop reached its bound); ms = wall time of the build.  All zero before the first build. */
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
                            int32_t *reason, double *ms);
@@ -1295,6 +1307,12 @@ int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t
    context (mode 1 is then not applicable).  deftri_plan_build_info afterwards describes this build. */
 int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode,
                              int32_t tile, uint64_t *digests, int32_t cap, int32_t *n);
+/* TEST ONLY: build the plan exactly as deftri_debug_plan_digest does and write 8 figures of its phase-1 blocks and
+   wave layout, computed on the host from the finished plan: waves; waves with wsplit 1; waves whose 64-row
+   look-ahead covers rows of two sort windows; waves with zero steps; the slot steps (woff's last entry); phase-1
+   blocks; depth blocks among them; the largest hv_blk run.  cap < 8: DEFTRI_E_ARG.  Works on a host-only context. */
+int deftri_debug_plan_layout_stats(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile,
+                                   int64_t *out, int32_t cap);
 /* TEST ONLY: 1 when tris [3 * n_tris] is THE Delaunay triangulation of xy (delaunay_still_valid, the structure
    memo's exact certificate), else 0. */
 int deftri_debug_delaunay_still_valid(int32_t n, const double *xy, int32_t n_tris, const int32_t *tris);

@@ -2,7 +2,8 @@
 // stages 1-3, 5, 6 and 8) on the device (plan_dev.hip).  Every stage has a unique output — a stable sort from
 // ascending ids, component roots that are the smallest id, a first-encounter numbering — so the arrays are the
 // host's bit for bit.  With deftri_set_tile_builder the tile layout (spcg_tile.cpp build_tiles, stage 4a)
-// is built there too.
+// is built there too, and with deftri_set_layout_builder the phase-1 blocks and the phase-2 wave layout
+// (stages 7 and 8b), whose two slot arrays can stay on the device.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,7 +44,7 @@ class PlanDevice {
     // kernels, one download.  before_alloc: called (and cleared) before the arena grows
     int rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
              std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-             std::string &err, bool with_tiles = false);
+             std::string &err, bool with_tiles = false, bool with_layout = false);
     // stages 4-6 (rotation numbering, rep / depth edges by row, incidences) for H.arap_ids on the rows of the
     // last rows() call: one upload of arap_ids, the kernels, one download into H
     int edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &err);
@@ -56,6 +57,15 @@ class PlanDevice {
     // is downloaded for the host's build_tiles
     int tiles(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
               SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err);
+    // deftri_set_layout_builder: rows() with with_layout lays out the scratch of stages 7 and 8b
+    // and uploads dep_scale with the other inputs.
+    // layout() is those two stages on the arrays edges() left on the device: dperm, blk, hv_blk, hv_blk_off (ran
+    // bit 0), the window sort and the wave cut with rowmap, woff and wsplit (bit 1), the slot fill of pmap and pidx
+    // (bit 2).  The slot arrays stay on the device (H.pmap_dev, H.pidx_dev, H.slots_dev: valid until the next build
+    // on this arena) and come to H.pmap / H.pidx only with download_slots.  When 64 x slots does not fit an int only
+    // bit 0 is set and H keeps the host's stage 8b to do.  Returns 0, 1 (bound) or -1 (err)
+    int layout(const deftri_problem_desc &d, std::function<void()> *before_alloc, SpPlanHost &H, bool download_slots,
+               int32_t &ran, std::string &err);
 
  private:
     bool reserve(size_t dev_bytes, size_t pin_bytes, std::function<void()> *before_alloc);
@@ -65,19 +75,24 @@ class PlanDevice {
     int dev_;
     hipStream_t st_;
     char *buf_ = nullptr, *pin_ = nullptr, *tbuf_ = nullptr;     // tbuf_: the tile arrays (sized after the counts)
-    size_t cap_ = 0, pin_cap_ = 0, tcap_ = 0;
-    hipEvent_t ev_[24] = {};
+    char *sbuf_ = nullptr;                                       // the slot arrays pmap | pidx (sized after the cut)
+    size_t cap_ = 0, pin_cap_ = 0, tcap_ = 0, scap_ = 0;
+    hipEvent_t ev_[28] = {};
     // the arena's pieces (byte offsets), laid out by rows()
     struct Layout {
         size_t ap, rot, rep_point, dep_point, xy, par, root, flag, gid, grep, mm, lohi, key[2], id[2], hist, gpos, cur,
             part, dl1, hdr, por, rop, gp, dl1_end, aid, rv, first, rflag, kr, kd, ki, ioff, dl2, hdr2, rot_ids, arl, rep_ids,
             rep_off, dep_ids, dep_off, inc, inc_off, dl2_end,
             // the tile stages' scratch (with_tiles)
-            egi, egj, erow, ooff, oe, okj, pred, tioff, ie, tend, ja, jb, mark, midx, tstart, tne, tnh, tcut, thdr, total;
+            egi, egj, erow, ooff, oe, okj, pred, tioff, ie, tend, ja, jb, mark, midx, tstart, tne, tnh, tcut, thdr,
+            // stages 7 and 8b (with_layout); dl3 .. dl3_end is their download
+            dscale, dflag, bkey, boff, bord, blk0, order, scnt, wnext, wsteps, wsp, wja, wjb, wmark, widx, wsoff, dl3, lhdr,
+            dperm, blk, hvb, hvoff, rowmap, woff, wsplit, dl3_end, total;
     } L_{};
     bool with_tiles_ = false, order_on_dev_ = false;           // order_on_dev_: tiles() left arap_ids in L_.oe
+    bool with_layout_ = false;
     int32_t P_ = 0;
-    int64_t E_ = 0;
+    int64_t E_ = 0, nloc_ = -1;                                // nloc_: the local edges of the last edges(), -1 none
 };
 
 }  // namespace deftri

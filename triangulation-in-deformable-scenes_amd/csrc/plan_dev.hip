@@ -1,5 +1,5 @@
 // plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h), and
-// its tile layout (build_tiles of one rank).
+// its tile layout (build_tiles of one rank), its phase-1 blocks and its phase-2 wave layout (§5m).
 //
 // No workgroup waits on another: a scan over more than one workgroup's elements is three launches (tile sums,
 // the scan of the sums by one workgroup, the tiles' own scans), a sort by a dense key (a row, a group) is count,
@@ -32,7 +32,9 @@ static_assert(kRadixPasses * kPlanRadixBits == 42, "the passes cover the curve k
 static_assert(kPlanScanTile == 8 * kBlk && kPlanRadixTile == kBlk, "one workgroup per tile");
 enum { kHdrBound = 0, kHdrNg = 1, kHdrNrot = 2, kHdrWords = 16,
        // the tile stages' header: a condition build_tiles refuses, tiles, padded entries, halo rows, cut entries
-       kHdrRefuse = 3, kHdrNt = 4, kHdrEntries = 5, kHdrHalo = 6, kHdrCut = 7, kHdrSegmax = 8, kHdrLds = 9 };
+       kHdrRefuse = 3, kHdrNt = 4, kHdrEntries = 5, kHdrHalo = 6, kHdrCut = 7, kHdrSegmax = 8, kHdrLds = 9,
+       // the layout stages' header (stages 7 and 8b): waves, slot steps
+       kLhNw = 4, kLhSlots = 5 };
 
 namespace dev {
 
@@ -658,6 +660,182 @@ __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int
     }
 }
 
+// ---- stages 7 and 8b: phase-1 blocks and the phase-2 wave layout (spcg_plan.cpp) ---------------
+// One rank, one pair, at most two scales: every local ARAP edge has heavy vertex 0, the local depth edges are all
+// of them, a local row is its global row.  hdr: the layout's header (the words k_tile_jump reads stay 0)
+
+// flag [D + 1]: depth edge j (in dep_ids order) is of scale 0; its exclusive scan places the scale-0 edges
+__global__ __launch_bounds__(kBlk) void k_dep_flag(int D, const int *dep_ids, const int *dscale, int *flag) {
+    PLAN_FOR(j, (int64_t)D + 1) flag[j] = j < D ? dscale[dep_ids[j]] == 0 : 0;
+}
+
+// dperm: the local depth edges sorted stably by scale — scale 0 in order, then the rest in order (n0 = pos0[D])
+__global__ __launch_bounds__(kBlk) void k_dperm(int D, const int *dep_ids, const int *dscale, const int *pos0, int *dperm) {
+    const int n0 = pos0[D];
+    PLAN_FOR(j, D) {
+        const int p = pos0[j];
+        dperm[dscale[dep_ids[j]] == 0 ? p : n0 + ((int)j - p)] = (int)j;
+    }
+}
+
+// the blocks in the host's order of creation — owned ARAP, halo-only ARAP, depth scale 0, depth scale 1, each in
+// runs of kSpBlock — and each block's key, the row of its first edge's point
+__global__ __launch_bounds__(kBlk) void k_blk_make(int nb, int nao, int nloc, int n0, int D, const int *aid, const int *ap,
+                                                  const int *rop, const int *dep_point, const int *dep_ids, const int *dperm,
+                                                  const int *dscale, int4 *blk0, int *bkey) {
+    const int nb0 = (nao + kSpBlock - 1) / kSpBlock, nb1 = nb0 + (nloc - nao + kSpBlock - 1) / kSpBlock,
+              nb2 = nb1 + (n0 + kSpBlock - 1) / kSpBlock;
+    PLAN_FOR(b, nb) {
+        int kind = SP_ARAP, owned = 1, lo = 0, hi = nao, k = (int)b;
+        if (b >= nb2) { kind = SP_DEP; lo = n0; hi = D; k = (int)b - nb2; }
+        else if (b >= nb1) { kind = SP_DEP; hi = n0; k = (int)b - nb1; }
+        else if (b >= nb0) { owned = 0; lo = nao; hi = nloc; k = (int)b - nb0; }
+        const int begin = lo + k * kSpBlock, end = min(hi, begin + kSpBlock);
+        int hv = 0, key;
+        if (kind == SP_ARAP) key = rop[ap[4 * (int64_t)aid[begin]]];
+        else {
+            const int e = dep_ids[dperm[begin]];
+            hv = dscale[e];
+            key = rop[dep_point[e]];
+        }
+        blk0[b] = make_int4(kind | owned << 8, hv, begin, end);
+        bkey[b] = key;
+    }
+}
+
+// the dispatch order: sorted block s = x seg + j (segment x's j-th block) goes to the position it has in the
+// host's list "for j, for x: if x seg + j < nb" — the rows j' < j hold q + 1 blocks while j' <= r, else q
+__global__ __launch_bounds__(kBlk) void k_blk_deal(int nb, const int *bord, const int4 *blk0, int4 *blk) {
+    const int seg = (nb + 7) / 8, q = (nb - 1) / seg, r = (nb - 1) % seg;
+    PLAN_FOR(s, nb) {
+        const int x = (int)s / seg, j = (int)s % seg;
+        const int64_t pos = (int64_t)j * (q + 1) - max(0, j - r - 1) + x;
+        blk[pos] = blk0[bord[s]];
+    }
+}
+
+// hv_blk_off / hv_blk: per heavy vertex (nlist = Q + S <= 3) its blocks in final block order, by one workgroup
+__global__ __launch_bounds__(1024) void k_blk_heavy(int nb, int nlist, const int4 *blk, int *hvb, int *hvoff) {
+    __shared__ int s[1024];
+    int base = 0;
+    for (int h = 0; h < nlist && h < 3; h++) {
+        if (threadIdx.x == 0) hvoff[h] = base;
+        int carry = 0;
+        for (int b0 = 0; b0 < nb; b0 += 1024) {
+            const int b = b0 + threadIdx.x;
+            int f = 0;
+            if (b < nb) {
+                const int4 v = blk[b];
+                const int heavy = (v.x & 0xff) == SP_ARAP ? ((v.x >> 8) ? v.y : -1) : 1 + v.y;
+                f = heavy == h;
+            }
+            int tot;
+            const int ex = block_excl_scan(f, s, &tot);
+            if (f) hvb[base + carry + ex] = b;
+            carry += tot;
+        }
+        base += carry;
+    }
+    if (threadIdx.x == 0) hvoff[nlist] = base;
+}
+
+__device__ inline int row_slots(int l, const int *ioff, const int *doff) { return ioff[l + 1] - ioff[l] + doff[l + 1] - doff[l]; }
+
+// the rows of every window of kSpSortWindow by slot count, descending and stable: a row's place is the number of
+// larger counts plus the equal counts before it (one workgroup per window, one thread per row)
+__global__ __launch_bounds__(kSpSortWindow) void k_win_sort(int P, int nwin, const int *ioff, const int *doff, int *order, int *scnt) {
+    __shared__ int c[kSpSortWindow];
+    for (int w = blockIdx.x; w < nwin; w += gridDim.x) {
+        const int w0 = w * kSpSortWindow, n = min(kSpSortWindow, P - w0), t = threadIdx.x;
+        const int mine = t < n ? row_slots(w0 + t, ioff, doff) : -1;
+        c[t] = mine;
+        __syncthreads();
+        if (t < n) {
+            int rank = 0;
+            for (int u = 0; u < n; u++) {
+                const int v = c[u];
+                rank += (v > mine) | ((v == mine) & (u < t));
+            }
+            order[w0 + rank] = w0 + t;
+            scnt[w0 + rank] = mine;
+        }
+        __syncthreads();
+    }
+}
+
+// a wave starting at sorted row 32 g: split when the next 64 rows (to P, across windows) hold a count above
+// kSpWaveSplit; its steps from the rows it takes; the next wave's node.  Node ni ends the chain
+__global__ __launch_bounds__(kBlk) void k_wave_cut(int P, int ni, const int *scnt, int *wnext, int *wsteps, int *wsp) {
+    PLAN_FOR(g, (int64_t)ni + 1) {
+        if (g == ni) { wnext[g] = ni; wsteps[g] = 0; wsp[g] = 0; continue; }
+        const int i = 32 * (int)g;
+        int kmax = 0;
+        for (int j = 0; j < 64 && i + j < P; j++) kmax = max(kmax, scnt[i + j]);
+        const int sp = kSpWaveSplit > 0 && kmax > kSpWaveSplit;
+        const int nr = sp ? 32 : 64;
+        int steps = 0;
+        for (int j = 0; j < nr && i + j < P; j++) {
+            const int c = scnt[i + j];
+            steps = max(steps, sp ? (c + 1) / 2 : c);
+        }
+        wnext[g] = min(ni, (int)g + nr / 32);
+        wsteps[g] = steps;
+        wsp[g] = sp;
+    }
+}
+
+// the marked nodes are the waves: widx their flags, wsoff their steps (both ni + 1 entries, then scanned)
+__global__ __launch_bounds__(kBlk) void k_wave_marks(int ni, const int *mark, const int *wsteps, int *widx, int *wsoff) {
+    PLAN_FOR(g, (int64_t)ni + 1) {
+        const int m = g < ni && mark[g];
+        widx[g] = m;
+        wsoff[g] = m ? wsteps[g] : 0;
+    }
+}
+
+// rowmap, wsplit and woff of every wave (x = node << 6 | lane), the wave count and the slot steps
+__global__ __launch_bounds__(kBlk) void k_wave_write(int P, int ni, const int *mark, const int *widx, const int *wsoff, const int *wsp,
+                                                    const int *order, int *rowmap, int *woff, uint8_t *wsplit, int *hdr) {
+    PLAN_FOR(x, 64 * (int64_t)ni) {
+        if (x == 0) {
+            const int nw = widx[ni];
+            woff[nw] = wsoff[ni];
+            hdr[kLhNw] = nw;
+            hdr[kLhSlots] = wsoff[ni];
+        }
+        const int g = (int)(x >> 6), j = (int)(x & 63);
+        if (!mark[g]) continue;
+        const int w = widx[g], sp = wsp[g], i = 32 * g;
+        rowmap[64 * (int64_t)w + j] = j < (sp ? 32 : 64) && i + j < P ? order[i + j] : -1;
+        if (j == 0) { wsplit[w] = (uint8_t)sp; woff[w] = wsoff[g]; }
+    }
+}
+
+// one thread per (wave, lane) writes its row's slot list into the -1-filled pmap / pidx: the ARAP incidences, then
+// the depth couplings; a split row's second half goes to lane j + 32.  nsl: the slot steps (the arrays hold 64 nsl)
+__global__ __launch_bounds__(kBlk) void k_slot_fill(int nw, int nsl, const int *rowmap, const int *woff, const uint8_t *wsplit,
+                                                   const int *ioff, const int *inc, const int *doff, const int *dep_ids,
+                                                   const int *dscale, int *pmap, int *pidx, int *hdr) {
+    PLAN_FOR(x, 64 * (int64_t)nw) {
+        const int w = (int)(x >> 6), j = (int)(x & 63);
+        const bool sp = wsplit[w] != 0;
+        if (j >= (sp ? 32 : 64)) continue;
+        const int l = rowmap[x];
+        if (l < 0) continue;
+        const int a0 = ioff[l], na = ioff[l + 1] - a0, b0 = doff[l], size = na + doff[l + 1] - b0;
+        const int h = sp ? (size + 1) / 2 : size, base = woff[w];
+        if (size > 2 * kPlanRunMax || base + h > nsl) { hdr[kHdrBound] = 1; continue; }
+        for (int t = 0; t < size; t++) {
+            int pm, pi;
+            if (t < na) { pm = inc[a0 + t]; pi = pm >> 2; }
+            else { const int xd = b0 + t - na; pm = -(2 + xd); pi = -(2 + dscale[dep_ids[xd]]); }
+            const int64_t at = 64 * (int64_t)(base + (t < h ? t : t - h)) + (t < h ? j : j + 32);
+            pmap[at] = pm;
+            pidx[at] = pi;
+        }
+    }
+}
+
 }  // namespace dev
 
 unsigned grid_for(int64_t n, int per_block = kBlk) {
@@ -676,10 +854,11 @@ const bool g_timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     } while (0)
 
 PlanDevice::~PlanDevice() {
-    if (!buf_ && !pin_ && !tbuf_ && !ev_[0]) return;
+    if (!buf_ && !pin_ && !tbuf_ && !sbuf_ && !ev_[0]) return;
     hipSetDevice(dev_);
     if (buf_) hipFree(buf_);
     if (tbuf_) hipFree(tbuf_);
+    if (sbuf_) hipFree(sbuf_);
     if (pin_) hipHostFree(pin_);
     for (hipEvent_t e : ev_) if (e) hipEventDestroy(e);
 }
@@ -744,10 +923,12 @@ void PlanDevice::report(int first, int last, const char *const *names) const {
 
 int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
                      std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-                     std::string &err, bool with_tiles) {
+                     std::string &err, bool with_tiles, bool with_layout) {
     hipSetDevice(dev_);
     with_tiles_ = with_tiles;
+    with_layout_ = with_layout;
     order_on_dev_ = false;
+    nloc_ = -1;
     const int32_t P = d.n_points, NR = std::max(d.n_rot, 1);
     const int64_t E = d.n_arap, R = d.n_rep, D = d.n_depth;
     const size_t Pz = (size_t)P, Ez = (size_t)E;
@@ -755,7 +936,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     const double *xy = d.order_xy ? d.order_xy : d.points;
     const int rtile = (int)((Pz + kPlanRadixTile - 1) / kPlanRadixTile);
     const int mm_grid = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (P + kBlk - 1) / kBlk));
-    const int64_t scan_max = std::max<int64_t>({(int64_t)P + 1, (int64_t)kRadixDigits * rtile, 2 * E + 1});
+    const int64_t scan_max = std::max<int64_t>({(int64_t)P + 1, (int64_t)kRadixDigits * rtile, 2 * E + 1, D + 1});
     const size_t n_rot_cap = (size_t)std::min<int64_t>(NR, 2 * E);
     {
         size_t o = 0;
@@ -785,11 +966,24 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
             L.midx = piece(4 * (Pz + 2)); L.tstart = piece(4 * (Pz + 2)); L.tne = piece(4 * (Pz + 2)); L.tnh = piece(4 * (Pz + 2));
             L.tcut = piece(4 * (Pz + 2)); L.thdr = piece(4 * kHdrWords);
         }
+        L.dl3 = L.dl3_end = o;
+        if (with_layout) {
+            // at most nbm blocks, ni wave starts (every 32 rows) and as many waves
+            const size_t nbm = Ez / kSpBlock + (size_t)D / kSpBlock + 4, ni = (Pz + 31) / 32, Dz = (size_t)D;
+            L.dscale = piece(4 * Dz); L.dflag = piece(4 * (Dz + 1)); L.bkey = piece(4 * nbm); L.boff = piece(4 * (Pz + 1));
+            L.bord = piece(4 * nbm); L.blk0 = piece(16 * nbm); L.order = piece(4 * Pz); L.scnt = piece(4 * Pz);
+            L.wnext = piece(4 * (ni + 1)); L.wsteps = piece(4 * (ni + 1)); L.wsp = piece(4 * (ni + 1)); L.wja = piece(4 * (ni + 1));
+            L.wjb = piece(4 * (ni + 1)); L.wmark = piece(4 * (ni + 1)); L.widx = piece(4 * (ni + 1)); L.wsoff = piece(4 * (ni + 1));
+            L.dl3 = o;                                      // the layout's download: one region
+            L.lhdr = piece(4 * kHdrWords); L.dperm = piece(4 * Dz); L.blk = piece(16 * nbm); L.hvb = piece(4 * nbm);
+            L.hvoff = piece(4 * 4); L.rowmap = piece(4 * 64 * ni); L.woff = piece(4 * (ni + 1)); L.wsplit = piece(ni);
+            L.dl3_end = o;
+        }
         L.total = o;
     }
     const Layout &L = L_;
     P_ = P; E_ = E;
-    if (!reserve(L.total, std::max(L.dl1_end - L.dl1, L.dl2_end - L.dl2), before_alloc)) {
+    if (!reserve(L.total, std::max({L.dl1_end - L.dl1, L.dl2_end - L.dl2, L.dl3_end - L.dl3}), before_alloc)) {
         err = "plan builder: allocation failed";
         return -1;
     }
@@ -809,6 +1003,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     if (R > 0) hipMemcpyAsync(B + L.rep_point, d.rep_point, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
     if (D > 0) hipMemcpyAsync(B + L.dep_point, d.dep_point, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     hipMemcpyAsync(d_xy, xy, 8 * (size_t)stride * Pz, hipMemcpyHostToDevice, st_);
+    if (with_layout && D > 0) hipMemcpyAsync(B + L.dscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     hipEventRecord(ev_[1], st_);
     // 1. groups
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
@@ -891,6 +1086,7 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
         *d_dep_off = (int *)(B + L.dep_off), *d_inc = (int *)(B + L.inc);
     int64_t *d_inc_off = (int64_t *)(B + L.inc_off);
 
+    nloc_ = -1;
     hipEventRecord(ev_[6], st_);
     if (order_on_dev_ && nloc == E) hipMemcpyAsync(d_aid, B + L.oe, 4 * (size_t)nloc, hipMemcpyDeviceToDevice, st_);
     else hipMemcpyAsync(d_aid, H.arap_ids.data(), 4 * (size_t)nloc, hipMemcpyHostToDevice, st_);
@@ -949,6 +1145,7 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
     take(H.dep_off, L.dep_off, (size_t)P + 1);
     take(H.inc, L.inc, (size_t)n4);
     take(H.inc_off, L.inc_off, (size_t)P + 1);
+    nloc_ = nloc;
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> plan arrays", ms_since(t0));
     return 0;
 }
@@ -1122,6 +1319,162 @@ int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, i
     H.tile_halo_rows = nhr;
     order_on_dev_ = true;
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
+    return 0;
+}
+
+int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *before_alloc, SpPlanHost &H, bool download_slots,
+                       int32_t &ran, std::string &err) {
+    ran = 0;
+    hipSetDevice(dev_);
+    const Layout &L = L_;
+    const int32_t P = P_, S = d.n_scales;
+    const int64_t E = E_, D = d.n_depth, nloc = (int64_t)H.arap_ids.size();
+    const int32_t nao = H.n_arap_owned;
+    if (!buf_ || !with_layout_ || nloc_ < 0 || nloc_ != nloc || P != d.n_points || E != d.n_arap || d.n_pairs != 1 || S < 0 || S > 2 ||
+        nao < 0 || nao > nloc || (int64_t)H.dep_ids.size() != D || (D > 0 && S < 1) || H.lo != 0 || H.hi != P || P < 1) {
+        err = "plan builder: layout() without the edges of this problem";
+        return -1;
+    }
+    int n0 = 0;                                           // depth edges of scale 0
+    for (int64_t e = 0; e < D; e++) n0 += d.dep_scale[e] == 0;
+    auto blocks = [](int64_t n) { return (n + kSpBlock - 1) / kSpBlock; };
+    const int64_t nb = blocks(nao) + blocks(nloc - nao) + blocks(n0) + blocks(D - n0);
+    const int ni = (P + 31) / 32, nwin = (P + kSpSortWindow - 1) / kSpSortWindow;
+    if (nb > E / kSpBlock + D / kSpBlock + 4) { err = "plan builder: more phase-1 blocks than the arena holds"; return -1; }
+    // the wave layout's int scan: a row holds at most 2 kPlanRunMax slots, a wave's steps are one row's count
+    const bool waves = 16 * (int64_t)P < (1LL << 31);
+    char *B = buf_;
+    const int *d_ap = (const int *)(B + L.ap), *d_rop = (const int *)(B + L.rop), *d_aid = (const int *)(B + L.aid),
+              *d_dep_point = (const int *)(B + L.dep_point), *d_dep_ids = (const int *)(B + L.dep_ids),
+              *d_dep_off = (const int *)(B + L.dep_off), *d_ioff = (const int *)(B + L.ioff), *d_inc = (const int *)(B + L.inc);
+    const int *d_dscale = (const int *)(B + L.dscale);       // uploaded by rows() with the other inputs
+    int *d_dflag = (int *)(B + L.dflag), *d_bkey = (int *)(B + L.bkey), *d_boff = (int *)(B + L.boff),
+        *d_bord = (int *)(B + L.bord), *d_order = (int *)(B + L.order), *d_scnt = (int *)(B + L.scnt), *d_wnext = (int *)(B + L.wnext),
+        *d_wsteps = (int *)(B + L.wsteps), *d_wsp = (int *)(B + L.wsp), *d_wja = (int *)(B + L.wja), *d_wjb = (int *)(B + L.wjb),
+        *d_wmark = (int *)(B + L.wmark), *d_widx = (int *)(B + L.widx), *d_wsoff = (int *)(B + L.wsoff), *d_hdr = (int *)(B + L.lhdr),
+        *d_dperm = (int *)(B + L.dperm), *d_hvb = (int *)(B + L.hvb), *d_hvoff = (int *)(B + L.hvoff), *d_rowmap = (int *)(B + L.rowmap),
+        *d_woff = (int *)(B + L.woff);
+    int4 *d_blk0 = (int4 *)(B + L.blk0), *d_blk = (int4 *)(B + L.blk);
+    uint8_t *d_wsplit = (uint8_t *)(B + L.wsplit);
+
+    hipEventRecord(ev_[21], st_);
+    // 7. dperm, the blocks, their dispatch order, the heavy vertices' lists
+    hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
+    hipMemsetAsync(d_hvoff, 0, 4 * 4, st_);
+    LAUNCH(k_dep_flag, D + 1, (int)D, d_dep_ids, d_dscale, d_dflag);
+    scan(d_dflag, D + 1);
+    LAUNCH(k_dperm, D, (int)D, d_dep_ids, d_dscale, (const int *)d_dflag, d_dperm);
+    LAUNCH(k_blk_make, nb, (int)nb, (int)nao, (int)nloc, n0, (int)D, d_aid, d_ap, d_rop, d_dep_point, d_dep_ids, (const int *)d_dperm,
+           d_dscale, d_blk0, d_bkey);
+    sort_by_row(nb, d_bkey, P, d_boff, d_bord, d_hdr);
+    LAUNCH(k_blk_deal, nb, (int)nb, (const int *)d_bord, (const int4 *)d_blk0, d_blk);
+    hipLaunchKernelGGL(dev::k_blk_heavy, dim3(1), dim3(1024), 0, st_, (int)nb, 1 + S, (const int4 *)d_blk, d_hvb, d_hvoff);
+    hipEventRecord(ev_[22], st_);
+    // 8b. the windows' rows by slot count, the wave cut from every multiple of 32, the chain from row 0
+    if (waves) {
+        const int64_t nodes = (int64_t)ni + 1;
+        hipLaunchKernelGGL(dev::k_win_sort, dim3((unsigned)std::min(nwin, kGridMax)), dim3(kSpSortWindow), 0, st_, P, nwin, d_ioff,
+                           d_dep_off, d_order, d_scnt);
+        LAUNCH(k_wave_cut, nodes, P, ni, (const int *)d_scnt, d_wnext, d_wsteps, d_wsp);
+        hipMemsetAsync(d_wmark, 0, 4 * (size_t)nodes, st_);
+        LAUNCH(k_fill, 1, (int64_t)1, d_wmark, 1);
+        int rounds = 1;
+        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
+        const int *jin = d_wnext;
+        int *jout = d_wja;
+        for (int r = 0; r < rounds; r++) {
+            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, d_wmark, (const int *)d_hdr);
+            jin = jout;
+            jout = jout == d_wja ? d_wjb : d_wja;
+        }
+        LAUNCH(k_wave_marks, nodes, ni, (const int *)d_wmark, (const int *)d_wsteps, d_widx, d_wsoff);
+        scan(d_widx, nodes);
+        scan(d_wsoff, nodes);
+        LAUNCH(k_wave_write, 64 * (int64_t)ni, P, ni, (const int *)d_wmark, (const int *)d_widx, (const int *)d_wsoff, (const int *)d_wsp,
+               (const int *)d_order, d_rowmap, d_woff, d_wsplit, d_hdr);
+    }
+    hipEventRecord(ev_[23], st_);
+    hipMemcpyAsync(pin_, B + L.dl3, (waves ? L.dl3_end : L.rowmap) - L.dl3, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[24], st_);
+    hipError_t e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (layout): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names1[] = {"dev 7 phase-1 blocks", "dev 8b row sort, wave cut", "dev download layout"};
+    report(21, 24, names1);
+    auto at = [&](size_t off) { return pin_ + (off - L.dl3); };
+    const int *hdr = (const int *)at(L.lhdr), *hvoff = (const int *)at(L.hvoff);
+    if (hdr[kHdrBound]) return 1;
+    const int32_t nw = waves ? hdr[kLhNw] : 0;
+    const int64_t nsl = waves ? hdr[kLhSlots] : 0;
+    if (hvoff[0] != 0 || hvoff[1 + S] < 0 || hvoff[1 + S] > nb || (waves && (nw < 1 || nw > ni || nsl < 0 || nsl > 16 * (int64_t)P))) {
+        err = "plan builder: the device wrote impossible layout counts";
+        return -1;
+    }
+    auto t0 = std::chrono::steady_clock::now();
+    auto take = [&](auto &v, size_t off, size_t n) {
+        using V = typename std::remove_reference<decltype(v)>::type::value_type;
+        const V *p = (const V *)at(off);
+        v.assign(p, p + n);
+    };
+    take(H.dperm, L.dperm, (size_t)D);
+    take(H.blk, L.blk, 4 * (size_t)nb);
+    take(H.hv_blk, L.hvb, (size_t)hvoff[1 + S]);
+    H.hv_blk_off.assign(hvoff, hvoff + 1 + S + 1);
+    ran |= 1;
+    // (the host builds stage 8b when 64 x slots does not fit an int)
+    if (!waves || 64 * nsl >= (1LL << 31)) return 0;
+    take(H.rowmap, L.rowmap, 64 * (size_t)nw);
+    take(H.wsplit, L.wsplit, (size_t)nw);
+    {
+        const int *wo = (const int *)at(L.woff);
+        H.woff.assign(wo, wo + nw + 1);
+    }
+    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> layout arrays", ms_since(t0));
+    // the slot arrays: pmap | pidx in a buffer of their own, kept for the solver's device-to-device copy
+    const size_t nel = 64 * (size_t)nsl, half = pad(4 * nel), need = 2 * half;
+    if (need > scap_) {
+        if (before_alloc && *before_alloc) {
+            (*before_alloc)();
+            *before_alloc = nullptr;
+        }
+        if (sbuf_) hipFree(sbuf_);
+        sbuf_ = nullptr; scap_ = 0;
+        const size_t want = need + need / 4;
+        if (hipMalloc((void **)&sbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
+        scap_ = want;
+    }
+    int *d_pmap = (int *)sbuf_, *d_pidx = (int *)(sbuf_ + half);
+    hipEventRecord(ev_[25], st_);
+    if (nel > 0) {
+        hipMemsetAsync(sbuf_, 0xff, need, st_);
+        LAUNCH(k_slot_fill, 64 * (int64_t)nw, nw, (int)nsl, (const int *)d_rowmap, (const int *)d_woff, (const uint8_t *)d_wsplit, d_ioff,
+               d_inc, d_dep_off, d_dep_ids, d_dscale, d_pmap, d_pidx, d_hdr);
+    }
+    hipEventRecord(ev_[26], st_);
+    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    if (download_slots && nel > 0) {
+        H.pmap.resize(nel);
+        H.pidx.resize(nel);
+        hipMemcpyAsync(H.pmap.data(), d_pmap, 4 * nel, hipMemcpyDeviceToHost, st_);
+        hipMemcpyAsync(H.pidx.data(), d_pidx, 4 * nel, hipMemcpyDeviceToHost, st_);
+    }
+    hipEventRecord(ev_[27], st_);
+    e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (layout): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names2[] = {"dev 8b slot fill", "dev download slots"};
+    report(25, 27, names2);
+    if (((const int *)pin_)[kHdrBound]) return 1;
+    H.pmap_dev = nel > 0 ? d_pmap : nullptr;
+    H.pidx_dev = nel > 0 ? d_pidx : nullptr;
+    H.slots_dev = (int64_t)nel;
+    ran |= 6;
     return 0;
 }
 

@@ -128,6 +128,7 @@ struct deftri_ctx {
     std::unique_ptr<PlanDevice> pdev;       // the plan builder's device arena and pinned staging (plan_dev.hip)
     int plan_builder = 0;                   // deftri_set_plan_builder
     int tile_builder = 0;                   // deftri_set_tile_builder
+    int layout_builder = 0;                 // deftri_set_layout_builder
     PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
@@ -1234,6 +1235,13 @@ int deftri_set_tile_builder(deftri_ctx *ctx, int32_t mode) {
     return 0;
 }
 
+int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_layout_builder: mode is 0 (stages 7 and 8b on the host) or 1 (device stages)");
+    ctx->layout_builder = mode;
+    return 0;
+}
+
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages, int32_t *reason, double *ms) {
     if (!ctx || !builder_used || !stages || !reason || !ms) return DEFTRI_E_ARG;
     *builder_used = ctx->plan_build.builder_used;
@@ -1243,25 +1251,61 @@ int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t
     return 0;
 }
 
+// the plan of the two debug entries below: the context's builders, every array on the host
+static int debug_build_plan(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile, SpPlanHost &H) {
+    int rc = validate(ctx, desc);
+    if (rc) return rc;
+    if (ctx->device >= 0) hipSetDevice(ctx->device);
+    std::string err;
+    rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
+                            mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build, ctx->tile_builder, ctx->layout_builder,
+                            false);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
 int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile, uint64_t *digests,
                              int32_t cap, int32_t *n) {
     if (!ctx || !desc || !digests || !n) return DEFTRI_E_ARG;
     if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_digest: mode is 0 or 1");
     if (cap < kPlanDigestCount + 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_digest: room for " + std::to_string(kPlanDigestCount + 1) + " digests needed");
-    int rc = validate(ctx, desc);
-    if (rc) return rc;
-    if (ctx->device >= 0) hipSetDevice(ctx->device);
     SpPlanHost H;
-    std::string err;
-    rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
-                            mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build, ctx->tile_builder);
-    if (rc) return fail(ctx, rc, err);
+    int rc = debug_build_plan(ctx, desc, mode, tile, H);
+    if (rc) return rc;
     std::vector<uint64_t> each;
     const uint64_t all = plan_digests(H, &each);
     if ((int)each.size() != kPlanDigestCount) return fail(ctx, DEFTRI_E_INTERNAL, "debug_plan_digest: digest count");
     std::copy(each.begin(), each.end(), digests);
     digests[kPlanDigestCount] = all;
     *n = kPlanDigestCount + 1;
+    return 0;
+}
+
+int deftri_debug_plan_layout_stats(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile, int64_t *out,
+                                   int32_t cap) {
+    if (!ctx || !desc || !out) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_layout_stats: mode is 0 or 1");
+    if (cap < 8) return fail(ctx, DEFTRI_E_ARG, "debug_plan_layout_stats: room for 8 figures needed");
+    SpPlanHost H;
+    int rc = debug_build_plan(ctx, desc, mode, tile, H);
+    if (rc) return rc;
+    const int64_t nw = (int64_t)H.wsplit.size(), nb = (int64_t)H.blk.size() / 4;
+    if ((int64_t)H.woff.size() != nw + 1 || (int64_t)H.rowmap.size() != 64 * nw)
+        return fail(ctx, DEFTRI_E_INTERNAL, "debug_plan_layout_stats: wave arrays");
+    int64_t split = 0, two = 0, empty = 0, depth = 0, run = 0;
+    // a wave's look-ahead: the 64 sorted rows from its first (to the last own row); sorted position i holds a row of
+    // window i / kSpSortWindow, and the waves' first positions follow from the rows they take
+    const int64_t nown = H.hi - H.lo;
+    for (int64_t w = 0, i = 0; w < nw; w++) {
+        split += H.wsplit[w] != 0;
+        empty += H.woff[w + 1] == H.woff[w];
+        const int64_t last = std::min(nown, i + 64) - 1;
+        two += last / kSpSortWindow != i / kSpSortWindow;
+        i += H.wsplit[w] ? 32 : 64;
+    }
+    for (int64_t b = 0; b < nb; b++) depth += (H.blk[4 * b] & 0xff) == SP_DEP;
+    for (size_t h = 0; h + 1 < H.hv_blk_off.size(); h++) run = std::max<int64_t>(run, H.hv_blk_off[h + 1] - H.hv_blk_off[h]);
+    out[0] = nw; out[1] = split; out[2] = two; out[3] = empty; out[4] = H.woff.empty() ? 0 : H.woff.back();
+    out[5] = nb; out[6] = depth; out[7] = run;
     return 0;
 }
 
@@ -1629,6 +1673,7 @@ int deftri_problem_upload(deftri_ctx *ctx, const deftri_problem_desc *desc) {
         ctx->sp->before_alloc = [ctx] { join_reaper(ctx); };
         ctx->sp->plan_builder = ctx->plan_builder;
         ctx->sp->tile_builder = ctx->tile_builder;
+        ctx->sp->layout_builder = ctx->layout_builder;
         ctx->sp->plan_dev = ctx->plan_builder ? plan_device(ctx) : nullptr;
         ctx->sp->plan_build = &ctx->plan_build;
         rc = ctx->sp->upload(*desc);

@@ -115,6 +115,11 @@ struct SpPlanHost {
     std::vector<int64_t> woff;                         // nwaves + 1, in slots
     std::vector<uint8_t> wsplit;                       // per wave: 1 = 32 rows on lane pairs (j, j + 32)
     std::vector<int32_t> pmap, pidx;                   // [slots * 64]
+    // deftri_set_layout_builder: the two arrays as the device builder left them (PlanDevice::layout), slots_dev
+    // elements each, valid until the next build on that arena; pmap / pidx above are then empty unless the build
+    // was asked to download them (the digest)
+    const int32_t *pmap_dev = nullptr, *pidx_dev = nullptr;
+    int64_t slots_dev = 0;
     int32_t max_heavy_blocks = 0;                      // most phase-1 blocks of one heavy vertex
     // halo exchange: rows (global) sent to / received from each peer, ascending
     std::vector<std::vector<int32_t>> send_rows, recv_rows;
@@ -200,10 +205,12 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // and the host passes elsewhere; info says what ran.  Returns 0, DEFTRI_E_ARG (err) when the problem cannot be
 // planned, DEFTRI_E_HIP (err) after a HIP error in the builder.  before_alloc (may be null): called and cleared
 // before the builder's arena grows.  tile_mode (deftri_set_tile_builder) 1: where mode 1 applies, build_tiles on
-// `pd` as well (PlanDevice::tiles; stages bits 6-9)
+// `pd` as well (PlanDevice::tiles; stages bits 6-9).  layout_mode (deftri_set_layout_builder) 1: where the device
+// built the tile layout, stages 7 and 8b on `pd` too (PlanDevice::layout; stages bits 10-12); keep_slots then
+// leaves pmap and pidx on the device (out.pmap_dev, out.pidx_dev) — unless DEFTRI_PLAN_DIGEST asks for the digest
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode = 0);
+                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false);
 // FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
 // not null one digest per array in that block's order (names: kPlanDigestNames)
 uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
@@ -378,6 +385,7 @@ class SpSolver {
     // deftri_set_plan_builder: the mode, the context's builder arena (null: no device stages) and where the
     // build reports what it did (deftri_plan_build_info; may be null)
     int plan_builder = 0, tile_builder = 0;          // (tile_builder: deftri_set_tile_builder)
+    int layout_builder = 0;                          // deftri_set_layout_builder
     PlanDevice *plan_dev = nullptr;
     PlanBuildInfo *plan_build = nullptr;
     int refresh(const deftri_problem_desc &d);     // same structure: values only, plan kept

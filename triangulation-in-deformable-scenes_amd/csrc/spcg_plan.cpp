@@ -157,10 +157,13 @@ uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
 }
 
 // pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
-// stages: the bit mask of the stages it ran
+// stages: the bit mask of the stages it ran.  layout_dev (deftri_set_layout_builder): 1 stages 7 and 8b on pd too
+// where it built the tile layout, 2 the same with pmap and pidx left on the device (H.pmap_dev, H.pidx_dev)
 static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
-                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false) {
+                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false,
+                      int layout_dev = 0) {
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
+    static const bool digest = std::getenv("DEFTRI_PLAN_DIGEST") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
     auto stage = [&](const char *name) {
         if (!timing) return;
@@ -186,7 +189,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         // (the tile stages' int counts: padded entries <= 2 E + 64 ng, and a group id shifted by 2 bits)
         tiles_dev = tiles_dev && tile && Q == 1 && S <= 2 && E > 0 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31) &&
                     sp_tile_lds_budget() < (1LL << 30);
-        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev);
+        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev, tiles_dev && layout_dev);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         *stages |= 7;
         stage("1-3 on the device (wall)");
@@ -329,6 +332,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     //     the ARAP edges in tile-entry order; the rows keep the Morton group order (no 4b sort: a
     //     tile's rows are one contiguous range)
     std::vector<int32_t> tile_order, tile_foreign;
+    bool tiles_built_dev = false;                 // the device built the tile layout (not refused)
     if (tile && Q == 1 && S <= 2 && E > 0) {
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
@@ -342,6 +346,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
             built = rc == 0;
             if (built) {
                 H.tile = true;
+                tiles_built_dev = true;
                 *stages |= 0x3c0;
             }
         } else if (pd) gp.swap(gp_dev);
@@ -540,73 +545,86 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     }
 
     stage("6 rep / depth by row");
+    // deftri_set_layout_builder: stages 7 and 8b on the device (plan_dev.hip) from the arrays edges()
+    // left there; what it did not run (ran's bits clear) stays with the host code below
+    bool dev7 = false, dev8b = false;
+    if (dev_edges && tiles_built_dev && layout_dev) {
+        int32_t ran = 0;
+        const int rc = pd->layout(d, before_alloc, H, layout_dev == 1 || digest, ran, err);
+        if (rc) return rc > 0 ? kPlanBound : kPlanHip;
+        dev7 = (ran & 1) != 0;
+        dev8b = (ran & 6) == 6;
+        *stages |= ran << 10;
+    }
     // 7. phase-1 blocks: ARAP (owned, then halo-only) per pair in runs of kSpBlock; depth edges by
     //    (scale, row) per scale
     const int32_t ndl = (int32_t)H.dep_ids.size();
-    H.dperm.resize(ndl);
-    std::iota(H.dperm.begin(), H.dperm.end(), 0);
-    par_counting_sort(H.dperm, std::max(S, 1), [&](int32_t j) { return d.dep_scale[H.dep_ids[j]]; });
-    auto add_blocks = [&](int kind, int owned, int64_t b0, int64_t b1, auto heavy_of) {
-        int64_t i = b0;
-        while (i < b1) {
-            const int32_t hv = heavy_of(i);
-            int64_t j = i;
-            while (j < b1 && j - i < kSpBlock && heavy_of(j) == hv) j++;
-            H.blk.push_back(kind | owned << 8);
-            H.blk.push_back(hv);
-            H.blk.push_back((int32_t)i);
-            H.blk.push_back((int32_t)j);
-            i = j;
+    if (!dev7) {
+        H.dperm.resize(ndl);
+        std::iota(H.dperm.begin(), H.dperm.end(), 0);
+        par_counting_sort(H.dperm, std::max(S, 1), [&](int32_t j) { return d.dep_scale[H.dep_ids[j]]; });
+        auto add_blocks = [&](int kind, int owned, int64_t b0, int64_t b1, auto heavy_of) {
+            int64_t i = b0;
+            while (i < b1) {
+                const int32_t hv = heavy_of(i);
+                int64_t j = i;
+                while (j < b1 && j - i < kSpBlock && heavy_of(j) == hv) j++;
+                H.blk.push_back(kind | owned << 8);
+                H.blk.push_back(hv);
+                H.blk.push_back((int32_t)i);
+                H.blk.push_back((int32_t)j);
+                i = j;
+            }
+        };
+        auto pair_of = [&](int64_t le) { return d.arap_pair[H.arap_ids[le]]; };
+        add_blocks(SP_ARAP, 1, 0, H.n_arap_owned, pair_of);
+        add_blocks(SP_ARAP, 0, H.n_arap_owned, nloc, pair_of);
+        add_blocks(SP_DEP, 1, 0, ndl, [&](int64_t i) { return d.dep_scale[H.dep_ids[H.dperm[i]]]; });
+        const int64_t nb = (int64_t)H.blk.size() / 4;
+        // dispatch order: blocks by the row of their first edge's point (stable), so the blocks of every
+        // pair / scale over one region of rows run together and share the rows' (z, p) in L2 / MALL
+        // instead of one sweep over all rows per pair (28 sweeps at C4)
+        {
+            std::vector<int64_t> key(nb);
+            for (int64_t b = 0; b < nb; b++) {
+                const int kind = H.blk[4 * b] & 0xff;
+                const int32_t i = H.blk[4 * b + 2];
+                key[b] = kind == SP_ARAP ? mrow[ap[4 * (int64_t)H.arap_ids[i]]] : mrow[d.dep_point[H.dep_ids[H.dperm[i]]]];
+            }
+            std::vector<int64_t> ord(nb);
+            std::iota(ord.begin(), ord.end(), 0);
+            std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return key[a] < key[b]; });
+            // XCD-aware: workgroup b runs on XCD b % 8, so the sorted list is cut into 8 contiguous
+            // segments and dealt out (position 8 j + x <- segment x's j-th block): each XCD's L2 walks
+            // its own run of rows
+            constexpr int kXcd = 8;
+            const int64_t seg = (nb + kXcd - 1) / kXcd;
+            std::vector<int64_t> pos_of;
+            pos_of.reserve(nb);
+            for (int64_t j = 0; j < seg; j++)
+                for (int x = 0; x < kXcd; x++)
+                    if (x * seg + j < nb) pos_of.push_back(x * seg + j);
+            std::vector<int32_t> blk2(H.blk.size());
+            for (int64_t b = 0; b < nb; b++)
+                for (int k = 0; k < 4; k++) blk2[4 * b + k] = H.blk[4 * ord[pos_of[b]] + k];
+            H.blk.swap(blk2);
         }
-    };
-    auto pair_of = [&](int64_t le) { return d.arap_pair[H.arap_ids[le]]; };
-    add_blocks(SP_ARAP, 1, 0, H.n_arap_owned, pair_of);
-    add_blocks(SP_ARAP, 0, H.n_arap_owned, nloc, pair_of);
-    add_blocks(SP_DEP, 1, 0, ndl, [&](int64_t i) { return d.dep_scale[H.dep_ids[H.dperm[i]]]; });
-    const int64_t nb = (int64_t)H.blk.size() / 4;
-    // dispatch order: blocks by the row of their first edge's point (stable), so the blocks of every
-    // pair / scale over one region of rows run together and share the rows' (z, p) in L2 / MALL
-    // instead of one sweep over all rows per pair (28 sweeps at C4)
-    {
-        std::vector<int64_t> key(nb);
-        for (int64_t b = 0; b < nb; b++) {
-            const int kind = H.blk[4 * b] & 0xff;
-            const int32_t i = H.blk[4 * b + 2];
-            key[b] = kind == SP_ARAP ? mrow[ap[4 * (int64_t)H.arap_ids[i]]] : mrow[d.dep_point[H.dep_ids[H.dperm[i]]]];
+        H.hv_blk_off.assign(Q + S + 1, 0);
+        auto blk_heavy = [&](int64_t b) -> int32_t {
+            const int kind = H.blk[4 * b] & 0xff, owned = H.blk[4 * b] >> 8;
+            if (kind == SP_ARAP) return owned ? H.blk[4 * b + 1] : -1;
+            return Q + H.blk[4 * b + 1];
+        };
+        for (int64_t b = 0; b < nb; b++) { const int32_t h = blk_heavy(b); if (h >= 0) H.hv_blk_off[h + 1]++; }
+        for (int32_t h = 0; h < Q + S; h++) H.hv_blk_off[h + 1] += H.hv_blk_off[h];
+        H.hv_blk.resize((size_t)H.hv_blk_off[Q + S]);
+        {
+            std::vector<int64_t> pos(H.hv_blk_off.begin(), H.hv_blk_off.end() - 1);
+            for (int64_t b = 0; b < nb; b++) { const int32_t h = blk_heavy(b); if (h >= 0) H.hv_blk[pos[h]++] = (int32_t)b; }
         }
-        std::vector<int64_t> ord(nb);
-        std::iota(ord.begin(), ord.end(), 0);
-        std::stable_sort(ord.begin(), ord.end(), [&](int64_t a, int64_t b) { return key[a] < key[b]; });
-        // XCD-aware: workgroup b runs on XCD b % 8, so the sorted list is cut into 8 contiguous
-        // segments and dealt out (position 8 j + x <- segment x's j-th block): each XCD's L2 walks
-        // its own run of rows
-        constexpr int kXcd = 8;
-        const int64_t seg = (nb + kXcd - 1) / kXcd;
-        std::vector<int64_t> pos_of;
-        pos_of.reserve(nb);
-        for (int64_t j = 0; j < seg; j++)
-            for (int x = 0; x < kXcd; x++)
-                if (x * seg + j < nb) pos_of.push_back(x * seg + j);
-        std::vector<int32_t> blk2(H.blk.size());
-        for (int64_t b = 0; b < nb; b++)
-            for (int k = 0; k < 4; k++) blk2[4 * b + k] = H.blk[4 * ord[pos_of[b]] + k];
-        H.blk.swap(blk2);
-    }
-    H.hv_blk_off.assign(Q + S + 1, 0);
-    auto blk_heavy = [&](int64_t b) -> int32_t {
-        const int kind = H.blk[4 * b] & 0xff, owned = H.blk[4 * b] >> 8;
-        if (kind == SP_ARAP) return owned ? H.blk[4 * b + 1] : -1;
-        return Q + H.blk[4 * b + 1];
-    };
-    for (int64_t b = 0; b < nb; b++) { const int32_t h = blk_heavy(b); if (h >= 0) H.hv_blk_off[h + 1]++; }
-    for (int32_t h = 0; h < Q + S; h++) H.hv_blk_off[h + 1] += H.hv_blk_off[h];
-    H.hv_blk.resize((size_t)H.hv_blk_off[Q + S]);
-    {
-        std::vector<int64_t> pos(H.hv_blk_off.begin(), H.hv_blk_off.end() - 1);
-        for (int64_t b = 0; b < nb; b++) { const int32_t h = blk_heavy(b); if (h >= 0) H.hv_blk[pos[h]++] = (int32_t)b; }
     }
 
-    stage("7 phase-1 blocks");
+    stage(dev7 ? "7, 8b on the device (wall)" : "7 phase-1 blocks");
     // 8. own rows' ARAP incidences (local edge << 2 | role), each row's in local-edge order
     //    (a counting sort over chunks of local edges: per-chunk row counts, chunk-ordered offsets,
     //    every chunk scatters its edges in order — the sequential order)
@@ -647,7 +665,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     //     rows instead, each on a lane pair: lane j the first ceil(c / 2) slots of its row, lane j + 32
     //     the rest (rowmap -1: the pair's sums go to lane j) — the longest waves' step counts halve,
     //     which is what bounds phase 2 and the rows' linearization (their span, not their bytes)
-    {
+    if (!dev8b) {
         const int split_t = kSpWaveSplit;
         std::vector<int32_t> cnt(nown);
         for (int32_t l = 0; l < nown; l++)
@@ -771,7 +789,6 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         H.tile_bytes[1] = (double)nown * (96 + 48 + 48 + 24 + 48 + 8) + (double)H.tile_cross * 24;
         // fused (one launch): q stays in registers, p in LDS — no q out / in, no (z, p) reload
     }
-    static const bool digest = std::getenv("DEFTRI_PLAN_DIGEST") != nullptr;
     // FNV-1a over every plan array (plan_digests): a rewrite of the build is checked against the previous one
     if (digest) std::fprintf(stderr, "[deftri plan] digest %016llx\n", (unsigned long long)plan_digests(H, nullptr));
     return kPlanOk;
@@ -784,7 +801,7 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode) {
+                       int tile_mode, int layout_mode, bool keep_slots) {
     const auto t0 = std::chrono::steady_clock::now();
     info = PlanBuildInfo();
     auto done = [&](int rc) {
@@ -797,7 +814,8 @@ int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool 
     if (mode == 1 && !applies) info.reason = 1;
     if (applies) {
         int32_t stages = 0;
-        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, tile_mode == 1);
+        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, tile_mode == 1,
+                                  layout_mode == 1 ? (keep_slots ? 2 : 1) : 0);
         if (rc == kPlanOk) {
             info.builder_used = 1;
             info.stages = stages;

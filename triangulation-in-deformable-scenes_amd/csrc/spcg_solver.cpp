@@ -246,7 +246,7 @@ int SpSolver::upload(const deftri_problem_desc &d) {
     // they apply; its arena is the context's, so only its growth joins the old solver's release
     PlanBuildInfo pbi;
     const int plan_rc = build_sp_plan_with(d, rank_, nranks_, fp32_jac != 0, H, err, want_tile, plan_builder, plan_dev,
-                                           &before_alloc, pbi, tile_builder);
+                                           &before_alloc, pbi, tile_builder, layout_builder, true);
     if (plan_build) *plan_build = pbi;
     if (before_alloc) {
         before_alloc();
@@ -417,7 +417,16 @@ int SpSolver::upload(const deftri_problem_desc &d) {
         int32_t *rm, *pm, *pi;
         int64_t *wo;
         uint8_t *ws;
-        PUT(rm, H.rowmap); PUT(wo, H.woff); PUT(pm, H.pmap); PUT(pi, H.pidx); PUT(ws, H.wsplit);
+        PUT(rm, H.rowmap); PUT(wo, H.woff); PUT(ws, H.wsplit);
+        if (H.slots_dev > 0 && H.pmap.empty()) {
+            // deftri_set_layout_builder: the builder left the two arrays on the device (same stream: the copies
+            // run after its kernels); they never come to the host
+            ALLOC(pm, H.slots_dev); ALLOC(pi, H.slots_dev);
+            SPOK(hipMemcpyAsync(pm, H.pmap_dev, sizeof(int32_t) * (size_t)H.slots_dev, hipMemcpyDeviceToDevice, st_));
+            SPOK(hipMemcpyAsync(pi, H.pidx_dev, sizeof(int32_t) * (size_t)H.slots_dev, hipMemcpyDeviceToDevice, st_));
+            SPOK(hipStreamSynchronize(st_));
+            H.pmap_dev = H.pidx_dev = nullptr;
+        } else { PUT(pm, H.pmap); PUT(pi, H.pidx); }
         G.rowmap = rm; G.woff = wo; G.pmap = pm; G.pidx = pi; G.wsplit = ws;
         if (H.tile && (G.merged || G.sd)) { G.pj = nullptr; G.pj32 = nullptr; }   // the fused product reads J once
         else if (fp32_jac) { ALLOC(G.pj32, 3 * 64 * G.nslots); }

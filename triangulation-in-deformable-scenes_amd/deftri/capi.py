@@ -95,6 +95,8 @@ def load():
         "deftri_set_mesh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_plan_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_set_layout_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_debug_plan_layout_stats": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_int64), C.c_int32]),
         "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "deftri_debug_plan_digest": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_uint64), C.c_int32,
                                                P(C.c_int32)]),
@@ -242,7 +244,12 @@ EXPORTED = [
     "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
     "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
+    "deftri_set_layout_builder", "deftri_debug_plan_layout_stats",
 ]
+
+# the figures of deftri_debug_plan_layout_stats, in its order
+PLAN_LAYOUT_STATS = ("waves", "split_waves", "two_window_waves", "zero_step_waves", "slot_steps", "blocks", "depth_blocks",
+                     "max_heavy_run")
 
 # the arrays of deftri_debug_plan_digest, in its order; the combined digest follows them
 PLAN_DIGEST_NAMES = (
@@ -709,6 +716,12 @@ class Context:
         plan builder 0."""
         self._check(self.lib.deftri_set_tile_builder(self.h, int(mode)))
 
+    def set_layout_builder(self, mode):
+        """Who builds the phase-1 blocks and the phase-2 wave layout where plan builder 1 and tile builder 1 both ran
+        (deftri_set_layout_builder): 0 the host (default), 1 the device stages (plan_build_info stages bits 10-12);
+        an upload then keeps pmap and pidx on the device.  No effect anywhere else."""
+        self._check(self.lib.deftri_set_layout_builder(self.h, int(mode)))
+
     def plan_build_info(self):
         """What the last iterative plan build did (deftri_plan_build_info): builder_used, stages (bit mask),
         reason (0 none, 1 not applicable, 2 a bounded loop reached its bound), ms."""
@@ -726,6 +739,15 @@ class Context:
                                                       out.ctypes.data_as(C.POINTER(C.c_uint64)), len(out), C.byref(n)))
         assert n.value == len(PLAN_DIGEST_NAMES), n.value
         return PLAN_DIGEST_NAMES, [int(x) for x in out]
+
+    def debug_plan_layout_stats(self, prob, mode, tile):
+        """Figures of the phase-1 blocks and the wave layout of the plan debug_plan_digest builds
+        (deftri_debug_plan_layout_stats), as a dict with the keys PLAN_LAYOUT_STATS."""
+        d = prob.to_desc()
+        out = np.zeros(len(PLAN_LAYOUT_STATS), np.int64)
+        self._check(self.lib.deftri_debug_plan_layout_stats(self.h, C.byref(d), int(mode), int(tile),
+                                                            out.ctypes.data_as(C.POINTER(C.c_int64)), len(out)))
+        return dict(zip(PLAN_LAYOUT_STATS, (int(x) for x in out)))
 
     def delaunay(self, xy, tris_cap=None):
         """The Delaunay triangulation of xy [n, 2] (deftri_delaunay2d) on this context: stars on the device, or on

@@ -1297,6 +1297,23 @@ int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode);
    2 a bounded loop reached its bound); ms = wall time of the build.  All zero before the first build. */
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
                            int32_t *reason, double *ms);
+/* Who runs the passes of a full ARAP graph build (deftri_arap_build_graph, deftri_arap_optimization; the branch
+   taken when neither the graph memo nor the structure memo answers): 0 (default) the host; 1 the device stages of
+   csrc/graph_build_dev.hip — the CSR adjacency, the vector map, the cot weights and rotations, the slot scan, the
+   point numbering and the edges; the triangulation (deftri_set_mesh_builder) and the area sum stay where they
+   are.  The graph is the host's, array for array.  It applies on a device context to a map with at least one
+   pair whose MapPoint ids take the direct id table, whose meshes skip no point and whose counts fit an int32;
+   anywhere else, and on a host-only context, the host build runs.  DEFTRI_E_ARG: a mode other than 0 or 1.  A
+   HIP error inside the builder fails the call with DEFTRI_E_HIP. */
+int deftri_set_graph_builder(deftri_ctx *ctx, int32_t mode);
+/* What the last full graph build of this context did (a memo hit leaves it as it is): builder_used 0 / 1; stages =
+   bit mask of the stages that ran on the device (bit 0 CSR adjacency, 1 vector map, 2 geometry, 3 slot scan,
+   4 point numbering, 5 edges: 0x3f for a device build); reason = why builder_used is 0 although mode is 1 (0 none,
+   1 not applicable, 2 an input error, which the host build reports, 3 a mesh the device stages hand back: an edge
+   with more than two opposite corners, a row above the sort's bound); ms = wall time of the build.  All zero
+   before the first full build. */
+int deftri_graph_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
+                            int32_t *reason, double *ms);
 /* TEST: build the plan of `desc` as an upload of this context would, with builder `mode` and with
    the tile layout requested (tile = 1) or not, allocate no solver, and return one FNV-1a digest
    per plan array in the order of the DEFTRI_PLAN_DIGEST block of build_sp_plan (32: row_of_point,

@@ -7,8 +7,9 @@ PLAN_BUILDER (deftri_set_plan_builder): 0 the host passes (default), 1 the plan'
 TILE_BUILDER (deftri_set_tile_builder): 0 build_tiles on the host (default), 1 the tile layout on the device too.
 LAYOUT_BUILDER (deftri_set_layout_builder): 0 the phase-1 blocks and the wave layout on the host (default), 1 on
 the device too, pmap and pidx staying there.
+GRAPH_BUILDER (deftri_set_graph_builder): 0 the graph build's passes on the host (default), 1 the device stages.
 
-usage: python tools/e2e_timing.py [N_CORR] [MESH_BUILDER] [PLAN_BUILDER] [TILE_BUILDER] [LAYOUT_BUILDER]"""
+usage: python tools/e2e_timing.py [N_CORR] [MESH_BUILDER] [PLAN_BUILDER] [TILE_BUILDER] [LAYOUT_BUILDER] [GRAPH_BUILDER]"""
 import json
 import pathlib
 import sys
@@ -24,6 +25,7 @@ mesh_builder = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 plan_builder = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 tile_builder = int(sys.argv[4]) if len(sys.argv) > 4 else 0
 layout_builder = int(sys.argv[5]) if len(sys.argv) > 5 else 0
+graph_builder = int(sys.argv[6]) if len(sys.argv) > 6 else 0
 p, m = bench.build_problem(n, 1)
 
 
@@ -36,6 +38,8 @@ def configure(c):
         c.set_tile_builder(tile_builder)
     if layout_builder:
         c.set_layout_builder(layout_builder)
+    if graph_builder:
+        c.set_graph_builder(graph_builder)
 
 
 out = bench.end_to_end(0, m, configure)
@@ -43,4 +47,5 @@ out["mesh_builder"] = mesh_builder
 out["plan_builder"] = plan_builder
 out["tile_builder"] = tile_builder
 out["layout_builder"] = layout_builder
+out["graph_builder"] = graph_builder
 print(json.dumps(out), flush=True)

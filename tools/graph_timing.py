@@ -2,6 +2,12 @@
 rewrite of the builder can be checked bit-for-bit against the previous build's output.
 
 usage: python tools/graph_timing.py [n_corr] [repeats] [--digest OUT.json] [--check IN.json] [--kfs K] [--device D]
+                                    [--mesh-builder M] [--graph-builder G]
+
+--graph-builder G (deftri_set_graph_builder; needs --device >= 0): 0 the host passes, 1 the device stages, "both" the
+two one after the other on one context — after a warm-up build, the median of the library's own time of each build
+(deftri_graph_stats' ms_last) and what deftri_graph_build_info says.  Run with DEFTRI_NO_GRAPH_MEMO=1 so that every
+call is a full build, and with DEFTRI_GRAPH_TIMING=1 for the device stages' event times and the bytes moved (stderr).
 """
 import argparse
 import copy
@@ -37,6 +43,8 @@ def main():
     ap.add_argument("repeats", type=int, nargs="?", default=3)
     ap.add_argument("--kfs", type=int, default=2)
     ap.add_argument("--device", type=int, default=-1, help="context device (>= 0: computeR on the GPU)")
+    ap.add_argument("--mesh-builder", type=int, default=0, help="deftri_set_mesh_builder")
+    ap.add_argument("--graph-builder", default=None, help="deftri_set_graph_builder: 0, 1 or both")
     ap.add_argument("--digest")
     ap.add_argument("--check")
     a = ap.parse_args()
@@ -45,6 +53,28 @@ def main():
     else:
         m = sim.multi_view_arrays(n=a.n, k=a.kfs, seed=1)
     host = capi.Context(a.device)
+    host.set_mesh_builder(a.mesh_builder)
+    if a.graph_builder is not None:
+        out = {"n": a.n, "kfs": a.kfs, "mesh_builder": a.mesh_builder, "repeats": a.repeats}
+        digests = []
+        for mode in ((0, 1) if a.graph_builder == "both" else (int(a.graph_builder),)):
+            host.set_graph_builder(mode)
+            p = host.build_graph(m, 1.0, 2e5, np.float32(0.003))         # warm-up: arenas, pinned staging
+            ms, wall = [], []
+            for r in range(a.repeats):
+                t = time.perf_counter()
+                p = host.build_graph(m, 1.0, 2e5, np.float32(0.003))
+                wall.append(1e3 * (time.perf_counter() - t))
+                ms.append(host.graph_stats()[2])
+            digests.append(digest(p))
+            out["graph_builder_%d" % mode] = {"ms_last_median": round(float(np.median(ms)), 3),
+                                              "ms_last": [round(x, 3) for x in ms],
+                                              "call_ms_median": round(float(np.median(wall)), 3),
+                                              "full_builds": host.graph_stats()[0] == 0,
+                                              "info": host.graph_build_info()}
+        out["equal"] = all(d == digests[0] for d in digests)
+        print(json.dumps(out))
+        return
     mc, keep = m.to_c()
     times = []
     p = None

@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <numeric>
 #include <thread>
@@ -558,9 +559,161 @@ void emit_pair_edges(const deftri_map &map, const PairEmit &pe, int chunk, const
     }
 }
 
+// deftri_set_graph_builder(1): the full build on the device (graph_build_dev.hip).  The host keeps what the device
+// stages take as given: extractPositions, the triangulation (the sweep or the star path), the area sum in triangle
+// order and the per-pair descriptor entries.  0 built; 1 / 2 / 3 the reason the host build runs instead (g's arrays
+// untouched); -1 a HIP error (err)
+// a triangulation device_full_build made: a build it hands back takes it from here instead of triangulating again
+struct MadeMesh {
+    std::vector<double> xy;
+    std::shared_ptr<const GraphResult::MeshData> mesh;
+};
+
+int device_full_build(const deftri_map &map, const std::vector<DepthView> &dv, int pair_window, int64_t id_lo, int64_t span,
+                      const MeshSource *mesh_src, double rep_weight, double arap_weight, double info_dep,
+                      GraphBuilderDevice &gbd, GraphResult &g, std::vector<MadeMesh> &made, std::string &err) {
+    using MeshData = GraphResult::MeshData;
+    const int K = map.n_keyframes;
+    if (span < 0) return 1;
+    const char *rep_env = std::getenv("DEFTRI_DELAUNAY_REPAIR");
+    if (rep_env && std::atoi(rep_env) != 0) return 1;
+    std::vector<int> need;
+    std::vector<char> used((size_t)K, 0);
+    int64_t slots = 0;
+    for (int a = 0; a < K; a++)
+        for (int b = a + 1; b < K; b++) {
+            if (pair_window > 0 && b - a > pair_window) continue;
+            used[a] = used[b] = 1;
+            slots += std::min(map.keyframes[a].n_slots, map.keyframes[b].n_slots);
+        }
+    for (int b = 1; b < K; b++)
+        for (int a = 0; a < b; a++)
+            if (!(pair_window > 0 && b - a > pair_window)) { need.push_back(b); break; }
+    if (need.empty() || 2 * slots >= ((int64_t)1 << 31)) return 1;
+    // extractPositions of every keyframe in a pair
+    std::vector<std::vector<double>> pos((size_t)K);
+    for (int a = 0; a < K; a++) {
+        if (!used[a]) continue;
+        const deftri_keyframe &f = map.keyframes[a];
+        pos[a].reserve(3 * (size_t)f.n_slots);
+        for (int s = 0; s < f.n_slots; s++)
+            if (f.point_id[s] >= 0)
+                for (int k = 0; k < 3; k++) pos[a].push_back((double)f.point_pos[3 * s + k]);
+    }
+    // every keyframe 1's triangulation, area and T, the keyframes on parallel host threads as in the host build
+    std::vector<std::shared_ptr<MeshData>> kf_mesh((size_t)K);
+    std::vector<GraphBuilderDevice::MeshIn> min(need.size());
+    std::vector<int> why(need.size(), 0);
+    made.assign(need.size(), MadeMesh());
+    parallel_for((int)need.size(), 1, [&](int lo, int hi) {
+        for (int i = lo; i < hi; i++) {
+            const int b = need[i];
+            auto md = std::make_shared<MeshData>();
+            md->pos1 = pos[b];
+            const int n = md->n1 = (int)md->pos1.size() / 3;
+            if (n < 3) { why[i] = 2; continue; }                        // the host build's error
+            double xmin = md->pos1[0], xmax = md->pos1[0];
+            bool finite = true;
+            std::vector<double> xy(2 * (size_t)n);
+            for (int v = 0; v < n; v++) {
+                const double *p = &md->pos1[3 * (size_t)v];
+                finite = finite && std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
+                xmin = std::min(xmin, p[0]); xmax = std::max(xmax, p[0]);
+                xy[2 * (size_t)v] = p[0]; xy[2 * (size_t)v + 1] = p[1];
+            }
+            if (!finite) { why[i] = 1; continue; }
+            std::string e;
+            const bool ok = mesh_src ? (*mesh_src)(xy.data(), n, md->tris, md->hull, md->skipped, e)
+                                     : delaunay2d(xy.data(), n, md->tris, md->hull, md->skipped);
+            if (!ok) { why[i] = 2; continue; }
+            made[i].mesh = md;
+            made[i].xy = std::move(xy);
+            if (md->skipped > 0) { why[i] = 1; continue; }
+            const int ntri = (int)md->tris.size() / 3;
+            bool in_range = md->tris.size() == 3 * (size_t)ntri;       // the geometry kernels index with these
+            for (int32_t v : md->tris) in_range = in_range && v >= 0 && v < n;
+            if (!in_range) { why[i] = 3; continue; }
+            md->T = ntri + std::max(0, md->hull - 2);
+            md->area = mesh_area(md->pos1, md->tris);
+            GraphBuilderDevice::MeshIn &m = min[i];
+            m.n1 = n; m.ntri = ntri; m.pos1 = md->pos1.data(); m.tris = md->tris.data();
+            m.xmin = xmin; m.xmax = xmax; m.out = md.get();
+            kf_mesh[b] = std::move(md);
+        }
+    });
+    for (int w : why)
+        if (w == 2) return 2;
+    for (int w : why)
+        if (w) return w;
+    std::vector<int> mesh_of((size_t)K, -1);
+    for (size_t i = 0; i < need.size(); i++) mesh_of[need[i]] = (int)i;
+    // the per-pair descriptor entries, in the host build's order
+    std::vector<GraphBuilderDevice::PairIn> pin;
+    std::vector<double> tg, scales, cam_pose, pair_area, pair_info;
+    std::vector<float> cam_kb8;
+    std::vector<int32_t> cam_of((size_t)K, -1), kf_scale((size_t)K, -1), pair_kf1, pair_kf2, pair_T, pair_hull;
+    auto cam_index = [&](int k) {
+        if (cam_of[k] < 0) {
+            cam_of[k] = (int32_t)(cam_pose.size() / 7);
+            const deftri_keyframe &kf = map.keyframes[k];
+            for (int i = 0; i < 7; i++) cam_pose.push_back(kf.pose[i]);
+            for (int i = 0; i < 8; i++) cam_kb8.push_back(kf.kb8[i]);
+        }
+        return cam_of[k];
+    };
+    int64_t rot_base = 0, arap_cap = 0;
+    for (int a = 0; a < K; a++)
+        for (int b = a + 1; b < K; b++) {
+            if (pair_window > 0 && b - a > pair_window) continue;
+            const deftri_keyframe &kf1 = map.keyframes[b], &kf2 = map.keyframes[a];
+            const MeshData &md = *kf_mesh[b];
+            double Tg[7];
+            pair_tg(map, a, b, Tg);
+            for (int i = 0; i < 7; i++) tg.push_back(Tg[i]);
+            GraphBuilderDevice::PairIn p;
+            p.a = a; p.b = b; p.mesh = mesh_of[b];
+            p.ns12 = std::min(kf1.n_slots, kf2.n_slots);
+            p.n2 = (int)pos[a].size() / 3;
+            p.pos2 = pos[a].data();
+            p.s1 = (int32_t)scales.size();
+            scales.push_back(kf1.depth_scale); kf_scale[b] = p.s1;
+            p.s2 = (int32_t)scales.size();
+            scales.push_back(kf2.depth_scale); kf_scale[a] = p.s2;
+            p.c1 = cam_index(b);
+            p.c2 = cam_index(a);
+            p.rot_base = (int32_t)rot_base;
+            rot_base += md.n1;
+            arap_cap += 2 * (int64_t)md.tris.size();
+            pair_area.push_back(md.area);
+            pair_info.push_back(arap_weight * std::pow((double)md.T, 2));
+            pair_kf1.push_back(b); pair_kf2.push_back(a);
+            pair_T.push_back(md.T); pair_hull.push_back(md.hull);
+            pin.push_back(p);
+        }
+    if (rot_base >= ((int64_t)1 << 31) / 9 || arap_cap >= ((int64_t)1 << 31) / 4) return 1;
+    int reason = 0;
+    const int rc = gbd.build(map, dv, min, pin, id_lo, span, rep_weight, info_dep, g, reason, err);
+    if (rc < 0) return -1;
+    if (rc > 0) return reason;
+    int64_t w_off = 0;
+    for (const GraphBuilderDevice::PairIn &p : pin) {
+        GraphResult::PairMesh pm;
+        pm.mesh = kf_mesh[p.b];
+        pm.n2 = p.n2; pm.kf1 = p.b; pm.kf2 = p.a;
+        pm.w_off = w_off;
+        w_off += (int64_t)pm.mesh->adj.size();
+        g.meshes.push_back(std::move(pm));
+    }
+    g.tg = std::move(tg); g.scales = std::move(scales); g.cam_pose = std::move(cam_pose); g.cam_kb8 = std::move(cam_kb8);
+    g.pair_area = std::move(pair_area); g.pair_info = std::move(pair_info); g.kf_scale = std::move(kf_scale);
+    g.pair_kf1 = std::move(pair_kf1); g.pair_kf2 = std::move(pair_kf2); g.pair_T = std::move(pair_T);
+    g.pair_hull = std::move(pair_hull);
+    return 0;
+}
+
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
                       GraphResult &g, std::string &err, int pair_window, GraphDevice *gdev, DepthImages *images,
-                      const MeshSource *mesh_src) {
+                      const MeshSource *mesh_src, int graph_builder, GraphBuilderDevice *gbd, GraphBuildInfo *info) {
     g.err_code = 0;
     // the keyframes with a depth image on the context: their depth measurements come from the image
     std::vector<DepthView> dv((size_t)std::max(map.n_keyframes, 0));
@@ -667,6 +820,71 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
     static const bool timing = std::getenv("DEFTRI_GRAPH_TIMING") != nullptr;
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    // the descriptor over the filled arrays and the memos: the end of a full build on either path
+    GraphBuildInfo bi;
+    std::vector<MadeMesh> made;
+    MeshSource cached_src;
+    auto finish = [&]() {
+        deftri_problem_desc &d = g.desc;
+        d = deftri_problem_desc{};
+        d.n_points = (int32_t)g.point_mpid.size();
+        d.n_pairs = (int32_t)g.pair_area.size();
+        d.n_scales = (int32_t)g.scales.size();
+        d.n_cams = (int32_t)(g.cam_pose.size() / 7);
+        d.n_rep = (int32_t)g.rep_point.size();
+        d.n_depth = (int32_t)g.dep_point.size();
+        d.n_arap = (int32_t)g.arap_pair.size();
+        d.n_rot = (int32_t)(g.rot.size() / 9);
+        d.points = g.points.data(); d.tg = g.tg.data(); d.scales = g.scales.data();
+        d.cam_kb8 = g.cam_kb8.data(); d.cam_pose = g.cam_pose.data();
+        d.rep_point = g.rep_point.data(); d.rep_cam = g.rep_cam.data(); d.rep_obs = g.rep_obs.data();
+        d.rep_info = g.rep_info.data();
+        d.huber_delta = (double)(float)std::sqrt(100.991);          // const float deltaMono = sqrt(100.991)
+        d.dep_point = g.dep_point.data(); d.dep_scale = g.dep_scale.data(); d.dep_cam = g.dep_cam.data();
+        d.dep_meas = g.dep_meas.data(); d.dep_info = g.dep_info.data();
+        d.arap_pts = g.arap_pts.data(); d.arap_pair = g.arap_pair.data(); d.arap_rot = g.arap_rot.data();
+        d.arap_w = g.arap_w.data(); d.rot = g.rot.data(); d.pair_area = g.pair_area.data(); d.pair_info = g.pair_info.data();
+        d.order_xy = g.order_xy.data();
+        g.memo_key = std::move(key);
+        g.memo_valid = true;
+        g.struct_key = std::move(skey);
+        g.struct_valid = true;
+        g.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
+        bi.ms = g.ms_last;
+        if (info) *info = bi;
+        return true;
+    };
+    if (graph_builder == 1) {
+        // the device path where it applies; the host build below otherwise, and info says why
+        const int rc = gbd ? device_full_build(map, dv, pair_window, pidx.lo, pidx.span, mesh_src, rep_weight, arap_weight, info_dep,
+                                               *gbd, g, made, err)
+                           : 1;
+        if (rc < 0) { g.err_code = DEFTRI_E_HIP; return false; }
+        if (timing && gbd && rc != 1)
+            std::fprintf(stderr, "[deftri graph] device build: reason %d, stages %.3f %.3f %.3f %.3f %.3f %.3f ms, up %lld B, down %lld B, %d syncs\n",
+                         rc, gbd->stage_ms[0], gbd->stage_ms[1], gbd->stage_ms[2], gbd->stage_ms[3], gbd->stage_ms[4],
+                         gbd->stage_ms[5], (long long)gbd->bytes_up, (long long)gbd->bytes_down, gbd->syncs);
+        bi.reason = rc;
+        if (rc == 0) {
+            bi.builder_used = 1;
+            bi.stages = 0x3f;
+            return finish();
+        }
+    }
+    if (info) *info = bi;                       // a host build that fails leaves the reason it ran for
+    if (!made.empty()) {
+        // the host build after a hand-back: the triangulations already made answer for their keyframes
+        cached_src = [&made, orig_src = mesh_src](const double *xy, int n, std::vector<int32_t> &tris, int &hull, int &skipped,
+                                                  std::string &e) {
+            for (const MadeMesh &c : made)
+                if (c.mesh && c.mesh->n1 == n && std::memcmp(c.xy.data(), xy, sizeof(double) * 2 * (size_t)n) == 0) {
+                    tris = c.mesh->tris; hull = c.mesh->hull; skipped = c.mesh->skipped;
+                    return true;
+                }
+            return orig_src ? (*orig_src)(xy, n, tris, hull, skipped, e) : delaunay2d(xy, n, tris, hull, skipped);
+        };
+        mesh_src = &cached_src;
+    }
     // the mesh of keyframe 1's positions (Delaunay, adjacency, area, cot weights, vector map), built
     // once per keyframe: every pair with that keyframe 1 has the same v1Positions
     std::vector<std::shared_ptr<GraphResult::MeshData>> kf1_mesh(K);
@@ -932,32 +1150,7 @@ bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weig
         });
         if (timing) std::fprintf(stderr, "[deftri graph] edges written: %.1f ms (arrays %.1f)\n", ms(t0, tnow()), ms(t0, t1));
     }
-    deftri_problem_desc &d = g.desc;
-    d = deftri_problem_desc{};
-    d.n_points = (int32_t)g.point_mpid.size();
-    d.n_pairs = (int32_t)g.pair_area.size();
-    d.n_scales = (int32_t)g.scales.size();
-    d.n_cams = (int32_t)(g.cam_pose.size() / 7);
-    d.n_rep = (int32_t)g.rep_point.size();
-    d.n_depth = (int32_t)g.dep_point.size();
-    d.n_arap = (int32_t)g.arap_pair.size();
-    d.n_rot = (int32_t)(g.rot.size() / 9);
-    d.points = g.points.data(); d.tg = g.tg.data(); d.scales = g.scales.data();
-    d.cam_kb8 = g.cam_kb8.data(); d.cam_pose = g.cam_pose.data();
-    d.rep_point = g.rep_point.data(); d.rep_cam = g.rep_cam.data(); d.rep_obs = g.rep_obs.data();
-    d.rep_info = g.rep_info.data();
-    d.huber_delta = (double)(float)std::sqrt(100.991);          // const float deltaMono = sqrt(100.991)
-    d.dep_point = g.dep_point.data(); d.dep_scale = g.dep_scale.data(); d.dep_cam = g.dep_cam.data();
-    d.dep_meas = g.dep_meas.data(); d.dep_info = g.dep_info.data();
-    d.arap_pts = g.arap_pts.data(); d.arap_pair = g.arap_pair.data(); d.arap_rot = g.arap_rot.data();
-    d.arap_w = g.arap_w.data(); d.rot = g.rot.data(); d.pair_area = g.pair_area.data(); d.pair_info = g.pair_info.data();
-    d.order_xy = g.order_xy.data();
-    g.memo_key = std::move(key);
-    g.memo_valid = true;
-    g.struct_key = std::move(skey);
-    g.struct_valid = true;
-    g.ms_last = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_build).count();
-    return true;
+    return finish();
 }
 
 void writeback_arap(deftri_map &map, const GraphResult &g, const std::vector<double> &points,

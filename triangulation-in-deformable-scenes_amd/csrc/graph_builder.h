@@ -92,6 +92,53 @@ class GraphDevice {
     size_t cap_ = 0;
 };
 
+// The three kernels of mesh_pass on arrays already on the device (graph_build_dev.hip's stage 2): cnt [>= the CSR
+// size] zeroed by the caller, slot twice that; *bad is set where an edge has more than two opposite corners
+void graph_geometry_launch(hipStream_t st, int n1, int n2, int ntri, const int32_t *tris, const int32_t *off, const int32_t *adj,
+                           const int32_t *pos_idx, const int32_t *inv, const double *pos1, const double *pos2, double *slot,
+                           int *cnt, int *bad, double *w, double *R);
+
+// deftri_graph_build_info: what the last full build did
+struct GraphBuildInfo {
+    int32_t builder_used = 0, stages = 0, reason = 0;
+    double ms = 0;
+};
+
+// The full build on the device (graph_build_dev.hip, deftri_set_graph_builder(1)): a grow-only arena and pinned
+// staging; build_arap_graph hands it the triangulated meshes and the pairs and gets the GraphResult arrays back
+class GraphBuilderDevice {
+ public:
+    struct MeshIn {
+        int n1 = 0, ntri = 0;
+        const double *pos1 = nullptr;
+        const int32_t *tris = nullptr;
+        double xmin = 0, xmax = 0;            // the range of the positions' x (the vector map's bucket grid)
+        GraphResult::MeshData *out = nullptr; // off, adj, pos_idx, inv and identity_map are filled here
+    };
+    struct PairIn {
+        int a = 0, b = 0, mesh = 0, ns12 = 0, n2 = 0;
+        const double *pos2 = nullptr;
+        int32_t c1 = 0, c2 = 0, s1 = 0, s2 = 0, rot_base = 0;
+    };
+    GraphBuilderDevice(int device, hipStream_t st);
+    ~GraphBuilderDevice();
+    // 0 built (g's edge, point, weight and rotation arrays and the meshes' arrays filled); 1 handed back to the host
+    // build, g untouched (reason 2 an input error, 3 a mesh the stages do not cover); -1 a HIP error (err)
+    int build(const deftri_map &map, const std::vector<DepthView> &dv, std::vector<MeshIn> &meshes,
+              const std::vector<PairIn> &pairs, int64_t id_lo, int64_t span, double rep_weight, double info_dep, GraphResult &g,
+              int &reason, std::string &err);
+    double stage_ms[6] = {0, 0, 0, 0, 0, 0};   // device time of each stage of the last build (events)
+    int64_t bytes_up = 0, bytes_down = 0;
+    int syncs = 0;                             // blocking synchronisations of the last build
+
+ private:
+    int dev_;
+    hipStream_t st_;
+    void *buf_ = nullptr, *pin_ = nullptr;
+    size_t cap_ = 0, pin_cap_ = 0;
+    hipEvent_t ev_[7] = {};
+};
+
 // Who triangulates a keyframe's (x, y): xy [2 * n] -> canonical tris, hull_size, skipped, as delaunay2d does and
 // with its result (deftri_set_mesh_builder: the star path of delaunay_dev.hip).  Called from parallel host
 // threads.  False: no triangulation exists (collinear input) or err.
@@ -100,9 +147,12 @@ using MeshSource = std::function<bool(const double *xy, int n, std::vector<int32
 
 // pair_window > 0: only keyframe pairs (a, b) with b - a <= pair_window in map order (the
 // sliding-window deviation of BASELINE C5; 0 = every pair, the reference's loop :640-645)
+// graph_builder 1 (deftri_set_graph_builder): a full build runs on gbd where it applies, the host build otherwise;
+// info (may be null) then says which
 bool build_arap_graph(const deftri_map &map, double rep_weight, double arap_weight, float depth_error,
                       GraphResult &g, std::string &err, int pair_window = 0, GraphDevice *gdev = nullptr,
-                      DepthImages *images = nullptr, const MeshSource *mesh_src = nullptr);
+                      DepthImages *images = nullptr, const MeshSource *mesh_src = nullptr, int graph_builder = 0,
+                      GraphBuilderDevice *gbd = nullptr, GraphBuildInfo *info = nullptr);
 
 void writeback_arap(deftri_map &map, const GraphResult &g, const std::vector<double> &points,
                     const std::vector<double> &scales, const std::vector<double> &tg, double *optimization_update);

@@ -89,6 +89,17 @@ GraphDevice::~GraphDevice() {
     }
 }
 
+void graph_geometry_launch(hipStream_t st, int n1, int n2, int ntri, const int32_t *tris, const int32_t *off, const int32_t *adj,
+                           const int32_t *pos_idx, const int32_t *inv, const double *pos1, const double *pos2, double *slot,
+                           int *cnt, int *bad, double *w, double *R) {
+    if (n1 <= 0) return;
+    const int64_t corners = 3 * (int64_t)ntri;
+    if (corners > 0)
+        k_cot_corners<<<(unsigned)((corners + kRBlock - 1) / kRBlock), kRBlock, 0, st>>>(ntri, tris, off, adj, pos1, slot, cnt, bad);
+    k_cot_finish<<<(n1 + kRBlock - 1) / kRBlock, kRBlock, 0, st>>>(n1, off, adj, slot, cnt, w);
+    k_compute_r<<<(n1 + kRBlock - 1) / kRBlock, kRBlock, 0, st>>>(n1, n2, off, adj, w, pos_idx, inv, pos1, pos2, R);
+}
+
 int GraphDevice::mesh_pass(int n1, int n2, const int32_t *tris, int ntri, const int32_t *off, const int32_t *adj,
                            int64_t nadj, const int32_t *pos_idx, const int32_t *inv, const double *pos1,
                            const double *pos2, double *w_out, double *R, std::string &err) {

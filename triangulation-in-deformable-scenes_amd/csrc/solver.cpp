@@ -131,6 +131,9 @@ struct deftri_ctx {
     int layout_builder = 0;                 // deftri_set_layout_builder
     PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
+    std::unique_ptr<GraphBuilderDevice> gbdev;   // the graph builder's device arena and pinned staging (graph_build_dev.hip)
+    int graph_builder = 0;                  // deftri_set_graph_builder
+    GraphBuildInfo graph_build;             // deftri_graph_build_info: the last full graph build
     DepthImages images;                     // the keyframes' depth images (deftri_set_depth_images)
     OrbState orb;                           // ORB::describe's pattern, device arena and events (orb.hip)
     // speculative lambda lanes (see Lane)
@@ -1124,6 +1127,7 @@ int deftri_ctx_destroy(deftri_ctx *ctx) {
     hipSetDevice(ctx->device);
     free_device(ctx);
     ctx->gdev.reset();
+    ctx->gbdev.reset();
     ctx->ddev.reset();
     { std::string e; ctx->images.set(0, nullptr, e); }
     delete ctx->sp_tr;
@@ -1239,6 +1243,22 @@ int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode) {
     if (!ctx) return DEFTRI_E_ARG;
     if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_layout_builder: mode is 0 (stages 7 and 8b on the host) or 1 (device stages)");
     ctx->layout_builder = mode;
+    return 0;
+}
+
+int deftri_set_graph_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_graph_builder: mode is 0 (the graph build's passes on the host) or 1 (device stages)");
+    ctx->graph_builder = mode;
+    return 0;
+}
+
+int deftri_graph_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages, int32_t *reason, double *ms) {
+    if (!ctx || !builder_used || !stages || !reason || !ms) return DEFTRI_E_ARG;
+    *builder_used = ctx->graph_build.builder_used;
+    *stages = ctx->graph_build.stages;
+    *reason = ctx->graph_build.reason;
+    *ms = ctx->graph_build.ms;
     return 0;
 }
 
@@ -2643,6 +2663,12 @@ GraphDevice *graph_device(deftri_ctx *ctx) {
     if (!ctx->gdev) ctx->gdev.reset(new GraphDevice(ctx->device, ctx->st));
     return ctx->gdev.get();
 }
+// deftri_set_graph_builder(1): the full build's device stages; nullptr on a host-only context (the host build)
+GraphBuilderDevice *graph_builder_device(deftri_ctx *ctx) {
+    if (ctx->device < 0 || ctx->graph_builder == 0) return nullptr;
+    if (!ctx->gbdev) ctx->gbdev.reset(new GraphBuilderDevice(ctx->device, ctx->st));
+    return ctx->gbdev.get();
+}
 // the star path's buffers: nullptr on a host-only context (every star on the host)
 DelaunayDevice *delaunay_device(deftri_ctx *ctx) {
     if (ctx->device < 0) return nullptr;
@@ -2674,7 +2700,7 @@ int deftri_arap_build_graph(deftri_ctx *ctx, const deftri_map *map, double rep_w
     if (!ctx || !map || !desc_out) return DEFTRI_E_ARG;
     std::string err;
     if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images,
-                          mesh_source(ctx)))
+                          mesh_source(ctx), ctx->graph_builder, graph_builder_device(ctx), &ctx->graph_build))
         return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     *desc_out = &ctx->graph.desc;
     return 0;
@@ -2754,7 +2780,7 @@ int deftri_arap_optimization(deftri_ctx *ctx, deftri_map *map, double rep_weight
     };
     std::string err;
     if (!build_arap_graph(*map, rep_weight, arap_weight, depth_error, ctx->graph, err, ctx->pair_window, graph_device(ctx), &ctx->images,
-                          mesh_source(ctx)))
+                          mesh_source(ctx), ctx->graph_builder, graph_builder_device(ctx), &ctx->graph_build))
         return fail(ctx, ctx->graph.err_code ? ctx->graph.err_code : DEFTRI_E_GRAPH, err);
     const double ms_graph = ms_since(t0);
     const auto t1 = std::chrono::steady_clock::now();

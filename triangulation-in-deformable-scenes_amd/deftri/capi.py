@@ -98,6 +98,8 @@ def load():
         "deftri_set_layout_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_debug_plan_layout_stats": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_int64), C.c_int32]),
         "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
+        "deftri_set_graph_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_graph_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "deftri_debug_plan_digest": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_uint64), C.c_int32,
                                                P(C.c_int32)]),
         "deftri_debug_delaunay_still_valid": (C.c_int, [C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32)]),
@@ -245,6 +247,7 @@ EXPORTED = [
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
     "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
     "deftri_set_layout_builder", "deftri_debug_plan_layout_stats",
+    "deftri_set_graph_builder", "deftri_graph_build_info",
 ]
 
 # the figures of deftri_debug_plan_layout_stats, in its order
@@ -704,6 +707,19 @@ class Context:
         """Who triangulates a keyframe in the graph builds of this context (deftri_set_mesh_builder): 0 the host
         sweep (the default), 1 the star path of Context.delaunay.  The graph is the same bit for bit."""
         self._check(self.lib.deftri_set_mesh_builder(self.h, int(mode)))
+
+    def set_graph_builder(self, mode):
+        """Who runs the passes of a full graph build of this context (deftri_set_graph_builder): 0 the host (the
+        default), 1 the device stages where they apply (a device context, the direct id table, no skipped point).
+        The graph is the same array for array; no effect on a host-only context."""
+        self._check(self.lib.deftri_set_graph_builder(self.h, int(mode)))
+
+    def graph_build_info(self):
+        """What the last full graph build did (deftri_graph_build_info): builder_used, stages (bit mask, 0x3f for a
+        device build), reason (0 none, 1 not applicable, 2 an input error, 3 a mesh handed back), ms."""
+        used, stages, reason, ms = C.c_int32(), C.c_int32(), C.c_int32(), C.c_double()
+        self._check(self.lib.deftri_graph_build_info(self.h, C.byref(used), C.byref(stages), C.byref(reason), C.byref(ms)))
+        return dict(builder_used=used.value, stages=stages.value, reason=reason.value, ms=ms.value)
 
     def set_plan_builder(self, mode):
         """Who builds the iterative plan at the next upload of this context (deftri_set_plan_builder): 0 the host

@@ -1264,8 +1264,8 @@ int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode);
    deftri_arap_optimization / deftri_deformation_optimization): 0 (default) the host passes of
    csrc/spcg_plan.cpp; 1 the device stages of csrc/plan_dev.hip where they apply, the host passes elsewhere.
    The device stages apply on a device context of one rank to a problem of one keyframe pair, at most two depth
-   scales and at least one ARAP edge whose upload asks for the tile layout (from 50,000 unknowns).  The plan is
-   equal array for array.  DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the
+   scales and at least one ARAP edge whose upload asks for the tile layout (from 50,000 unknowns); with
+   deftri_set_multi_pair_builder(1) to several pairs as well.  The plan is equal array for array.  DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the
    upload with DEFTRI_E_HIP. */
 int deftri_set_plan_builder(deftri_ctx *ctx, int32_t mode);
 /* Who cuts the one-pair tile layout (build_tiles, csrc/spcg_tile.cpp) wherever plan builder 1's device stages
@@ -1283,18 +1283,40 @@ int deftri_set_tile_builder(deftri_ctx *ctx, int32_t mode);
    upload the two slot arrays pmap and pidx then stay on the device and reach the solver by a device-to-device
    copy (with DEFTRI_PLAN_DIGEST=1 they are downloaded for the digest).  The plan is equal array for array.  The
    host builds stage 8b when 64 x its slot steps does not fit an int.  Anywhere else — plan or tile builder 0, a
-   host-only context, a refused tile layout, more than one pair, a sharded context — it has no effect.
+   host-only context, a refused tile layout, a sharded context — it has no effect.  On more than one pair it acts
+   only under deftri_set_multi_pair_builder(1), and then on stage 8b alone, whatever the tile builder says.
    DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the upload with DEFTRI_E_HIP.
    deftri_debug_plan_digest with mode 1 honours this setting; every array then comes back to the host. */
 int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode);
+/* Whether plan builder 1's device stages also take a problem of several keyframe pairs: 0 (default) no — such a
+   plan is the host's, and deftri_plan_build_info says "not applicable"; 1 yes.  It applies where all of these
+   hold: plan builder 1 and this switch at 1; a device context of one rank; more than one pair, at least one ARAP
+   edge and fewer than 2^29, fewer than 2^21 cameras; an upload (or deftri_debug_plan_digest with tile = 1) that
+   asks for the tile layout.  The device then builds the groups, their Morton order and the keyframe-major rows of
+   a multi-pair tile plan — the points by (camera of the point's reprojection edges, curve key of the point's own
+   position in that camera's box, point id), or the group order where a point's reprojection edges name two
+   cameras — and, after build_tiles_multi, the rotation numbering, the reprojection / depth edges by row and the
+   incidences (stages 0x3f).  build_tiles_multi (csrc/spcg_tile.cpp) stays on the host whatever
+   deftri_set_tile_builder says (bits 6-9 are never set); where it refuses the graph the host goes on from the
+   device's rows (stages 0x7).  With deftri_set_layout_builder(1) stage 8b (rowmap, woff, wsplit, pmap, pidx) runs
+   on the device too and an upload keeps pmap and pidx there (stages 0x183f: bits 11 and 12); stage 7 (dperm, blk,
+   hv_blk, hv_blk_off) is the host's for several pairs, so bit 10 stays clear.  A row with more than 256
+   incidences reaches the builder's bound: the whole plan is then the host's (reason 2).  The plan is equal array
+   for array.  Anywhere else — one pair, where the other switches decide as before; a sharded or host-only
+   context; plan builder 0; no tile request — it has no effect.  DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP
+   error inside the builder fails the upload with DEFTRI_E_HIP.  deftri_debug_plan_digest and
+   deftri_debug_plan_layout_stats with mode 1 honour this setting. */
+int deftri_set_multi_pair_builder(deftri_ctx *ctx, int32_t mode);
 /* What the last iterative plan build of this context did: builder_used 0 / 1; stages = bit mask of
    the stages that ran on the device (bit 0 groups, 1 Morton order, 2 rows, 3 rotation numbering,
    4 rep/depth by row, 5 incidences; with deftri_set_tile_builder(1) also 6 groups and edges by group,
    7 partition, 8 entries and slots, 9 cross slots: 0x3ff for a full device build; bits 0-2 alone: the tile
    layout was refused after them and the build went on on the host; with deftri_set_layout_builder(1) also
    10 phase-1 blocks, 11 row sort and wave cut, 12 slot fill, set only when those stages ran: 0x1fff for a full
-   device build with all three switches); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable,
-   2 a bounded loop reached its bound); ms = wall time of the build.  All zero before the first build. */
+   device build with all three switches; several pairs with deftri_set_multi_pair_builder(1): 0x3f built on the
+   device, 0x183f with layout builder 1 — bits 6-10 stay with the host there — and 0x7 where build_tiles_multi
+   refused); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable, 2 a bounded loop reached
+   its bound); ms = wall time of the build.  All zero before the first build. */
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
                            int32_t *reason, double *ms);
 /* Who runs the passes of a full ARAP graph build (deftri_arap_build_graph, deftri_arap_optimization; the branch

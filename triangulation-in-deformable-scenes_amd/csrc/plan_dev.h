@@ -3,7 +3,8 @@
 // ascending ids, component roots that are the smallest id, a first-encounter numbering — so the arrays are the
 // host's bit for bit.  With deftri_set_tile_builder the tile layout (spcg_tile.cpp build_tiles, stage 4a)
 // is built there too, and with deftri_set_layout_builder the phase-1 blocks and the phase-2 wave layout
-// (stages 7 and 8b), whose two slot arrays can stay on the device.
+// (stages 7 and 8b), whose two slot arrays can stay on the device.  deftri_set_multi_pair_builder opens
+// stages 1-3, 5, 6, 8 and 8b to a plan of several pairs.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -44,7 +45,13 @@ class PlanDevice {
     // kernels, one download.  before_alloc: called (and cleared) before the arena grows
     int rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
              std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-             std::string &err, bool with_tiles = false, bool with_layout = false);
+             std::string &err, bool with_tiles = false, bool with_layout = false, bool multi = false);
+    // deftri_set_multi_pair_builder: rows() with multi takes a problem of several pairs and numbers the
+    // rows keyframe-major as spcg_plan.cpp stage 3 does for a multi-pair tile plan — by (camera of the point's first
+    // reprojection edge, curve key of the point's own position in that camera's box, point) — unless a point's
+    // reprojection edges name two cameras, where the group order stays; the choice is made on the device from a
+    // flag word.  gp always comes back (build_tiles_multi runs on the host); with_layout then lays out stage 8b's
+    // scratch only, and layout() runs stage 8b alone (ran bits 1 and 2).  Needs n_cams < 2^21
     // stages 4-6 (rotation numbering, rep / depth edges by row, incidences) for H.arap_ids on the rows of the
     // last rows() call: one upload of arap_ids, the kernels, one download into H
     int edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &err);
@@ -87,10 +94,12 @@ class PlanDevice {
             egi, egj, erow, ooff, oe, okj, pred, tioff, ie, tend, ja, jb, mark, midx, tstart, tne, tnh, tcut, thdr,
             // stages 7 and 8b (with_layout); dl3 .. dl3_end is their download
             dscale, dflag, bkey, boff, bord, blk0, order, scnt, wnext, wsteps, wsp, wja, wjb, wmark, widx, wsoff, dl3, lhdr,
-            dperm, blk, hvb, hvoff, rowmap, woff, wsplit, dl3_end, total;
+            dperm, blk, hvb, hvoff, rowmap, woff, wsplit, dl3_end,
+            // the keyframe-major rows of several pairs (multi)
+            pxy, rcam, rfirst, pcam, cbox, total;
     } L_{};
     bool with_tiles_ = false, order_on_dev_ = false;           // order_on_dev_: tiles() left arap_ids in L_.oe
-    bool with_layout_ = false;
+    bool with_layout_ = false, multi_ = false;
     int32_t P_ = 0;
     int64_t E_ = 0, nloc_ = -1;                                // nloc_: the local edges of the last edges(), -1 none
 };

@@ -1,5 +1,6 @@
 // plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h), and
-// its tile layout (build_tiles of one rank), its phase-1 blocks and its phase-2 wave layout (§5m).
+// its tile layout (build_tiles of one rank), its phase-1 blocks and its phase-2 wave layout (§5m); for
+// several pairs the keyframe-major rows, with the same edge stages and wave layout after them (§5o).
 //
 // No workgroup waits on another: a scan over more than one workgroup's elements is three launches (tile sums,
 // the scan of the sums by one workgroup, the tiles' own scans), a sort by a dense key (a row, a group) is count,
@@ -34,7 +35,9 @@ enum { kHdrBound = 0, kHdrNg = 1, kHdrNrot = 2, kHdrWords = 16,
        // the tile stages' header: a condition build_tiles refuses, tiles, padded entries, halo rows, cut entries
        kHdrRefuse = 3, kHdrNt = 4, kHdrEntries = 5, kHdrHalo = 6, kHdrCut = 7, kHdrSegmax = 8, kHdrLds = 9,
        // the layout stages' header (stages 7 and 8b): waves, slot steps
-       kLhNw = 4, kLhSlots = 5 };
+       kLhNw = 4, kLhSlots = 5,
+       // the rows of several pairs: a point with two cameras (the group order stays), the point count for the sort
+       kHdrManyCam = 10, kHdrP = 11 };
 
 namespace dev {
 
@@ -302,6 +305,71 @@ __global__ __launch_bounds__(kBlk) void k_run_sort(int nkeys, const int *off, in
 
 __global__ __launch_bounds__(kBlk) void k_inverse(int64_t n, const int *perm, int *inv) {
     PLAN_FOR(i, n) inv[perm[i]] = (int)i;
+}
+
+// ---- stage 3 of several pairs: the rows keyframe-major (spcg_plan.cpp) ---------------------
+// a double as an integer of the same order (finite values; -0 below +0), and back
+__device__ inline unsigned long long box_enc(double x) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return b >> 63 ? ~b : b | 1ull << 63;
+}
+
+__device__ inline double box_dec(unsigned long long u) {
+    return __longlong_as_double((long long)(u >> 63 ? u & ~(1ull << 63) : ~u));
+}
+
+// first[p]: the smallest reprojection edge at point p (INT_MAX: none)
+__global__ __launch_bounds__(kBlk) void k_rep_first(int64_t R, const int *rep_point, int *first) {
+    PLAN_FOR(e, R) atomicMin(&first[rep_point[e]], (int)e);
+}
+
+// one_cam is false when an edge names another camera than the first edge of its point
+__global__ __launch_bounds__(kBlk) void k_cam_check(int64_t R, const int *rep_point, const int *rep_cam, const int *first, int *hdr) {
+    PLAN_FOR(e, R)
+        if (rep_cam[first[rep_point[e]]] != rep_cam[e]) hdr[kHdrManyCam] = 1;
+}
+
+// box [4 (C + 1)]: per camera lo x, lo y (to be minimised), hi x, hi y (maximised), encoded
+__global__ __launch_bounds__(kBlk) void k_box_init(int n4, unsigned long long *box) {
+    PLAN_FOR(i, n4) box[i] = box_enc((i & 3) < 2 ? 1e300 : -1e300);
+}
+
+// cam(p) = the camera of p's first edge, C without one; its box takes p's finite coordinates.  An integer atomic
+// minimum / maximum gives the same result in any order; a thread whose value does not pass the word it reads
+// (a stale word is only ever looser) leaves the atomic out
+__global__ __launch_bounds__(kBlk) void k_cam_box(int P, int C, const int *first, const int *rep_cam, const double *pts, int stride,
+                                                 int *pcam, unsigned long long *box) {
+    PLAN_FOR(p, P) {
+        const int f = first[p], cam = f == INT_MAX ? C : rep_cam[f];
+        pcam[p] = cam;
+        for (int c = 0; c < 2; c++) {
+            const double v = pts[(int64_t)stride * p + c];
+            if (!isfinite(v)) continue;
+            const unsigned long long u = box_enc(v);
+            unsigned long long *lo = box + 4 * (int64_t)cam + c, *hi = lo + 2;
+            if (u < __hip_atomic_load(lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(lo, u);
+            if (u > __hip_atomic_load(hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(hi, u);
+        }
+    }
+}
+
+// key = cam << 42 | curve_key of the point's own position in its camera's box; id = p, ascending
+__global__ __launch_bounds__(kBlk) void k_cam_keys(int P, const int *pcam, const double *pts, int stride, const unsigned long long *box,
+                                                  uint64_t *key, int *id) {
+    PLAN_FOR(p, P) {
+        const int cam = pcam[p];
+        const unsigned long long *b = box + 4 * (int64_t)cam;
+        const double lo[2] = {box_dec(b[0]), box_dec(b[1])}, hi[2] = {box_dec(b[2]), box_dec(b[3])};
+        const double *q = pts + (int64_t)stride * p;
+        key[p] = (uint64_t)cam << 42 | curve_key(q[0], q[1], lo, hi);
+        id[p] = (int)p;
+    }
+}
+
+// the rows are the sorted points unless the flag word chose the group order, which por already holds
+__global__ __launch_bounds__(kBlk) void k_rows_pick(int P, const int *hdr, const int *sorted, int *por) {
+    if (hdr[kHdrManyCam]) return;
+    PLAN_FOR(r, P) por[r] = sorted[r];
 }
 
 // ---- stage 4: rotation numbering -------------------------------------------------------------------
@@ -923,10 +991,15 @@ void PlanDevice::report(int first, int last, const char *const *names) const {
 
 int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
                      std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-                     std::string &err, bool with_tiles, bool with_layout) {
+                     std::string &err, bool with_tiles, bool with_layout, bool multi) {
     hipSetDevice(dev_);
+    if (multi && (with_tiles || d.n_cams >= (1 << 21))) {
+        err = "plan builder: rows() of several pairs with the tile stages, or with 2^21 cameras";
+        return -1;
+    }
     with_tiles_ = with_tiles;
     with_layout_ = with_layout;
+    multi_ = multi;
     order_on_dev_ = false;
     nloc_ = -1;
     const int32_t P = d.n_points, NR = std::max(d.n_rot, 1);
@@ -968,16 +1041,25 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         }
         L.dl3 = L.dl3_end = o;
         if (with_layout) {
-            // at most nbm blocks, ni wave starts (every 32 rows) and as many waves
-            const size_t nbm = Ez / kSpBlock + (size_t)D / kSpBlock + 4, ni = (Pz + 31) / 32, Dz = (size_t)D;
-            L.dscale = piece(4 * Dz); L.dflag = piece(4 * (Dz + 1)); L.bkey = piece(4 * nbm); L.boff = piece(4 * (Pz + 1));
+            // at most nbm blocks, ni wave starts (every 32 rows) and as many waves; several pairs: stage 8b alone,
+            // so stage 7's pieces (D7 depth edges, nbm blocks, P7 block keys) are empty
+            const size_t ni = (Pz + 31) / 32, Dz = (size_t)D, D7 = multi ? 0 : Dz, P7 = multi ? 0 : Pz + 1;
+            const size_t nbm = multi ? 0 : Ez / kSpBlock + (size_t)D / kSpBlock + 4;
+            L.dscale = piece(4 * Dz); L.dflag = piece(4 * (D7 + 1)); L.bkey = piece(4 * nbm); L.boff = piece(4 * P7);
             L.bord = piece(4 * nbm); L.blk0 = piece(16 * nbm); L.order = piece(4 * Pz); L.scnt = piece(4 * Pz);
             L.wnext = piece(4 * (ni + 1)); L.wsteps = piece(4 * (ni + 1)); L.wsp = piece(4 * (ni + 1)); L.wja = piece(4 * (ni + 1));
             L.wjb = piece(4 * (ni + 1)); L.wmark = piece(4 * (ni + 1)); L.widx = piece(4 * (ni + 1)); L.wsoff = piece(4 * (ni + 1));
             L.dl3 = o;                                      // the layout's download: one region
-            L.lhdr = piece(4 * kHdrWords); L.dperm = piece(4 * Dz); L.blk = piece(16 * nbm); L.hvb = piece(4 * nbm);
+            L.lhdr = piece(4 * kHdrWords); L.dperm = piece(4 * D7); L.blk = piece(16 * nbm); L.hvb = piece(4 * nbm);
             L.hvoff = piece(4 * 4); L.rowmap = piece(4 * 64 * ni); L.woff = piece(4 * (ni + 1)); L.wsplit = piece(ni);
             L.dl3_end = o;
+        }
+        L.pxy = L.rcam = L.rfirst = L.pcam = L.cbox = o;
+        if (multi) {
+            // the points' own coordinates (with order_xy: beside it), the edges' cameras, per point its first edge and
+            // its camera, per camera (and the bucket without one) its box
+            L.pxy = piece(d.order_xy ? 24 * Pz : 0); L.rcam = piece(4 * (size_t)R); L.rfirst = piece(4 * Pz); L.pcam = piece(4 * Pz);
+            L.cbox = piece(32 * ((size_t)std::max(d.n_cams, 1) + 1));
         }
         L.total = o;
     }
@@ -987,6 +1069,9 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         err = "plan builder: allocation failed";
         return -1;
     }
+    if (g_timing)
+        std::fprintf(stderr, "[deftri plan] arena %.1f MiB of %.1f, pinned staging %.1f MiB\n", L.total / 1048576.0, cap_ / 1048576.0,
+                     pin_cap_ / 1048576.0);
     char *B = buf_;
     int *d_ap = (int *)(B + L.ap), *d_par = (int *)(B + L.par), *d_root = (int *)(B + L.root), *d_flag = (int *)(B + L.flag),
         *d_gid = (int *)(B + L.gid), *d_grep = (int *)(B + L.grep), *d_hist = (int *)(B + L.hist), *d_gpos = (int *)(B + L.gpos),
@@ -1004,6 +1089,8 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     if (D > 0) hipMemcpyAsync(B + L.dep_point, d.dep_point, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     hipMemcpyAsync(d_xy, xy, 8 * (size_t)stride * Pz, hipMemcpyHostToDevice, st_);
     if (with_layout && D > 0) hipMemcpyAsync(B + L.dscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
+    if (multi && R > 0) hipMemcpyAsync(B + L.rcam, d.rep_cam, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
+    if (multi && d.order_xy) hipMemcpyAsync(B + L.pxy, d.points, 24 * Pz, hipMemcpyHostToDevice, st_);
     hipEventRecord(ev_[1], st_);
     // 1. groups
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
@@ -1019,22 +1106,46 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
                        d_mm);
     hipLaunchKernelGGL(dev::k_minmax_final, dim3(1), dim3(kBlk), 0, st_, mm_grid, (const double *)d_mm, d_lohi);
     LAUNCH(k_keys, P, d_ng, (const int *)d_grep, (const double *)d_xy, stride, (const double *)d_lohi, d_key[0], d_id[0]);
-    int cur = 0;
+    // the stable LSD radix sort of the *np keys in d_key[0] / d_id[0]; returns the buffer that holds the result
     const dim3 rgrid((unsigned)std::min(rtile, kGridMax));
-    for (int pass = 0; pass < kRadixPasses; pass++) {
-        const int sh = kPlanRadixBits * pass;
-        hipLaunchKernelGGL(dev::k_radix_hist, rgrid, dim3(kBlk), 0, st_, d_ng, (const uint64_t *)d_key[cur], sh, d_hist, rtile);
-        scan(d_hist, (int64_t)kRadixDigits * rtile);
-        hipLaunchKernelGGL(dev::k_radix_scatter, rgrid, dim3(kBlk), 0, st_, d_ng, (const uint64_t *)d_key[cur],
-                           (const int *)d_id[cur], sh, (const int *)d_hist, rtile, d_key[cur ^ 1], d_id[cur ^ 1]);
-        cur ^= 1;
-    }
+    auto radix_sort = [&](const int *np, int passes) {
+        int cur = 0;
+        for (int pass = 0; pass < passes; pass++) {
+            const int sh = kPlanRadixBits * pass;
+            hipLaunchKernelGGL(dev::k_radix_hist, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)d_key[cur], sh, d_hist, rtile);
+            scan(d_hist, (int64_t)kRadixDigits * rtile);
+            hipLaunchKernelGGL(dev::k_radix_scatter, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)d_key[cur],
+                               (const int *)d_id[cur], sh, (const int *)d_hist, rtile, d_key[cur ^ 1], d_id[cur ^ 1]);
+            cur ^= 1;
+        }
+        return cur;
+    };
+    int cur = radix_sort(d_ng, kRadixPasses);
     LAUNCH(k_gpos, P, d_ng, (const int *)d_id[cur], d_gpos);
     hipEventRecord(ev_[3], st_);
     // 3. rows: the points by (gpos[gid[p]], p)
     LAUNCH(k_gp, P, P, (const int *)d_gid, (const int *)d_gpos, d_gp);
     int *d_start = d_flag;                                  // the groups' offsets (P + 1: keys past ng are empty)
     sort_by_row(P, d_gp, P, d_start, d_por, d_hdr);
+    if (multi) {
+        // several pairs: by (camera, curve key in the camera's box, point) instead, when every point has one camera.
+        // The camera is the key's bits from 42 up: ceil(bits(C) / 7) more passes of the same sort
+        const int C = std::max(d.n_cams, 1);
+        int cbits = 0;
+        while (C >> cbits) cbits++;
+        const double *d_pts = d.order_xy ? (const double *)(B + L.pxy) : (const double *)d_xy;
+        int *d_rcam = (int *)(B + L.rcam), *d_rfirst = (int *)(B + L.rfirst), *d_pcam = (int *)(B + L.pcam);
+        unsigned long long *d_box = (unsigned long long *)(B + L.cbox);
+        LAUNCH(k_fill, 1, (int64_t)1, d_hdr + kHdrP, P);
+        LAUNCH(k_fill, P, (int64_t)P, d_rfirst, INT_MAX);
+        LAUNCH(k_rep_first, R, R, (const int *)(B + L.rep_point), d_rfirst);
+        LAUNCH(k_cam_check, R, R, (const int *)(B + L.rep_point), (const int *)d_rcam, (const int *)d_rfirst, d_hdr);
+        LAUNCH(k_box_init, 4 * (C + 1), 4 * (C + 1), d_box);
+        LAUNCH(k_cam_box, P, P, C, (const int *)d_rfirst, (const int *)d_rcam, d_pts, 3, d_pcam, d_box);
+        LAUNCH(k_cam_keys, P, P, (const int *)d_pcam, d_pts, 3, (const unsigned long long *)d_box, d_key[0], d_id[0]);
+        cur = radix_sort(d_hdr + kHdrP, kRadixPasses + (cbits + kPlanRadixBits - 1) / kPlanRadixBits);
+        LAUNCH(k_rows_pick, P, P, (const int *)d_hdr, (const int *)d_id[cur], d_por);
+    }
     LAUNCH(k_inverse, P, (int64_t)P, (const int *)d_por, d_rop);
     hipEventRecord(ev_[4], st_);
     // (gp is the region's last piece: the tile stages read it on the device, so it stays there)
@@ -1330,17 +1441,19 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
     const int32_t P = P_, S = d.n_scales;
     const int64_t E = E_, D = d.n_depth, nloc = (int64_t)H.arap_ids.size();
     const int32_t nao = H.n_arap_owned;
-    if (!buf_ || !with_layout_ || nloc_ < 0 || nloc_ != nloc || P != d.n_points || E != d.n_arap || d.n_pairs != 1 || S < 0 || S > 2 ||
-        nao < 0 || nao > nloc || (int64_t)H.dep_ids.size() != D || (D > 0 && S < 1) || H.lo != 0 || H.hi != P || P < 1) {
+    if (!buf_ || !with_layout_ || nloc_ < 0 || nloc_ != nloc || P != d.n_points || E != d.n_arap ||
+        (multi_ ? d.n_pairs < 2 : d.n_pairs != 1 || S > 2) || S < 0 || nao < 0 || nao > nloc || (int64_t)H.dep_ids.size() != D || (D > 0 && S < 1) || H.lo != 0 || H.hi != P || P < 1) {
         err = "plan builder: layout() without the edges of this problem";
         return -1;
     }
+    // several pairs (multi_): stage 7 is written for one pair and two scales, so it stays on the host
+    const bool dev7 = !multi_;
     int n0 = 0;                                           // depth edges of scale 0
-    for (int64_t e = 0; e < D; e++) n0 += d.dep_scale[e] == 0;
+    for (int64_t e = 0; dev7 && e < D; e++) n0 += d.dep_scale[e] == 0;
     auto blocks = [](int64_t n) { return (n + kSpBlock - 1) / kSpBlock; };
-    const int64_t nb = blocks(nao) + blocks(nloc - nao) + blocks(n0) + blocks(D - n0);
+    const int64_t nb = dev7 ? blocks(nao) + blocks(nloc - nao) + blocks(n0) + blocks(D - n0) : 0;
     const int ni = (P + 31) / 32, nwin = (P + kSpSortWindow - 1) / kSpSortWindow;
-    if (nb > E / kSpBlock + D / kSpBlock + 4) { err = "plan builder: more phase-1 blocks than the arena holds"; return -1; }
+    if (dev7 && nb > E / kSpBlock + D / kSpBlock + 4) { err = "plan builder: more phase-1 blocks than the arena holds"; return -1; }
     // the wave layout's int scan: a row holds at most 2 kPlanRunMax slots, a wave's steps are one row's count
     const bool waves = 16 * (int64_t)P < (1LL << 31);
     char *B = buf_;
@@ -1361,14 +1474,16 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
     // 7. dperm, the blocks, their dispatch order, the heavy vertices' lists
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
     hipMemsetAsync(d_hvoff, 0, 4 * 4, st_);
-    LAUNCH(k_dep_flag, D + 1, (int)D, d_dep_ids, d_dscale, d_dflag);
-    scan(d_dflag, D + 1);
-    LAUNCH(k_dperm, D, (int)D, d_dep_ids, d_dscale, (const int *)d_dflag, d_dperm);
-    LAUNCH(k_blk_make, nb, (int)nb, (int)nao, (int)nloc, n0, (int)D, d_aid, d_ap, d_rop, d_dep_point, d_dep_ids, (const int *)d_dperm,
-           d_dscale, d_blk0, d_bkey);
-    sort_by_row(nb, d_bkey, P, d_boff, d_bord, d_hdr);
-    LAUNCH(k_blk_deal, nb, (int)nb, (const int *)d_bord, (const int4 *)d_blk0, d_blk);
-    hipLaunchKernelGGL(dev::k_blk_heavy, dim3(1), dim3(1024), 0, st_, (int)nb, 1 + S, (const int4 *)d_blk, d_hvb, d_hvoff);
+    if (dev7) {
+        LAUNCH(k_dep_flag, D + 1, (int)D, d_dep_ids, d_dscale, d_dflag);
+        scan(d_dflag, D + 1);
+        LAUNCH(k_dperm, D, (int)D, d_dep_ids, d_dscale, (const int *)d_dflag, d_dperm);
+        LAUNCH(k_blk_make, nb, (int)nb, (int)nao, (int)nloc, n0, (int)D, d_aid, d_ap, d_rop, d_dep_point, d_dep_ids,
+               (const int *)d_dperm, d_dscale, d_blk0, d_bkey);
+        sort_by_row(nb, d_bkey, P, d_boff, d_bord, d_hdr);
+        LAUNCH(k_blk_deal, nb, (int)nb, (const int *)d_bord, (const int4 *)d_blk0, d_blk);
+        hipLaunchKernelGGL(dev::k_blk_heavy, dim3(1), dim3(1024), 0, st_, (int)nb, 1 + S, (const int4 *)d_blk, d_hvb, d_hvoff);
+    }
     hipEventRecord(ev_[22], st_);
     // 8b. the windows' rows by slot count, the wave cut from every multiple of 32, the chain from row 0
     if (waves) {
@@ -1409,7 +1524,7 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
     if (hdr[kHdrBound]) return 1;
     const int32_t nw = waves ? hdr[kLhNw] : 0;
     const int64_t nsl = waves ? hdr[kLhSlots] : 0;
-    if (hvoff[0] != 0 || hvoff[1 + S] < 0 || hvoff[1 + S] > nb || (waves && (nw < 1 || nw > ni || nsl < 0 || nsl > 16 * (int64_t)P))) {
+    if ((dev7 && (hvoff[0] != 0 || hvoff[1 + S] < 0 || hvoff[1 + S] > nb)) || (waves && (nw < 1 || nw > ni || nsl < 0 || nsl > 16 * (int64_t)P))) {
         err = "plan builder: the device wrote impossible layout counts";
         return -1;
     }
@@ -1419,11 +1534,13 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
         const V *p = (const V *)at(off);
         v.assign(p, p + n);
     };
-    take(H.dperm, L.dperm, (size_t)D);
-    take(H.blk, L.blk, 4 * (size_t)nb);
-    take(H.hv_blk, L.hvb, (size_t)hvoff[1 + S]);
-    H.hv_blk_off.assign(hvoff, hvoff + 1 + S + 1);
-    ran |= 1;
+    if (dev7) {
+        take(H.dperm, L.dperm, (size_t)D);
+        take(H.blk, L.blk, 4 * (size_t)nb);
+        take(H.hv_blk, L.hvb, (size_t)hvoff[1 + S]);
+        H.hv_blk_off.assign(hvoff, hvoff + 1 + S + 1);
+        ran |= 1;
+    }
     // (the host builds stage 8b when 64 x slots does not fit an int)
     if (!waves || 64 * nsl >= (1LL << 31)) return 0;
     take(H.rowmap, L.rowmap, 64 * (size_t)nw);

@@ -129,6 +129,7 @@ struct deftri_ctx {
     int plan_builder = 0;                   // deftri_set_plan_builder
     int tile_builder = 0;                   // deftri_set_tile_builder
     int layout_builder = 0;                 // deftri_set_layout_builder
+    int multi_pair_builder = 0;             // deftri_set_multi_pair_builder
     PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     std::unique_ptr<GraphBuilderDevice> gbdev;   // the graph builder's device arena and pinned staging (graph_build_dev.hip)
@@ -1246,6 +1247,13 @@ int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode) {
     return 0;
 }
 
+int deftri_set_multi_pair_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_multi_pair_builder: mode is 0 (a plan of several pairs on the host) or 1 (device stages)");
+    ctx->multi_pair_builder = mode;
+    return 0;
+}
+
 int deftri_set_graph_builder(deftri_ctx *ctx, int32_t mode) {
     if (!ctx) return DEFTRI_E_ARG;
     if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_graph_builder: mode is 0 (the graph build's passes on the host) or 1 (device stages)");
@@ -1279,7 +1287,7 @@ static int debug_build_plan(deftri_ctx *ctx, const deftri_problem_desc *desc, in
     std::string err;
     rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
                             mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build, ctx->tile_builder, ctx->layout_builder,
-                            false);
+                            false, ctx->multi_pair_builder);
     return rc ? fail(ctx, rc, err) : 0;
 }
 
@@ -1694,6 +1702,7 @@ int deftri_problem_upload(deftri_ctx *ctx, const deftri_problem_desc *desc) {
         ctx->sp->plan_builder = ctx->plan_builder;
         ctx->sp->tile_builder = ctx->tile_builder;
         ctx->sp->layout_builder = ctx->layout_builder;
+        ctx->sp->multi_pair_builder = ctx->multi_pair_builder;
         ctx->sp->plan_dev = ctx->plan_builder ? plan_device(ctx) : nullptr;
         ctx->sp->plan_build = &ctx->plan_build;
         rc = ctx->sp->upload(*desc);

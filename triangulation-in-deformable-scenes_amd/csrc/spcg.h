@@ -207,10 +207,13 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // before the builder's arena grows.  tile_mode (deftri_set_tile_builder) 1: where mode 1 applies, build_tiles on
 // `pd` as well (PlanDevice::tiles; stages bits 6-9).  layout_mode (deftri_set_layout_builder) 1: where the device
 // built the tile layout, stages 7 and 8b on `pd` too (PlanDevice::layout; stages bits 10-12); keep_slots then
-// leaves pmap and pidx on the device (out.pmap_dev, out.pidx_dev) — unless DEFTRI_PLAN_DIGEST asks for the digest
+// leaves pmap and pidx on the device (out.pmap_dev, out.pidx_dev) — unless DEFTRI_PLAN_DIGEST asks for the digest.
+// multi_mode (deftri_set_multi_pair_builder) 1: mode 1 applies to several pairs on one rank as well (any number of
+// scales, fewer than 2^21 cameras): stages 1-3 with the keyframe-major rows, 5, 6 and 8 on `pd`, build_tiles_multi
+// on the host whatever tile_mode says, and with layout_mode 1 stage 8b (stages bits 11 and 12; stage 7 on the host)
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false);
+                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false, int multi_mode = 0);
 // FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
 // not null one digest per array in that block's order (names: kPlanDigestNames)
 uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
@@ -386,6 +389,7 @@ class SpSolver {
     // build reports what it did (deftri_plan_build_info; may be null)
     int plan_builder = 0, tile_builder = 0;          // (tile_builder: deftri_set_tile_builder)
     int layout_builder = 0;                          // deftri_set_layout_builder
+    int multi_pair_builder = 0;                      // deftri_set_multi_pair_builder
     PlanDevice *plan_dev = nullptr;
     PlanBuildInfo *plan_build = nullptr;
     int refresh(const deftri_problem_desc &d);     // same structure: values only, plan kept

@@ -158,7 +158,9 @@ uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
 
 // pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
 // stages: the bit mask of the stages it ran.  layout_dev (deftri_set_layout_builder): 1 stages 7 and 8b on pd too
-// where it built the tile layout, 2 the same with pmap and pidx left on the device (H.pmap_dev, H.pidx_dev)
+// where it built the tile layout, 2 the same with pmap and pidx left on the device (H.pmap_dev, H.pidx_dev).
+// Several pairs (deftri_set_multi_pair_builder; the caller has checked one rank and the tile request): pd numbers the
+// rows keyframe-major, build_tiles_multi stays on the host, and layout_dev runs stage 8b alone
 static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                       bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false,
                       int layout_dev = 0) {
@@ -184,12 +186,14 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
 
     std::vector<int32_t> gid, gpos, gp_dev;   // group of each point; the groups' Morton positions; gpos[gid[p]]
     int32_t ng = 0;
+    const bool multi_dev = pd && Q > 1;
     if (pd) {
         // stages 1-3 on the device (plan_dev.hip): the same groups, order and rows
         // (the tile stages' int counts: padded entries <= 2 E + 64 ng, and a group id shifted by 2 bits)
         tiles_dev = tiles_dev && tile && Q == 1 && S <= 2 && E > 0 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31) &&
                     sp_tile_lds_budget() < (1LL << 30);
-        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev, tiles_dev && layout_dev);
+        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev,
+                                (tiles_dev || multi_dev) && layout_dev, multi_dev);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         *stages |= 7;
         stage("1-3 on the device (wall)");
@@ -367,8 +371,12 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         // several pairs on one rank: tiles per pair over (pair, group) units (spcg_tile.cpp)
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
-        std::vector<int32_t> gp(P);
-        for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
+        std::vector<int32_t> gp;
+        if (pd) gp.swap(gp_dev);
+        else {
+            gp.resize(P);
+            for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
+        }
         TileInput ti;
         ti.P = P; ti.ng = ng; ti.E = E; ti.ap = ap; ti.gpos = gp.data(); ti.row_of_point = H.row_of_point.data();
         ti.Q = Q; ti.S = S; ti.pair = d.arap_pair; ti.D = D; ti.dep_point = d.dep_point; ti.dep_scale = d.dep_scale;
@@ -548,7 +556,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     // deftri_set_layout_builder: stages 7 and 8b on the device (plan_dev.hip) from the arrays edges()
     // left there; what it did not run (ran's bits clear) stays with the host code below
     bool dev7 = false, dev8b = false;
-    if (dev_edges && tiles_built_dev && layout_dev) {
+    if (dev_edges && (tiles_built_dev || multi_dev) && layout_dev) {
         int32_t ran = 0;
         const int rc = pd->layout(d, before_alloc, H, layout_dev == 1 || digest, ran, err);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
@@ -801,15 +809,18 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode, int layout_mode, bool keep_slots) {
+                       int tile_mode, int layout_mode, bool keep_slots, int multi_mode) {
     const auto t0 = std::chrono::steady_clock::now();
     info = PlanBuildInfo();
     auto done = [&](int rc) {
         info.ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         return rc;
     };
-    // the condition of stage 4a's one-pair tile branch, and a device
-    const bool applies = mode == 1 && pd && nranks == 1 && d.n_pairs == 1 && d.n_scales <= 2 && d.n_arap > 0 &&
+    // the condition of stage 4a's one-pair tile branch, and a device; with deftri_set_multi_pair_builder that of its
+    // multi-pair branch as well (the camera is the sort key's bits from 42 up: below 2^21 cameras)
+    const bool one_pair = d.n_pairs == 1 && d.n_scales <= 2;
+    const bool multi_pair = multi_mode == 1 && d.n_pairs > 1 && d.n_cams < (1 << 21);
+    const bool applies = mode == 1 && pd && nranks == 1 && (one_pair || multi_pair) && d.n_arap > 0 &&
                          d.n_arap < (1LL << 29) && tile;
     if (mode == 1 && !applies) info.reason = 1;
     if (applies) {

@@ -96,6 +96,7 @@ def load():
         "deftri_set_plan_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_layout_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_set_multi_pair_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_debug_plan_layout_stats": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_int64), C.c_int32]),
         "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "deftri_set_graph_builder": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -246,7 +247,7 @@ EXPORTED = [
     "deftri_undistort_points", "deftri_image_bounds", "deftri_distribute_features",
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
     "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
-    "deftri_set_layout_builder", "deftri_debug_plan_layout_stats",
+    "deftri_set_layout_builder", "deftri_debug_plan_layout_stats", "deftri_set_multi_pair_builder",
     "deftri_set_graph_builder", "deftri_graph_build_info",
 ]
 
@@ -735,8 +736,16 @@ class Context:
     def set_layout_builder(self, mode):
         """Who builds the phase-1 blocks and the phase-2 wave layout where plan builder 1 and tile builder 1 both ran
         (deftri_set_layout_builder): 0 the host (default), 1 the device stages (plan_build_info stages bits 10-12);
-        an upload then keeps pmap and pidx on the device.  No effect anywhere else."""
+        an upload then keeps pmap and pidx on the device.  On several pairs under set_multi_pair_builder(1): the wave
+        layout alone (bits 11-12).  No effect anywhere else."""
         self._check(self.lib.deftri_set_layout_builder(self.h, int(mode)))
+
+    def set_multi_pair_builder(self, mode):
+        """Whether plan builder 1's device stages also take a problem of several keyframe pairs
+        (deftri_set_multi_pair_builder): 0 no (default), 1 yes — one rank, the tile layout requested; plan_build_info
+        stages 0x3f, with layout builder 1 0x183f (stage 8b; an upload then keeps pmap and pidx on the device).
+        build_tiles_multi and stage 7 stay on the host.  No effect with plan builder 0 or on one pair."""
+        self._check(self.lib.deftri_set_multi_pair_builder(self.h, int(mode)))
 
     def plan_build_info(self):
         """What the last iterative plan build did (deftri_plan_build_info): builder_used, stages (bit mask),

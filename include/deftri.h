@@ -1297,8 +1297,8 @@ int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode);
    position in that camera's box, point id), or the group order where a point's reprojection edges name two
    cameras — and, after build_tiles_multi, the rotation numbering, the reprojection / depth edges by row and the
    incidences (stages 0x3f).  build_tiles_multi (csrc/spcg_tile.cpp) stays on the host whatever
-   deftri_set_tile_builder says (bits 6-9 are never set); where it refuses the graph the host goes on from the
-   device's rows (stages 0x7).  With deftri_set_layout_builder(1) stage 8b (rowmap, woff, wsplit, pmap, pidx) runs
+   deftri_set_tile_builder says (bits 6-9 come only with deftri_set_multi_tile_builder(1)); where it refuses the
+   graph the host goes on from the device's rows (stages 0x7).  With deftri_set_layout_builder(1) stage 8b (rowmap, woff, wsplit, pmap, pidx) runs
    on the device too and an upload keeps pmap and pidx there (stages 0x183f: bits 11 and 12); stage 7 (dperm, blk,
    hv_blk, hv_blk_off) is the host's for several pairs, so bit 10 stays clear.  A row with more than 256
    incidences reaches the builder's bound: the whole plan is then the host's (reason 2).  The plan is equal array
@@ -1307,6 +1307,23 @@ int deftri_set_layout_builder(deftri_ctx *ctx, int32_t mode);
    error inside the builder fails the upload with DEFTRI_E_HIP.  deftri_debug_plan_digest and
    deftri_debug_plan_layout_stats with mode 1 honour this setting. */
 int deftri_set_multi_pair_builder(deftri_ctx *ctx, int32_t mode);
+/* Who cuts the tile layout of several keyframe pairs (build_tiles_multi, csrc/spcg_tile.cpp) wherever
+   deftri_set_multi_pair_builder(1)'s device stages apply: 0 (default) the host; 1 the device stages of
+   csrc/plan_dev.hip — the (pair, group) units in each pair's own Morton order and the edges by unit (stages bit 6),
+   the partition per pair (bit 7), entries, slots, own rows and shares (bit 8), cross slots (bit 9) — which also keep
+   the groups and the tile-entry edge order on the device between the plan builder's stages: stages 0x3ff, 0x1bff with
+   layout builder 1 (stage 7 stays the host's, bit 10 clear).  The plan is equal array for array.  A graph
+   build_tiles_multi refuses (not two depth scales per pair, an edge inside one group, an edge's copies in two
+   groups, a unit whose rows differ between its edges, a vertex with more than 64 ARAP edges in a pair, a depth edge
+   outside its pair's mesh, a row in no pair's mesh) is handed to the host's build_tiles_multi after the device's
+   rows, as with mode 0 (stages 0x7); so is one whose (pair, group) table has 2^28 entries or more, which the host
+   then accepts (stages 0x3f).  A unit with more than 256 in-edges, or a row in more than 256 pairs, reaches the
+   builder's bound (reason 2).  It is a switch of its own: deftri_set_tile_builder acts on one pair only.  Anywhere
+   else — one pair, plan or multi-pair builder 0, a sharded or host-only context, no tile request — it has no effect.
+   DEFTRI_E_ARG: a mode other than 0 or 1.  A HIP error inside the builder fails the upload with DEFTRI_E_HIP.
+   deftri_debug_plan_digest, deftri_debug_plan_tile_digest and deftri_debug_plan_layout_stats with mode 1 honour this
+   setting. */
+int deftri_set_multi_tile_builder(deftri_ctx *ctx, int32_t mode);
 /* What the last iterative plan build of this context did: builder_used 0 / 1; stages = bit mask of
    the stages that ran on the device (bit 0 groups, 1 Morton order, 2 rows, 3 rotation numbering,
    4 rep/depth by row, 5 incidences; with deftri_set_tile_builder(1) also 6 groups and edges by group,
@@ -1315,7 +1332,8 @@ int deftri_set_multi_pair_builder(deftri_ctx *ctx, int32_t mode);
    10 phase-1 blocks, 11 row sort and wave cut, 12 slot fill, set only when those stages ran: 0x1fff for a full
    device build with all three switches; several pairs with deftri_set_multi_pair_builder(1): 0x3f built on the
    device, 0x183f with layout builder 1 — bits 6-10 stay with the host there — and 0x7 where build_tiles_multi
-   refused); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable, 2 a bounded loop reached
+   refused; with deftri_set_multi_tile_builder(1) also bits 6 units and edges by unit, 7 partition, 8 entries, slots,
+   own rows and shares, 9 cross slots: 0x3ff, 0x1bff with layout builder 1, bit 10 staying clear); reason = why builder_used is 0 although mode is 1 (0 none, 1 not applicable, 2 a bounded loop reached
    its bound); ms = wall time of the build.  All zero before the first build. */
 int deftri_plan_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_t *stages,
                            int32_t *reason, double *ms);
@@ -1346,6 +1364,13 @@ int deftri_graph_build_info(const deftri_ctx *ctx, int32_t *builder_used, int32_
    context (mode 1 is then not applicable).  deftri_plan_build_info afterwards describes this build. */
 int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode,
                              int32_t tile, uint64_t *digests, int32_t cap, int32_t *n);
+/* TEST ONLY: build the plan exactly as deftri_debug_plan_digest does (the context's switches honoured) and return
+   FNV-1a digests of what only a tile plan of several pairs holds and the 33 above leave out: tile_trow, tile_tdst,
+   tile_poff, tile_nshare, the scalars {ntile, tile_entries, tile_cross, tile_segmax, tile_lds, tile_halo_rows,
+   tile_planes, tile_multi} as int64, then their combination.  *n receives the count (6); cap too small:
+   DEFTRI_E_ARG.  For a one-pair plan the four arrays are empty.  Works on a host-only context. */
+int deftri_debug_plan_tile_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode,
+                                  int32_t tile, uint64_t *digests, int32_t cap, int32_t *n);
 /* TEST ONLY: build the plan exactly as deftri_debug_plan_digest does and write 8 figures of its phase-1 blocks and
    wave layout, computed on the host from the finished plan: waves; waves with wsplit 1; waves whose 64-row
    look-ahead covers rows of two sort windows; waves with zero steps; the slot steps (woff's last entry); phase-1

@@ -6,9 +6,10 @@ the per-stage lines pass through to stderr and are counted per name as well.
 
 MULTI_PAIR_BUILDER (deftri_set_multi_pair_builder, with plan builder 1): 0 the plan on the host (default), 1 the device
 stages of a multi-pair plan.  LAYOUT_BUILDER (deftri_set_layout_builder): 1 the wave layout on the device too.
+MULTI_TILE_BUILDER (deftri_set_multi_tile_builder): 1 the tile layout (build_tiles_multi) on the device too.
 An older library under DEFTRI_LIB has no such entries: they are called only when asked for.
 
-usage: python tools/multi_pair_plan_timing.py N K [MULTI_PAIR_BUILDER] [LAYOUT_BUILDER]"""
+usage: python tools/multi_pair_plan_timing.py N K [MULTI_PAIR_BUILDER] [LAYOUT_BUILDER] [MULTI_TILE_BUILDER]"""
 import json
 import os
 import pathlib
@@ -27,6 +28,7 @@ from deftri import capi, sim  # noqa: E402
 n, k = int(sys.argv[1]), int(sys.argv[2])
 multi_pair_builder = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 layout_builder = int(sys.argv[4]) if len(sys.argv) > 4 else 0
+multi_tile_builder = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 p = sim.multi_view_problem(n, k)
 
 
@@ -58,6 +60,8 @@ with capi.Context(0) as c:
         c.set_multi_pair_builder(multi_pair_builder)
     if layout_builder:
         c.set_layout_builder(layout_builder)
+    if multi_tile_builder:
+        c.set_multi_tile_builder(multi_tile_builder)
     for i in range(3):
         dt, text = captured(lambda: c.upload(p))
         m = re.search(r"\[deftri upload\] plan ([0-9.]+) ms, values \+ allocations \+ copies ([0-9.]+) ms", text)
@@ -74,6 +78,7 @@ with capi.Context(0) as c:
         uploads.append(u)
     info = c.plan_info()
 out = {"n": n, "k": k, "points": p.n_points, "pairs": p.n_pairs, "arap_edges": int(len(p.arap_pair)),
-       "multi_pair_builder": multi_pair_builder, "layout_builder": layout_builder, "plan": info.get("plan"),
+       "multi_pair_builder": multi_pair_builder, "layout_builder": layout_builder, "multi_tile_builder": multi_tile_builder,
+       "plan": info.get("plan"),
        "tiles": info.get("tiles"), "lib": os.environ.get("DEFTRI_LIB", "built"), "cold": uploads[0], "repeated": uploads[1:]}
 print(json.dumps(out), flush=True)

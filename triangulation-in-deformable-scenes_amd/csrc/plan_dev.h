@@ -4,7 +4,8 @@
 // host's bit for bit.  With deftri_set_tile_builder the tile layout (spcg_tile.cpp build_tiles, stage 4a)
 // is built there too, and with deftri_set_layout_builder the phase-1 blocks and the phase-2 wave layout
 // (stages 7 and 8b), whose two slot arrays can stay on the device.  deftri_set_multi_pair_builder opens
-// stages 1-3, 5, 6, 8 and 8b to a plan of several pairs.
+// stages 1-3, 5, 6, 8 and 8b to a plan of several pairs, and deftri_set_multi_tile_builder builds its tile
+// layout (spcg_tile.cpp build_tiles_multi, stage 4a) there as well.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -45,12 +46,12 @@ class PlanDevice {
     // kernels, one download.  before_alloc: called (and cleared) before the arena grows
     int rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
              std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-             std::string &err, bool with_tiles = false, bool with_layout = false, bool multi = false);
+             std::string &err, bool with_tiles = false, bool with_layout = false, bool multi = false, bool multi_tiles = false);
     // deftri_set_multi_pair_builder: rows() with multi takes a problem of several pairs and numbers the
     // rows keyframe-major as spcg_plan.cpp stage 3 does for a multi-pair tile plan — by (camera of the point's first
     // reprojection edge, curve key of the point's own position in that camera's box, point) — unless a point's
     // reprojection edges name two cameras, where the group order stays; the choice is made on the device from a
-    // flag word.  gp always comes back (build_tiles_multi runs on the host); with_layout then lays out stage 8b's
+    // flag word.  gp comes back unless multi_tiles keeps it for tiles_multi(); with_layout then lays out stage 8b's
     // scratch only, and layout() runs stage 8b alone (ran bits 1 and 2).  Needs n_cams < 2^21
     // stages 4-6 (rotation numbering, rep / depth edges by row, incidences) for H.arap_ids on the rows of the
     // last rows() call: one upload of arap_ids, the kernels, one download into H
@@ -64,6 +65,15 @@ class PlanDevice {
     // is downloaded for the host's build_tiles
     int tiles(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
               SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err);
+    // deftri_set_multi_tile_builder: rows() with multi and multi_tiles uploads arap_pair and dep_scale too
+    // and leaves gp on the device.  tiles_multi() is build_tiles_multi (spcg_tile.cpp) on the rows of the last rows()
+    // call: the (pair, group) units in each pair's own Morton order, the edges by unit, the partition per pair,
+    // entries, slots, own rows and shares, cross slots, then one download of the tile arrays and scalars into H and of
+    // the edge order into `order`; edges() then takes arap_ids from the device.  Its scratch is an arena of its own,
+    // laid out here because it follows the group count.  Returns as tiles() does; 2 also where a count leaves the int
+    // range the kernels index with (build_tiles_multi then runs on the host)
+    int tiles_multi(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
+                    SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err);
     // deftri_set_layout_builder: rows() with with_layout lays out the scratch of stages 7 and 8b
     // and uploads dep_scale with the other inputs.
     // layout() is those two stages on the arrays edges() left on the device: dperm, blk, hv_blk, hv_blk_off (ran
@@ -76,15 +86,18 @@ class PlanDevice {
 
  private:
     bool reserve(size_t dev_bytes, size_t pin_bytes, std::function<void()> *before_alloc);
-    void scan(int *data, int64_t n);
-    void sort_by_row(int64_t n, const int *key, int32_t nkeys, int *off, int *out, int *hdr);
+    // part / cur: the scratch of the scan's tile sums and of the fill's cursors (null: the arena's own pieces)
+    void scan(int *data, int64_t n, int *part = nullptr);
+    void sort_by_row(int64_t n, const int *key, int32_t nkeys, int *off, int *out, int *hdr, int *cur = nullptr, int *part = nullptr);
+    int radix_sort(uint64_t *const key[2], int *const id[2], int *hist, int *part, const int *np, int ntile, int passes);
     void report(int first, int last, const char *const *names) const;
     int dev_;
     hipStream_t st_;
     char *buf_ = nullptr, *pin_ = nullptr, *tbuf_ = nullptr;     // tbuf_: the tile arrays (sized after the counts)
     char *sbuf_ = nullptr;                                       // the slot arrays pmap | pidx (sized after the cut)
-    size_t cap_ = 0, pin_cap_ = 0, tcap_ = 0, scap_ = 0;
-    hipEvent_t ev_[28] = {};
+    char *mbuf_ = nullptr;                                       // the scratch of tiles_multi (sized by the units)
+    size_t cap_ = 0, pin_cap_ = 0, tcap_ = 0, scap_ = 0, mcap_ = 0;
+    hipEvent_t ev_[40] = {};
     // the arena's pieces (byte offsets), laid out by rows()
     struct Layout {
         size_t ap, rot, rep_point, dep_point, xy, par, root, flag, gid, grep, mm, lohi, key[2], id[2], hist, gpos, cur,
@@ -96,10 +109,13 @@ class PlanDevice {
             dscale, dflag, bkey, boff, bord, blk0, order, scnt, wnext, wsteps, wsp, wja, wjb, wmark, widx, wsoff, dl3, lhdr,
             dperm, blk, hvb, hvoff, rowmap, woff, wsplit, dl3_end,
             // the keyframe-major rows of several pairs (multi)
-            pxy, rcam, rfirst, pcam, cbox, total;
+            pxy, rcam, rfirst, pcam, cbox,
+            // arap_pair and dep_scale for tiles_multi (multi_tiles; mdscale is dscale where with_layout laid it out)
+            mpair, mdscale, total;
     } L_{};
-    bool with_tiles_ = false, order_on_dev_ = false;           // order_on_dev_: tiles() left arap_ids in L_.oe
-    bool with_layout_ = false, multi_ = false;
+    bool with_tiles_ = false, order_on_dev_ = false;           // order_on_dev_: tiles() left arap_ids at order_dev_
+    const int *order_dev_ = nullptr;
+    bool with_layout_ = false, multi_ = false, multi_tiles_ = false;
     int32_t P_ = 0;
     int64_t E_ = 0, nloc_ = -1;                                // nloc_: the local edges of the last edges(), -1 none
 };

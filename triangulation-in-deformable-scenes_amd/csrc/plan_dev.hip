@@ -1,6 +1,7 @@
 // plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h), and
 // its tile layout (build_tiles of one rank), its phase-1 blocks and its phase-2 wave layout (§5m); for
-// several pairs the keyframe-major rows, with the same edge stages and wave layout after them (§5o).
+// several pairs the keyframe-major rows, with the same edge stages and wave layout after them (§5o), and their tile
+// layout over (pair, group) units (build_tiles_multi, §5p).
 //
 // No workgroup waits on another: a scan over more than one workgroup's elements is three launches (tile sums,
 // the scan of the sums by one workgroup, the tiles' own scans), a sort by a dense key (a row, a group) is count,
@@ -37,7 +38,9 @@ enum { kHdrBound = 0, kHdrNg = 1, kHdrNrot = 2, kHdrWords = 16,
        // the layout stages' header (stages 7 and 8b): waves, slot steps
        kLhNw = 4, kLhSlots = 5,
        // the rows of several pairs: a point with two cameras (the group order stays), the point count for the sort
-       kHdrManyCam = 10, kHdrP = 11 };
+       kHdrManyCam = 10, kHdrP = 11,
+       // the tile layout of several pairs: the units, the share planes
+       kHdrNu = 12, kHdrPlanes = 13 };
 
 namespace dev {
 
@@ -458,16 +461,18 @@ __global__ __launch_bounds__(kBlk) void k_tile_pred(int64_t E, const int *oe, co
 }
 
 // the greedy cut from every start: tend[gs] = the first group the tile begun at gs does not take (build_tiles'
-// loop; whether [gs, g] fits is a function of that set of groups alone).  At most umax + 1 steps
+// loop; whether [gs, g] fits is a function of that set of groups alone).  At most umax + 1 steps.  upair (several
+// pairs, else null): the units' pairs — a tile ends with its pair
 __global__ __launch_bounds__(kBlk) void k_tile_end(int ng, const int *start, const int *ooff, const int *okj, const int *pred,
                                                   const int *ioff, const int *ie, const int *egi, int umax, int budget, int fixed,
-                                                  int *tend, const int *hdr) {
+                                                  int *tend, const int *hdr, const int *upair) {
     if (tile_stop(hdr)) return;
     PLAN_FOR(gs64, (int64_t)ng + 1) {
         const int gs = (int)gs64;
         if (gs == ng) { tend[gs] = ng; continue; }
         int nr = 0, nh = 0, ns = 0, units = 0, g = gs;
         for (int step = 0; step <= umax && g < ng; step++) {
+            if (upair && upair[g] != upair[gs]) break;
             const int sz = start[g + 1] - start[g];
             int dnh = 0, dns = 0;
             bool was_halo = false;
@@ -583,11 +588,15 @@ struct TileOut {
     uint32_t *m0, *m1;
 };
 
-// one workgroup per tile: build_tiles' second stage as :338-468 writes it.  tne, tnh, tcut: the tiles' bases
+// one workgroup per tile: build_tiles' second stage as :338-468 writes it.  tne, tnh, tcut: the tiles' bases.
+// Several pairs (urow, upair not null; build_tiles_multi's :781-866): a group is a unit, start[u] = 2 u, a row is its
+// place 2 u + c in the tile row list (erow holds those), and urow gives the plan's row for the halo list and the cross
+// slots' targets; the tile's pair goes to the table
 __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int *start, const int *gp, const int *por,
                                                    const int *ooff, const int *oe, const int *okj, const int *pred, const int *ioff,
                                                    const int *ie, const int *egi, const int4 *erow, const int *tne, const int *tnh,
-                                                   const int *tcut, TileOut o, int *hdr, const int *hdr_in) {
+                                                   const int *tcut, TileOut o, int *hdr, const int *hdr_in, const int *urow,
+                                                   const int *upair) {
     __shared__ int hl[kTileHaloMax], hs[kTileHaloMax], ho[kTileHaloMax];   // halo groups << 2 | rows: found, sorted; row offsets
     __shared__ int gst[128], rsb[kBlk], sc[kBlk];
     __shared__ int s_hn, s_ne;
@@ -636,7 +645,7 @@ __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int
         // the own rows' slot counts: the in-edges of the row's group from the tile's groups that aim at the row
         int cnt = 0;
         if (tid < nr) {
-            const int R = r0 + tid, g = gp[por[R]];
+            const int R = r0 + tid, g = urow ? R >> 1 : gp[por[R]];
             for (int x = ioff[g]; x < ioff[g + 1]; x++) {
                 const int f = ie[x], gf = egi[f];
                 if (gf >= g0 && gf < g1) {
@@ -657,7 +666,7 @@ __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int
         if (hn > 0) nh = ho[hn - 1] + (hs[hn - 1] & 3);
         for (int r = tid; r < hn; r += kBlk) {
             const int gj = hs[r] >> 2, sz = hs[r] & 3;
-            for (int c = 0; c < sz; c++) o.halo[h0 + ho[r] + c] = start[gj] + c;
+            for (int c = 0; c < sz; c++) o.halo[h0 + ho[r] + c] = urow ? urow[start[gj] + c] : start[gj] + c;
         }
         // the entries, 256 consecutive out-edges at a time: the cut entries before each are a scan with a carry
         int carry = 0;
@@ -690,8 +699,8 @@ __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int
                 const int lrow = nr + ho[lo] - start[gj];
                 w0 |= (uint32_t)(lrow + w.z) | (uint32_t)(lrow + w.w) << 12 | kTmCut;
                 const int x = x0 + 2 * before;
-                o.xrow[x] = w.z;
-                o.xrow[x + 1] = w.w;
+                o.xrow[x] = urow ? urow[w.z] : w.z;
+                o.xrow[x + 1] = urow ? urow[w.w] : w.w;
             } else {
                 // the slot an in-tile entry takes on a row of j: its rank among the (entry, which) aimed at that
                 // row in entry order — the order (gi, e), then p1_j before p2_j
@@ -722,10 +731,139 @@ __global__ __launch_bounds__(kBlk) void k_tile_fill(const int *tstart, const int
         if (tid == 0) {
             if (k0 == k1) { o.chunk[2 * (e0 / 64)] = k0; o.chunk[2 * (e0 / 64) + 1] = x0; }
             int *T = o.tab + 8 * (int64_t)t;
-            T[0] = r0; T[1] = nr; T[2] = nh; T[3] = e0; T[4] = ne; T[5] = h0; T[6] = ns; T[7] = 0;
+            T[0] = r0; T[1] = nr; T[2] = nh; T[3] = e0; T[4] = ne; T[5] = h0; T[6] = ns; T[7] = upair ? upair[g0] : 0;
         }
         __syncthreads();
     }
+}
+
+// ---- the tile layout of several pairs (build_tiles_multi, spcg_tile.cpp) -------------------
+// A unit is a (pair q, group g) some edge end touches, flat index k = q ng + g.  Its flag is an idempotent store; its
+// points (the p1 copy upt, the p2 copy upt2) are the smallest any end names — on a graph build_tiles_multi accepts
+// every end names the same two, and k_mu_edges refuses one where an end does not
+__global__ __launch_bounds__(kBlk) void k_mu_flag(int64_t E, const int4 *ap, const int *pair, const int *gp, int Q, int ng, int *uflag,
+                                                 int *upt, int *upt2, int *hdr) {
+    PLAN_FOR(e, E) {
+        const int q = pair[e];
+        if (q < 0 || q >= Q) { hdr[kHdrRefuse] = 1; continue; }
+        const int4 v = ap[e];
+        const int ki = q * ng + gp[v.x], kj = q * ng + gp[v.z];
+        uflag[ki] = 1;
+        uflag[kj] = 1;
+        atomicMin(&upt[ki], v.x);
+        atomicMin(&upt2[ki], v.y);
+        atomicMin(&upt[kj], v.z);
+        atomicMin(&upt2[kj], v.w);
+    }
+}
+
+// per pair the box of its units' points (box [4 Q] as k_box_init leaves it; the atomics as in k_cam_box)
+__global__ __launch_bounds__(kBlk) void k_mu_box(int nU, int ng, const int *uflag, const int *upt, const double *pts,
+                                                unsigned long long *box) {
+    PLAN_FOR(k, nU) {
+        if (!uflag[k]) continue;
+        const int q = (int)k / ng;
+        for (int c = 0; c < 2; c++) {
+            const unsigned long long u = box_enc(pts[3 * (int64_t)upt[k] + c]);
+            unsigned long long *lo = box + 4 * (int64_t)q + c, *hi = lo + 2;
+            if (u < __hip_atomic_load(lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(lo, u);
+            if (u > __hip_atomic_load(hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(hi, u);
+        }
+    }
+}
+
+// uidx: the exclusive scan of the flags (nU + 1 entries), the units' numbers in ascending (q, g).  key = q << 42 | the
+// curve key of the unit's point in its pair's box, id = k
+__global__ __launch_bounds__(kBlk) void k_mu_keys(int nU, int ng, const int *uflag, const int *uidx, const int *upt, const double *pts,
+                                                 const unsigned long long *box, uint64_t *key, int *id, int *hdr) {
+    PLAN_FOR(k, nU) {
+        if (k == 0) hdr[kHdrNu] = uidx[nU];
+        if (!uflag[k]) continue;
+        const int q = (int)k / ng;
+        const unsigned long long *b = box + 4 * (int64_t)q;
+        const double lo[2] = {box_dec(b[0]), box_dec(b[1])}, hi[2] = {box_dec(b[2]), box_dec(b[3])};
+        const double *pp = pts + 3 * (int64_t)upt[k];
+        key[uidx[k]] = (uint64_t)q << 42 | curve_key(pp[0], pp[1], lo, hi);
+        id[uidx[k]] = (int)k;
+    }
+}
+
+// ids: the units in their order (q, key, g).  uid [nU] (filled with -1 before), the units' rows and pairs, and
+// ustart[u] = 2 u for u <= nmax + 1 — the "groups' first rows" the one-pair kernels read
+__global__ __launch_bounds__(kBlk) void k_mu_units(int nmax, int ng, const int *ids, const int *upt, const int *upt2, const int *rop,
+                                                  int *uid, int *urow, int *upair, int *ustart, const int *hdr) {
+    const int nu = min(hdr[kHdrNu], nmax);
+    PLAN_FOR(u, (int64_t)nmax + 2) {
+        ustart[u] = 2 * (int)u;
+        if (u >= nu) continue;
+        const int k = ids[u];
+        uid[k] = (int)u;
+        urow[2 * u] = rop[upt[k]];
+        urow[2 * u + 1] = rop[upt2[k]];
+        upair[u] = k / ng;
+    }
+}
+
+// per edge its units, and its four rows as places 2 u + c in the tile row list.  Refused: an edge inside one unit, an
+// edge's copies in two groups, an end that names another point than its unit's
+__global__ __launch_bounds__(kBlk) void k_mu_edges(int64_t E, const int4 *ap, const int *pair, const int *gp, int Q, int ng,
+                                                  const int *uid, const int *upt, const int *upt2, int *egi, int *egj, int4 *erow,
+                                                  int *hdr) {
+    PLAN_FOR(e, E) {
+        const int q = pair[e];
+        const int4 v = ap[e];
+        int ui = 0, uj = 0;
+        bool bad = q < 0 || q >= Q;
+        if (!bad) {
+            const int ki = q * ng + gp[v.x], kj = q * ng + gp[v.z];
+            ui = uid[ki];
+            uj = uid[kj];
+            bad = ui == uj || ui < 0 || uj < 0 || gp[v.y] != gp[v.x] || gp[v.w] != gp[v.z] || upt[ki] != v.x || upt2[ki] != v.y ||
+                  upt[kj] != v.z || upt2[kj] != v.w;
+        }
+        if (bad) { hdr[kHdrRefuse] = 1; ui = uj = 0; }
+        egi[e] = ui;
+        egj[e] = uj;
+        erow[e] = make_int4(2 * ui, 2 * ui + 1, 2 * uj, 2 * uj + 1);
+    }
+}
+
+// every depth edge's (row, pair of its scale) is a row of that pair's unit of its group
+__global__ __launch_bounds__(kBlk) void k_mu_depth(int64_t D, const int *dep_point, const int *dscale, const int *gp, const int *rop,
+                                                  int Q, int ng, const int *uid, const int *urow, int *hdr) {
+    PLAN_FOR(x, D) {
+        const int p = dep_point[x], q = dscale[x] >> 1;
+        const int u = q >= 0 && q < Q ? uid[q * ng + gp[p]] : -1;
+        if (u < 0 || (urow[2 * u] != rop[p] && urow[2 * u + 1] != rop[p])) hdr[kHdrRefuse] = 1;
+    }
+}
+
+// soff: the offsets of the tile row list's entries by row.  A row in no unit is refused; the share planes
+__global__ __launch_bounds__(kBlk) void k_mu_rows(int P, const int *soff, int *hdr) {
+    PLAN_FOR(r, P) {
+        const int c = soff[r + 1] - soff[r];
+        if (c == 0) hdr[kHdrRefuse] = 1;
+        else if (c - 1 > hdr[kHdrPlanes]) atomicMax(&hdr[kHdrPlanes], c - 1);
+    }
+}
+
+// spos: the place of entry k in the sort by (row, k).  Its share is its rank among its row's entries; share 0 is home
+__global__ __launch_bounds__(kBlk) void k_mu_shares(int64_t n2, const int *urow, const int *soff, const int *spos, int *trow, int *tdst) {
+    PLAN_FOR(k, n2) {
+        const int r = urow[k], j = spos[k] - soff[r];
+        tdst[k] = j;
+        trow[k] = j == 0 ? r | (int)(1u << 31) : r;
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void k_mu_nshare(int P, const int *soff, int *nshare) {
+    PLAN_FOR(r, P) nshare[r] = soff[r + 1] - soff[r];
+}
+
+// poff[q]: the first tile at or after pair q's first unit — uidx[q ng] units come before the pair, midx (the scan of
+// the tile starts' marks) counts the tiles that start before a unit; poff[Q] is the tile count
+__global__ __launch_bounds__(kBlk) void k_mu_poff(int Q, int ng, const int *uidx, const int *midx, int *poff) {
+    PLAN_FOR(q, (int64_t)Q + 1) poff[q] = midx[uidx[q * ng]];
 }
 
 // ---- stages 7 and 8b: phase-1 blocks and the phase-2 wave layout (spcg_plan.cpp) ---------------
@@ -922,11 +1060,12 @@ const bool g_timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     } while (0)
 
 PlanDevice::~PlanDevice() {
-    if (!buf_ && !pin_ && !tbuf_ && !sbuf_ && !ev_[0]) return;
+    if (!buf_ && !pin_ && !tbuf_ && !sbuf_ && !mbuf_ && !ev_[0]) return;
     hipSetDevice(dev_);
     if (buf_) hipFree(buf_);
     if (tbuf_) hipFree(tbuf_);
     if (sbuf_) hipFree(sbuf_);
+    if (mbuf_) hipFree(mbuf_);
     if (pin_) hipHostFree(pin_);
     for (hipEvent_t e : ev_) if (e) hipEventDestroy(e);
 }
@@ -956,10 +1095,10 @@ bool PlanDevice::reserve(size_t dev_bytes, size_t pin_bytes, std::function<void(
 }
 
 // the exclusive scan of data [n] in place: reduce / scan of the tile sums / apply, or one launch for one tile
-void PlanDevice::scan(int *data, int64_t n) {
+void PlanDevice::scan(int *data, int64_t n, int *part) {
     if (n <= 0) return;
     const int ntile = (int)((n + kPlanScanTile - 1) / kPlanScanTile);
-    int *part = (int *)(buf_ + L_.part);
+    if (!part) part = (int *)(buf_ + L_.part);
     const dim3 grid((unsigned)std::min(ntile, kGridMax));
     if (ntile > 1) {
         hipLaunchKernelGGL(dev::k_scan_reduce, grid, dim3(kBlk), 0, st_, n, data, part, ntile);
@@ -969,15 +1108,31 @@ void PlanDevice::scan(int *data, int64_t n) {
 }
 
 // out: the items 0 .. n - 1 sorted by (key, item); off [nkeys + 1]: the keys' offsets
-void PlanDevice::sort_by_row(int64_t n, const int *key, int32_t nkeys, int *off, int *out, int *hdr) {
+void PlanDevice::sort_by_row(int64_t n, const int *key, int32_t nkeys, int *off, int *out, int *hdr, int *cur, int *part) {
     hipMemsetAsync(off, 0, sizeof(int) * ((size_t)nkeys + 1), st_);
     if (n <= 0) return;
-    int *cur = (int *)(buf_ + L_.cur);
+    if (!cur) cur = (int *)(buf_ + L_.cur);
     hipMemsetAsync(cur, 0, sizeof(int) * (size_t)nkeys, st_);
     LAUNCH(k_count, n, n, key, off);
-    scan(off, (int64_t)nkeys + 1);
+    scan(off, (int64_t)nkeys + 1, part);
     LAUNCH(k_place, n, n, key, (const int *)off, cur, out);
     LAUNCH(k_run_sort, nkeys, nkeys, (const int *)off, out, hdr);
+}
+
+// the stable LSD radix sort of the *np keys in key[0] / id[0] (ntile tiles of kPlanRadixTile hold them); returns the
+// buffer that holds the result
+int PlanDevice::radix_sort(uint64_t *const key[2], int *const id[2], int *hist, int *part, const int *np, int ntile, int passes) {
+    const dim3 rgrid((unsigned)std::min(ntile, kGridMax));
+    int cur = 0;
+    for (int pass = 0; pass < passes; pass++) {
+        const int sh = kPlanRadixBits * pass;
+        hipLaunchKernelGGL(dev::k_radix_hist, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)key[cur], sh, hist, ntile);
+        scan(hist, (int64_t)kRadixDigits * ntile, part);
+        hipLaunchKernelGGL(dev::k_radix_scatter, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)key[cur], (const int *)id[cur], sh,
+                           (const int *)hist, ntile, key[cur ^ 1], id[cur ^ 1]);
+        cur ^= 1;
+    }
+    return cur;
 }
 
 void PlanDevice::report(int first, int last, const char *const *names) const {
@@ -991,8 +1146,9 @@ void PlanDevice::report(int first, int last, const char *const *names) const {
 
 int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
                      std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-                     std::string &err, bool with_tiles, bool with_layout, bool multi) {
+                     std::string &err, bool with_tiles, bool with_layout, bool multi, bool multi_tiles) {
     hipSetDevice(dev_);
+    multi_tiles = multi_tiles && multi;
     if (multi && (with_tiles || d.n_cams >= (1 << 21))) {
         err = "plan builder: rows() of several pairs with the tile stages, or with 2^21 cameras";
         return -1;
@@ -1000,6 +1156,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     with_tiles_ = with_tiles;
     with_layout_ = with_layout;
     multi_ = multi;
+    multi_tiles_ = multi_tiles;
     order_on_dev_ = false;
     nloc_ = -1;
     const int32_t P = d.n_points, NR = std::max(d.n_rot, 1);
@@ -1061,6 +1218,11 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
             L.pxy = piece(d.order_xy ? 24 * Pz : 0); L.rcam = piece(4 * (size_t)R); L.rfirst = piece(4 * Pz); L.pcam = piece(4 * Pz);
             L.cbox = piece(32 * ((size_t)std::max(d.n_cams, 1) + 1));
         }
+        L.mpair = L.mdscale = o;
+        if (multi_tiles) {
+            L.mpair = piece(4 * Ez);
+            L.mdscale = with_layout ? L.dscale : piece(4 * (size_t)D);
+        }
         L.total = o;
     }
     const Layout &L = L_;
@@ -1091,6 +1253,8 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     if (with_layout && D > 0) hipMemcpyAsync(B + L.dscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     if (multi && R > 0) hipMemcpyAsync(B + L.rcam, d.rep_cam, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
     if (multi && d.order_xy) hipMemcpyAsync(B + L.pxy, d.points, 24 * Pz, hipMemcpyHostToDevice, st_);
+    if (multi_tiles) hipMemcpyAsync(B + L.mpair, d.arap_pair, 4 * Ez, hipMemcpyHostToDevice, st_);
+    if (multi_tiles && !with_layout && D > 0) hipMemcpyAsync(B + L.mdscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     hipEventRecord(ev_[1], st_);
     // 1. groups
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
@@ -1106,21 +1270,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
                        d_mm);
     hipLaunchKernelGGL(dev::k_minmax_final, dim3(1), dim3(kBlk), 0, st_, mm_grid, (const double *)d_mm, d_lohi);
     LAUNCH(k_keys, P, d_ng, (const int *)d_grep, (const double *)d_xy, stride, (const double *)d_lohi, d_key[0], d_id[0]);
-    // the stable LSD radix sort of the *np keys in d_key[0] / d_id[0]; returns the buffer that holds the result
-    const dim3 rgrid((unsigned)std::min(rtile, kGridMax));
-    auto radix_sort = [&](const int *np, int passes) {
-        int cur = 0;
-        for (int pass = 0; pass < passes; pass++) {
-            const int sh = kPlanRadixBits * pass;
-            hipLaunchKernelGGL(dev::k_radix_hist, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)d_key[cur], sh, d_hist, rtile);
-            scan(d_hist, (int64_t)kRadixDigits * rtile);
-            hipLaunchKernelGGL(dev::k_radix_scatter, rgrid, dim3(kBlk), 0, st_, np, (const uint64_t *)d_key[cur],
-                               (const int *)d_id[cur], sh, (const int *)d_hist, rtile, d_key[cur ^ 1], d_id[cur ^ 1]);
-            cur ^= 1;
-        }
-        return cur;
-    };
-    int cur = radix_sort(d_ng, kRadixPasses);
+    int cur = radix_sort(d_key, d_id, d_hist, nullptr, d_ng, rtile, kRadixPasses);
     LAUNCH(k_gpos, P, d_ng, (const int *)d_id[cur], d_gpos);
     hipEventRecord(ev_[3], st_);
     // 3. rows: the points by (gpos[gid[p]], p)
@@ -1143,13 +1293,13 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         LAUNCH(k_box_init, 4 * (C + 1), 4 * (C + 1), d_box);
         LAUNCH(k_cam_box, P, P, C, (const int *)d_rfirst, (const int *)d_rcam, d_pts, 3, d_pcam, d_box);
         LAUNCH(k_cam_keys, P, P, (const int *)d_pcam, d_pts, 3, (const unsigned long long *)d_box, d_key[0], d_id[0]);
-        cur = radix_sort(d_hdr + kHdrP, kRadixPasses + (cbits + kPlanRadixBits - 1) / kPlanRadixBits);
+        cur = radix_sort(d_key, d_id, d_hist, nullptr, d_hdr + kHdrP, rtile, kRadixPasses + (cbits + kPlanRadixBits - 1) / kPlanRadixBits);
         LAUNCH(k_rows_pick, P, P, (const int *)d_hdr, (const int *)d_id[cur], d_por);
     }
     LAUNCH(k_inverse, P, (int64_t)P, (const int *)d_por, d_rop);
     hipEventRecord(ev_[4], st_);
     // (gp is the region's last piece: the tile stages read it on the device, so it stays there)
-    hipMemcpyAsync(pin_, B + L.dl1, (with_tiles ? L.gp : L.dl1_end) - L.dl1, hipMemcpyDeviceToHost, st_);
+    hipMemcpyAsync(pin_, B + L.dl1, (with_tiles || multi_tiles ? L.gp : L.dl1_end) - L.dl1, hipMemcpyDeviceToHost, st_);
     hipEventRecord(ev_[5], st_);
     hipError_t e = hipStreamSynchronize(st_);
     if (e == hipSuccess) e = hipGetLastError();
@@ -1171,7 +1321,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
                   *gpp = (const int32_t *)(pin_ + (L.gp - L.dl1));
     point_of_row.assign(por, por + P);
     row_of_point.assign(rop, rop + P);
-    if (with_tiles) gp.clear();
+    if (with_tiles || multi_tiles) gp.clear();
     else gp.assign(gpp, gpp + P);
     return 0;
 }
@@ -1199,7 +1349,7 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
 
     nloc_ = -1;
     hipEventRecord(ev_[6], st_);
-    if (order_on_dev_ && nloc == E) hipMemcpyAsync(d_aid, B + L.oe, 4 * (size_t)nloc, hipMemcpyDeviceToDevice, st_);
+    if (order_on_dev_ && nloc == E) hipMemcpyAsync(d_aid, order_dev_, 4 * (size_t)nloc, hipMemcpyDeviceToDevice, st_);
     else hipMemcpyAsync(d_aid, H.arap_ids.data(), 4 * (size_t)nloc, hipMemcpyHostToDevice, st_);
     hipEventRecord(ev_[7], st_);
     // 4. rotation rows numbered in first-encounter order over the positions 2 le + k
@@ -1295,7 +1445,8 @@ int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, i
     hipEventRecord(ev_[13], st_);
     // b. partition: the cut from every start, the chain from group 0 marked by pointer doubling and compacted
     LAUNCH(k_tile_end, nodes, ng, d_start, (const int *)d_ooff, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
-           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr);
+           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr,
+           (const int *)nullptr);
     hipMemsetAsync(d_mark, 0, 4 * ((size_t)ng + 2), st_);
     LAUNCH(k_fill, 1, (int64_t)1, d_mark, 1);
     {
@@ -1388,7 +1539,7 @@ int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, i
     hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)d_tstart, d_start, d_gp,
                        d_por, (const int *)d_ooff, (const int *)d_oe, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
                        (const int *)d_ie, (const int *)d_egi, (const int4 *)d_erow, (const int *)d_tne, (const int *)d_tnh,
-                       (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr);
+                       (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr, (const int *)nullptr, (const int *)nullptr);
     hipEventRecord(ev_[18], st_);
     // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
     sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3);
@@ -1429,6 +1580,272 @@ int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, i
     H.tile_lds = hdr[kHdrLds];
     H.tile_halo_rows = nhr;
     order_on_dev_ = true;
+    order_dev_ = d_oe;
+    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
+    return 0;
+}
+
+int PlanDevice::tiles_multi(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
+                            SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp, std::string &err) {
+    hipSetDevice(dev_);
+    const Layout &L = L_;
+    const int32_t P = P_, Q = d.n_pairs;
+    const int64_t E = E_, D = d.n_depth;
+    if (!buf_ || !multi_tiles_ || P != d.n_points || E != d.n_arap || ng < 1 || ng > P || Q < 2 || E < 1) {
+        err = "plan builder: tiles_multi() without the rows of this problem";
+        return -1;
+    }
+    char *B = buf_;
+    const int *d_ap = (const int *)(B + L.ap), *d_gp = (const int *)(B + L.gp), *d_rop = (const int *)(B + L.rop),
+              *d_pair = (const int *)(B + L.mpair), *d_dscale = (const int *)(B + L.mdscale), *d_dep_point = (const int *)(B + L.dep_point);
+    const double *d_pts = d.order_xy ? (const double *)(B + L.pxy) : (const double *)(B + L.xy);
+    hipError_t e = hipSuccess;
+    // build_tiles_multi refuses this graph, or a count leaves the int range: it runs on the host from these rows, and needs gp
+    auto to_host = [&]() {
+        hipMemcpyAsync(pin_, d_gp, 4 * (size_t)P, hipMemcpyDeviceToHost, st_);
+        e = hipStreamSynchronize(st_);
+        if (e != hipSuccess) {
+            err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
+            return -1;
+        }
+        gp.assign((const int32_t *)pin_, (const int32_t *)pin_ + P);
+        return 2;
+    };
+    // the int ranges: a unit's flat index q ng + g, a unit id shifted by 2 bits, the padded entries <= 2 E + 64 tiles
+    const int64_t nU64 = (int64_t)Q * ng, nmax64 = std::min<int64_t>(nU64, 2 * E);
+    if (d.n_scales != 2 * Q || nU64 >= (1LL << 28) || 2 * E + 64 * nmax64 >= (1LL << 31)) return to_host();
+    const int nU = (int)nU64, nmax = (int)nmax64;             // nmax: the units at most (every edge end flags one)
+    const size_t Ez = (size_t)E, Uz = (size_t)nU, Nz = (size_t)nmax, Pz = (size_t)P;
+    const int rtile = (int)((Nz + kPlanRadixTile - 1) / kPlanRadixTile);
+    const int64_t scan_max = std::max<int64_t>({(int64_t)nU + 1, (int64_t)kRadixDigits * rtile, (int64_t)P + 1});
+    size_t o = 0;
+    auto piece = [&](size_t bytes) { const size_t at = o; o += pad(bytes); return at; };
+    const size_t o_hdr = piece(4 * kHdrWords), o_uflag = piece(4 * Uz), o_uidx = piece(4 * (Uz + 1)), o_upt = piece(4 * Uz),
+                 o_upt2 = piece(4 * Uz), o_uid = piece(4 * Uz), o_box = piece(32 * (size_t)Q), o_key0 = piece(8 * Nz), o_key1 = piece(8 * Nz),
+                 o_id0 = piece(4 * Nz), o_id1 = piece(4 * Nz), o_hist = piece(4 * (size_t)kRadixDigits * rtile),
+                 o_part = piece(4 * (size_t)((scan_max + kPlanScanTile - 1) / kPlanScanTile + 1)), o_cur = piece(4 * (std::max(Nz, Pz) + 1)),
+                 o_urow = piece(8 * Nz), o_upair = piece(4 * (Nz + 1)), o_ustart = piece(4 * (Nz + 2)), o_egi = piece(4 * Ez),
+                 o_egj = piece(4 * Ez), o_erow = piece(16 * Ez), o_ooff = piece(4 * (Nz + 1)), o_oe = piece(4 * Ez), o_okj = piece(4 * Ez),
+                 o_pred = piece(4 * Ez), o_ioff = piece(4 * (Nz + 1)), o_ie = piece(4 * Ez), o_tend = piece(4 * (Nz + 1)),
+                 o_ja = piece(4 * (Nz + 1)), o_jb = piece(4 * (Nz + 1)), o_mark = piece(4 * (Nz + 2)), o_midx = piece(4 * (Nz + 2)),
+                 o_tstart = piece(4 * (Nz + 2)), o_tne = piece(4 * (Nz + 2)), o_tnh = piece(4 * (Nz + 2)), o_tcut = piece(4 * (Nz + 2)),
+                 o_soff = piece(4 * (Pz + 1)), o_sk = piece(8 * Nz), o_spos = piece(8 * Nz);
+    if (o > mcap_) {
+        if (before_alloc && *before_alloc) {
+            (*before_alloc)();
+            *before_alloc = nullptr;
+        }
+        if (mbuf_) hipFree(mbuf_);
+        mbuf_ = nullptr; mcap_ = 0;
+        const size_t want = o + o / 4;
+        if (hipMalloc((void **)&mbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
+        mcap_ = want;
+    }
+    if (g_timing) std::fprintf(stderr, "[deftri plan] arena of the units %.1f MiB of %.1f\n", o / 1048576.0, mcap_ / 1048576.0);
+    char *M = mbuf_;
+    auto ip = [&](size_t off) { return (int *)(M + off); };
+    int *d_hdr = ip(o_hdr), *d_uflag = ip(o_uflag), *d_uidx = ip(o_uidx), *d_upt = ip(o_upt), *d_upt2 = ip(o_upt2), *d_uid = ip(o_uid),
+        *d_hist = ip(o_hist), *d_part = ip(o_part), *d_cur = ip(o_cur), *d_urow = ip(o_urow), *d_upair = ip(o_upair),
+        *d_ustart = ip(o_ustart), *d_egi = ip(o_egi), *d_egj = ip(o_egj), *d_erow = ip(o_erow), *d_ooff = ip(o_ooff), *d_oe = ip(o_oe),
+        *d_okj = ip(o_okj), *d_pred = ip(o_pred), *d_ioff = ip(o_ioff), *d_ie = ip(o_ie), *d_tend = ip(o_tend), *d_ja = ip(o_ja),
+        *d_jb = ip(o_jb), *d_mark = ip(o_mark), *d_midx = ip(o_midx), *d_tstart = ip(o_tstart), *d_tne = ip(o_tne), *d_tnh = ip(o_tnh),
+        *d_tcut = ip(o_tcut), *d_soff = ip(o_soff), *d_sk = ip(o_sk), *d_spos = ip(o_spos);
+    unsigned long long *d_box = (unsigned long long *)(M + o_box);
+    uint64_t *d_key[2] = {(uint64_t *)(M + o_key0), (uint64_t *)(M + o_key1)};
+    int *d_id[2] = {ip(o_id0), ip(o_id1)};
+
+    hipEventRecord(ev_[28], st_);
+    // a. the units: flags and points, the pairs' boxes, the keys, the sort by (q, key, g) from ascending (q, g)
+    hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
+    hipMemsetAsync(d_uflag, 0, 4 * Uz, st_);
+    LAUNCH(k_fill, nU, (int64_t)nU, d_upt, INT_MAX);
+    LAUNCH(k_fill, nU, (int64_t)nU, d_upt2, INT_MAX);
+    LAUNCH(k_fill, nU, (int64_t)nU, d_uid, -1);
+    LAUNCH(k_mu_flag, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, d_uflag, d_upt, d_upt2, d_hdr);
+    hipMemcpyAsync(d_uidx, d_uflag, 4 * Uz, hipMemcpyDeviceToDevice, st_);
+    hipMemsetAsync(d_uidx + nU, 0, 4, st_);
+    scan(d_uidx, (int64_t)nU + 1, d_part);
+    LAUNCH(k_box_init, 4 * Q, 4 * Q, d_box);
+    LAUNCH(k_mu_box, nU, nU, ng, (const int *)d_uflag, (const int *)d_upt, d_pts, d_box);
+    LAUNCH(k_mu_keys, nU, nU, ng, (const int *)d_uflag, (const int *)d_uidx, (const int *)d_upt, d_pts, (const unsigned long long *)d_box,
+           d_key[0], d_id[0], d_hdr);
+    int qbits = 0;
+    while (Q >> qbits) qbits++;
+    const int cur = radix_sort(d_key, d_id, d_hist, d_part, d_hdr + kHdrNu, rtile, kRadixPasses + (qbits + kPlanRadixBits - 1) / kPlanRadixBits);
+    LAUNCH(k_mu_units, (int64_t)nmax + 2, nmax, ng, (const int *)d_id[cur], (const int *)d_upt, (const int *)d_upt2, d_rop, d_uid, d_urow,
+           d_upair, d_ustart, (const int *)d_hdr);
+    hipEventRecord(ev_[29], st_);
+    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[30], st_);
+    e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names0[] = {"dev 4a units", "dev download unit count"};
+    report(28, 30, names0);
+    int hdr[kHdrWords];
+    std::memcpy(hdr, pin_, sizeof(hdr));
+    if (hdr[kHdrRefuse]) return to_host();
+    const int32_t nu = hdr[kHdrNu];
+    if (nu < 2 || nu > nmax) {
+        err = "plan builder: the device wrote an impossible unit count";
+        return -1;
+    }
+    const int64_t nodes = (int64_t)nu + 1, n2 = 2 * (int64_t)nu;
+    const dim3 tgrid((unsigned)std::min(nu, kGridMax));
+
+    hipEventRecord(ev_[31], st_);
+    // the edges by unit: the out-edges by (ui, e), the in-edges by (uj, e); the depth edges' and the rows' checks; the
+    // tile row list's entries by (row, entry) for the shares
+    LAUNCH(k_mu_edges, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, (const int *)d_uid, (const int *)d_upt, (const int *)d_upt2, d_egi,
+           d_egj, (int4 *)d_erow, d_hdr);
+    sort_by_row(E, d_egi, nu, d_ooff, d_oe, d_hdr, d_cur, d_part);
+    LAUNCH(k_tile_deg, nu, nu, (const int *)d_ooff, d_hdr);
+    sort_by_row(E, d_egj, nu, d_ioff, d_ie, d_hdr, d_cur, d_part);
+    LAUNCH(k_tile_pred, E, E, (const int *)d_oe, (const int *)d_egi, (const int *)d_egj, (const int *)d_ioff, (const int *)d_ie, d_okj,
+           d_pred, (const int *)d_hdr);
+    LAUNCH(k_mu_depth, D, D, d_dep_point, d_dscale, d_gp, d_rop, Q, ng, (const int *)d_uid, (const int *)d_urow, d_hdr);
+    sort_by_row(n2, d_urow, P, d_soff, d_sk, d_hdr, d_cur, d_part);
+    LAUNCH(k_inverse, n2, n2, (const int *)d_sk, d_spos);
+    LAUNCH(k_mu_rows, P, P, (const int *)d_soff, d_hdr);
+    hipEventRecord(ev_[32], st_);
+    // b. partition: the cut from every start (a tile ends with its pair), the chain from unit 0 marked and compacted
+    LAUNCH(k_tile_end, nodes, nu, (const int *)d_ustart, (const int *)d_ooff, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
+           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr,
+           (const int *)d_upair);
+    hipMemsetAsync(d_mark, 0, 4 * ((size_t)nu + 2), st_);
+    LAUNCH(k_fill, 1, (int64_t)1, d_mark, 1);
+    {
+        int rounds = 1;
+        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
+        const int *jin = d_tend;
+        int *jout = d_ja;
+        for (int r = 0; r < rounds; r++) {
+            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, d_mark, (const int *)d_hdr);
+            jin = jout;
+            jout = jout == d_ja ? d_jb : d_ja;
+        }
+    }
+    LAUNCH(k_tile_midx, nodes, nu, (const int *)d_mark, d_midx);
+    scan(d_midx, nodes, d_part);
+    LAUNCH(k_tile_tstart, nodes, nu, (const int *)d_mark, (const int *)d_midx, d_tstart, d_hdr);
+    hipEventRecord(ev_[33], st_);
+    // c (counts). per tile its padded entries, halo rows and cut entries; their scans are the tiles' bases
+    hipMemsetAsync(d_tne, 0, 4 * ((size_t)nu + 1), st_);
+    hipMemsetAsync(d_tnh, 0, 4 * ((size_t)nu + 1), st_);
+    hipMemsetAsync(d_tcut, 0, 4 * ((size_t)nu + 1), st_);
+    hipLaunchKernelGGL(dev::k_tile_count, tgrid, dim3(kBlk), 0, st_, (const int *)d_tstart, (const int *)d_ustart, (const int *)d_ooff,
+                       (const int *)d_okj, (const int *)d_pred, (int)kSpTileLdsFixed, d_tne, d_tnh, d_tcut, d_hdr);
+    scan(d_tne, nodes, d_part);
+    scan(d_tnh, nodes, d_part);
+    scan(d_tcut, nodes, d_part);
+    hipLaunchKernelGGL(dev::k_tile_totals, dim3(1), dim3(64), 0, st_, nu, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut, d_hdr);
+    hipEventRecord(ev_[34], st_);
+    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[35], st_);
+    e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names1[] = {"dev 4a edges by unit, shares", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
+    report(31, 35, names1);
+    std::memcpy(hdr, pin_, sizeof(hdr));
+    if (hdr[kHdrRefuse]) return to_host();
+    if (hdr[kHdrBound]) return 1;
+    const int32_t nt = hdr[kHdrNt], planes = hdr[kHdrPlanes];
+    const int64_t ne = hdr[kHdrEntries], nhr = hdr[kHdrHalo], nx = 2 * (int64_t)hdr[kHdrCut];
+    if (nt < 1 || nt > nu || ne < 64 * (int64_t)nt || ne % 64 || ne > 2 * E + 64 * (int64_t)nt || nhr < 0 || nhr > 2 * E || nx < 0 ||
+        nx > 2 * E || planes < 0 || planes >= Q) {
+        err = "plan builder: the device wrote impossible tile counts";
+        return -1;
+    }
+    // the tile arrays: one download region (header, tile arrays, the edge order), then the cross slots' scratch
+    o = 0;
+    const size_t t_hdr = piece(4 * kHdrWords), t_tab = piece(32 * (size_t)nt), t_m0 = piece(4 * (size_t)ne), t_m1 = piece(4 * (size_t)ne),
+                 t_chunk = piece(8 * (size_t)(ne / 64)), t_rs = piece(4 * (size_t)n2), t_halo = piece(4 * (size_t)nhr),
+                 t_xoff = piece(4 * (Pz + 1)), t_xdst = piece(4 * (size_t)nx), t_order = piece(4 * Ez), t_trow = piece(4 * (size_t)n2),
+                 t_tdst = piece(4 * (size_t)n2), t_poff = piece(4 * ((size_t)Q + 1)), t_nshare = piece(4 * Pz);
+    const size_t dl = o;
+    const size_t t_xrow = piece(4 * (size_t)nx), t_xs = piece(4 * (size_t)nx);
+    if ((o > tcap_ || dl > pin_cap_) && before_alloc && *before_alloc) {
+        (*before_alloc)();
+        *before_alloc = nullptr;
+    }
+    if (o > tcap_) {
+        if (tbuf_) hipFree(tbuf_);
+        tbuf_ = nullptr; tcap_ = 0;
+        const size_t want = o + o / 4;
+        if (hipMalloc((void **)&tbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
+        tcap_ = want;
+    }
+    if (!reserve(cap_, dl, nullptr)) { err = "plan builder: allocation failed"; return -1; }
+    char *T = tbuf_;
+    int *d_hdr3 = (int *)(T + t_hdr), *d_xoff = (int *)(T + t_xoff), *d_xdst = (int *)(T + t_xdst), *d_xs = (int *)(T + t_xs);
+    dev::TileOut out;
+    out.tab = (int *)(T + t_tab); out.chunk = (int *)(T + t_chunk); out.rs = (int *)(T + t_rs); out.halo = (int *)(T + t_halo);
+    out.xrow = (int *)(T + t_xrow); out.m0 = (uint32_t *)(T + t_m0); out.m1 = (uint32_t *)(T + t_m1);
+    hipEventRecord(ev_[36], st_);
+    // c. entries, slots and own rows, one workgroup per tile; the shares from the sort by (row, entry)
+    hipMemsetAsync(d_hdr3, 0, 4 * kHdrWords, st_);
+    hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)d_tstart,
+                       (const int *)d_ustart, (const int *)nullptr, (const int *)nullptr, (const int *)d_ooff, (const int *)d_oe,
+                       (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff, (const int *)d_ie, (const int *)d_egi,
+                       (const int4 *)d_erow, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr,
+                       (const int *)d_urow, (const int *)d_upair);
+    LAUNCH(k_mu_shares, n2, n2, (const int *)d_urow, (const int *)d_soff, (const int *)d_spos, (int *)(T + t_trow), (int *)(T + t_tdst));
+    LAUNCH(k_mu_nshare, P, P, (const int *)d_soff, (int *)(T + t_nshare));
+    LAUNCH(k_mu_poff, (int64_t)Q + 1, Q, ng, (const int *)d_uidx, (const int *)d_midx, (int *)(T + t_poff));
+    hipEventRecord(ev_[37], st_);
+    // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
+    sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3, d_cur, d_part);
+    LAUNCH(k_inverse, nx, nx, (const int *)d_xs, d_xdst);
+    hipMemcpyAsync(T + t_order, d_oe, 4 * Ez, hipMemcpyDeviceToDevice, st_);
+    hipEventRecord(ev_[38], st_);
+    hipMemcpyAsync(pin_, T, dl, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[39], st_);
+    e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) {
+        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
+        return -1;
+    }
+    static const char *const names2[] = {"dev 4a entries, slots, shares", "dev 4a cross slots", "dev download tiles"};
+    report(36, 39, names2);
+    const int *hdr3 = (const int *)(pin_ + t_hdr);
+    if (hdr3[kHdrBound] || hdr3[kHdrRefuse]) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto take = [&](auto &v, size_t off, size_t n) {
+        using V = typename std::remove_reference<decltype(v)>::type::value_type;
+        const V *p = (const V *)(pin_ + off);
+        v.assign(p, p + n);
+    };
+    take(H.tile_tab, t_tab, 8 * (size_t)nt);
+    take(H.tile_m0, t_m0, (size_t)ne);
+    take(H.tile_m1, t_m1, (size_t)ne);
+    take(H.tile_chunk, t_chunk, 2 * (size_t)(ne / 64));
+    take(H.tile_rs, t_rs, (size_t)n2);
+    take(H.tile_halo, t_halo, (size_t)nhr);
+    take(H.tile_xoff, t_xoff, Pz + 1);
+    take(H.tile_xdst, t_xdst, (size_t)nx);
+    take(order, t_order, Ez);
+    take(H.tile_trow, t_trow, (size_t)n2);
+    take(H.tile_tdst, t_tdst, (size_t)n2);
+    take(H.tile_poff, t_poff, (size_t)Q + 1);
+    take(H.tile_nshare, t_nshare, Pz);
+    H.tile_planes = planes;
+    H.tile_multi = true;
+    H.ntile = nt;
+    H.tile_entries = ne;
+    H.tile_cross = nx;
+    H.tile_segmax = std::max(1, hdr[kHdrSegmax]);
+    H.tile_lds = hdr[kHdrLds];
+    H.tile_halo_rows = nhr;
+    order_on_dev_ = true;
+    order_dev_ = d_oe;
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
     return 0;
 }

@@ -130,6 +130,7 @@ struct deftri_ctx {
     int tile_builder = 0;                   // deftri_set_tile_builder
     int layout_builder = 0;                 // deftri_set_layout_builder
     int multi_pair_builder = 0;             // deftri_set_multi_pair_builder
+    int multi_tile_builder = 0;             // deftri_set_multi_tile_builder
     PlanBuildInfo plan_build;               // deftri_plan_build_info: the last iterative plan build
     MeshSource mesh_src;                    // mesh_builder 1: delaunay_stars on this context
     std::unique_ptr<GraphBuilderDevice> gbdev;   // the graph builder's device arena and pinned staging (graph_build_dev.hip)
@@ -1254,6 +1255,13 @@ int deftri_set_multi_pair_builder(deftri_ctx *ctx, int32_t mode) {
     return 0;
 }
 
+int deftri_set_multi_tile_builder(deftri_ctx *ctx, int32_t mode) {
+    if (!ctx) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_multi_tile_builder: mode is 0 (build_tiles_multi on the host) or 1 (device stages)");
+    ctx->multi_tile_builder = mode;
+    return 0;
+}
+
 int deftri_set_graph_builder(deftri_ctx *ctx, int32_t mode) {
     if (!ctx) return DEFTRI_E_ARG;
     if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "set_graph_builder: mode is 0 (the graph build's passes on the host) or 1 (device stages)");
@@ -1287,7 +1295,7 @@ static int debug_build_plan(deftri_ctx *ctx, const deftri_problem_desc *desc, in
     std::string err;
     rc = build_sp_plan_with(*desc, ctx->rank, ctx->nranks, ctx->jac_fp32 != 0, H, err, tile != 0, mode,
                             mode ? plan_device(ctx) : nullptr, nullptr, ctx->plan_build, ctx->tile_builder, ctx->layout_builder,
-                            false, ctx->multi_pair_builder);
+                            false, ctx->multi_pair_builder, ctx->multi_tile_builder);
     return rc ? fail(ctx, rc, err) : 0;
 }
 
@@ -1305,6 +1313,23 @@ int deftri_debug_plan_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, i
     std::copy(each.begin(), each.end(), digests);
     digests[kPlanDigestCount] = all;
     *n = kPlanDigestCount + 1;
+    return 0;
+}
+
+int deftri_debug_plan_tile_digest(deftri_ctx *ctx, const deftri_problem_desc *desc, int32_t mode, int32_t tile, uint64_t *digests,
+                                  int32_t cap, int32_t *n) {
+    if (!ctx || !desc || !digests || !n) return DEFTRI_E_ARG;
+    if (mode != 0 && mode != 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_tile_digest: mode is 0 or 1");
+    if (cap < kPlanTileDigestCount + 1) return fail(ctx, DEFTRI_E_ARG, "debug_plan_tile_digest: room for " + std::to_string(kPlanTileDigestCount + 1) + " digests needed");
+    SpPlanHost H;
+    int rc = debug_build_plan(ctx, desc, mode, tile, H);
+    if (rc) return rc;
+    std::vector<uint64_t> each;
+    const uint64_t all = plan_tile_digests(H, &each);
+    if ((int)each.size() != kPlanTileDigestCount) return fail(ctx, DEFTRI_E_INTERNAL, "debug_plan_tile_digest: digest count");
+    std::copy(each.begin(), each.end(), digests);
+    digests[kPlanTileDigestCount] = all;
+    *n = kPlanTileDigestCount + 1;
     return 0;
 }
 
@@ -1703,6 +1728,7 @@ int deftri_problem_upload(deftri_ctx *ctx, const deftri_problem_desc *desc) {
         ctx->sp->tile_builder = ctx->tile_builder;
         ctx->sp->layout_builder = ctx->layout_builder;
         ctx->sp->multi_pair_builder = ctx->multi_pair_builder;
+        ctx->sp->multi_tile_builder = ctx->multi_tile_builder;
         ctx->sp->plan_dev = ctx->plan_builder ? plan_device(ctx) : nullptr;
         ctx->sp->plan_build = &ctx->plan_build;
         rc = ctx->sp->upload(*desc);

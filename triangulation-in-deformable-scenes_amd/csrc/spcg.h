@@ -210,15 +210,24 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // leaves pmap and pidx on the device (out.pmap_dev, out.pidx_dev) — unless DEFTRI_PLAN_DIGEST asks for the digest.
 // multi_mode (deftri_set_multi_pair_builder) 1: mode 1 applies to several pairs on one rank as well (any number of
 // scales, fewer than 2^21 cameras): stages 1-3 with the keyframe-major rows, 5, 6 and 8 on `pd`, build_tiles_multi
-// on the host whatever tile_mode says, and with layout_mode 1 stage 8b (stages bits 11 and 12; stage 7 on the host)
+// on the host whatever tile_mode says, and with layout_mode 1 stage 8b (stages bits 11 and 12; stage 7 on the host).
+// multi_tile_mode (deftri_set_multi_tile_builder) 1: where multi_mode 1 applies, build_tiles_multi on `pd` as well
+// (PlanDevice::tiles_multi; stages bits 6-9)
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false, int multi_mode = 0);
+                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false, int multi_mode = 0,
+                       int multi_tile_mode = 0);
 // FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
 // not null one digest per array in that block's order (names: kPlanDigestNames)
 uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
 extern const char *const kPlanDigestNames[];
 extern const int kPlanDigestCount;
+// the same over what only a tile plan of several pairs holds and plan_digests leaves out: tile_trow, tile_tdst,
+// tile_poff, tile_nshare, then the tile scalars {ntile, tile_entries, tile_cross, tile_segmax, tile_lds,
+// tile_halo_rows, tile_planes, tile_multi} as int64 (names: kPlanTileDigestNames)
+uint64_t plan_tile_digests(const SpPlanHost &H, std::vector<uint64_t> *each);
+extern const char *const kPlanTileDigestNames[];
+extern const int kPlanTileDigestCount;
 // host emulation of one sharded product on the plan (tests; spcg_plan.cpp)
 int sp_emulate_product(const deftri_problem_desc &d, const SpPlanHost &H, const double *Ja, const double *Wa,
                        const double *Jr, const double *Wr, const double *Jd, const double *Wd, double lambda,
@@ -390,6 +399,7 @@ class SpSolver {
     int plan_builder = 0, tile_builder = 0;          // (tile_builder: deftri_set_tile_builder)
     int layout_builder = 0;                          // deftri_set_layout_builder
     int multi_pair_builder = 0;                      // deftri_set_multi_pair_builder
+    int multi_tile_builder = 0;                      // deftri_set_multi_tile_builder
     PlanDevice *plan_dev = nullptr;
     PlanBuildInfo *plan_build = nullptr;
     int refresh(const deftri_problem_desc &d);     // same structure: values only, plan kept

@@ -156,14 +156,38 @@ uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
     return h;
 }
 
+const char *const kPlanTileDigestNames[] = {"tile_trow", "tile_tdst", "tile_poff", "tile_nshare", "tile_scalars"};
+const int kPlanTileDigestCount = (int)(sizeof(kPlanTileDigestNames) / sizeof(kPlanTileDigestNames[0]));
+
+uint64_t plan_tile_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
+    constexpr uint64_t kBasis = 1469598103934665603ULL, kPrime = 1099511628211ULL;
+    uint64_t h = kBasis;
+    if (each) each->clear();
+    auto add = [&](const void *v, size_t n) {
+        const unsigned char *c = (const unsigned char *)v;
+        uint64_t a = kBasis;
+        for (size_t i = 0; i < n; i++) {
+            h ^= c[i]; h *= kPrime;
+            a ^= c[i]; a *= kPrime;
+        }
+        if (each) each->push_back(a);
+    };
+    for (const std::vector<int32_t> *x : {&H.tile_trow, &H.tile_tdst, &H.tile_poff, &H.tile_nshare}) add(x->data(), 4 * x->size());
+    const int64_t sc[8] = {H.ntile, H.tile_entries, H.tile_cross, H.tile_segmax, H.tile_lds, H.tile_halo_rows, H.tile_planes,
+                           H.tile_multi ? 1 : 0};
+    add(sc, sizeof(sc));
+    return h;
+}
+
 // pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
 // stages: the bit mask of the stages it ran.  layout_dev (deftri_set_layout_builder): 1 stages 7 and 8b on pd too
 // where it built the tile layout, 2 the same with pmap and pidx left on the device (H.pmap_dev, H.pidx_dev).
 // Several pairs (deftri_set_multi_pair_builder; the caller has checked one rank and the tile request): pd numbers the
-// rows keyframe-major, build_tiles_multi stays on the host, and layout_dev runs stage 8b alone
+// rows keyframe-major and layout_dev runs stage 8b alone; build_tiles_multi stays on the host unless
+// mtiles_dev (deftri_set_multi_tile_builder) asks pd for it first (PlanDevice::tiles_multi)
 static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                       bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false,
-                      int layout_dev = 0) {
+                      int layout_dev = 0, bool mtiles_dev = false) {
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     static const bool digest = std::getenv("DEFTRI_PLAN_DIGEST") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
@@ -192,8 +216,10 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         // (the tile stages' int counts: padded entries <= 2 E + 64 ng, and a group id shifted by 2 bits)
         tiles_dev = tiles_dev && tile && Q == 1 && S <= 2 && E > 0 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31) &&
                     sp_tile_lds_budget() < (1LL << 30);
+        // (several pairs: tiles_multi() checks its own int ranges once it knows the groups)
+        mtiles_dev = mtiles_dev && multi_dev && tile && E > 0 && sp_tile_lds_budget() < (1LL << 30);
         const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev,
-                                (tiles_dev || multi_dev) && layout_dev, multi_dev);
+                                (tiles_dev || multi_dev) && layout_dev, multi_dev, mtiles_dev);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         *stages |= 7;
         stage("1-3 on the device (wall)");
@@ -372,7 +398,18 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
         std::vector<int32_t> gp;
-        if (pd) gp.swap(gp_dev);
+        bool built = false;
+        if (pd && mtiles_dev) {
+            // build_tiles_multi on the device (plan_dev.hip); 2: a graph it refuses — the host's below then
+            // says why, from the device's rows and groups
+            const int rc = pd->tiles_multi(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err);
+            if (rc == 1 || rc < 0) return rc > 0 ? kPlanBound : kPlanHip;
+            built = rc == 0;
+            if (built) {
+                H.tile = true;
+                *stages |= 0x3c0;
+            }
+        } else if (pd) gp.swap(gp_dev);
         else {
             gp.resize(P);
             for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
@@ -382,7 +419,7 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         ti.Q = Q; ti.S = S; ti.pair = d.arap_pair; ti.D = D; ti.dep_point = d.dep_point; ti.dep_scale = d.dep_scale;
         ti.points = d.points;
         std::string why;
-        H.tile = build_tiles_multi(ti, H, tile_order, why);
+        if (!built) H.tile = build_tiles_multi(ti, H, tile_order, why);
         if (!H.tile) {
             H.tile_why = why;
             tile_order.clear();
@@ -809,7 +846,7 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode, int layout_mode, bool keep_slots, int multi_mode) {
+                       int tile_mode, int layout_mode, bool keep_slots, int multi_mode, int multi_tile_mode) {
     const auto t0 = std::chrono::steady_clock::now();
     info = PlanBuildInfo();
     auto done = [&](int rc) {
@@ -826,7 +863,7 @@ int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool 
     if (applies) {
         int32_t stages = 0;
         const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, tile_mode == 1,
-                                  layout_mode == 1 ? (keep_slots ? 2 : 1) : 0);
+                                  layout_mode == 1 ? (keep_slots ? 2 : 1) : 0, multi_pair && multi_tile_mode == 1);
         if (rc == kPlanOk) {
             info.builder_used = 1;
             info.stages = stages;

@@ -246,7 +246,8 @@ int SpSolver::upload(const deftri_problem_desc &d) {
     // they apply; its arena is the context's, so only its growth joins the old solver's release
     PlanBuildInfo pbi;
     const int plan_rc = build_sp_plan_with(d, rank_, nranks_, fp32_jac != 0, H, err, want_tile, plan_builder, plan_dev,
-                                           &before_alloc, pbi, tile_builder, layout_builder, true, multi_pair_builder);
+                                           &before_alloc, pbi, tile_builder, layout_builder, true, multi_pair_builder,
+                                           multi_tile_builder);
     if (plan_build) *plan_build = pbi;
     if (before_alloc) {
         before_alloc();

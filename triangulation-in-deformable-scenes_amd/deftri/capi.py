@@ -97,6 +97,8 @@ def load():
         "deftri_set_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_layout_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_multi_pair_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_set_multi_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_debug_plan_tile_digest": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_uint64), C.c_int32, P(C.c_int32)]),
         "deftri_debug_plan_layout_stats": (C.c_int, [C.c_void_p, P(_abi.ProblemDesc), C.c_int32, C.c_int32, P(C.c_int64), C.c_int32]),
         "deftri_plan_build_info": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), P(C.c_int32), P(C.c_double)]),
         "deftri_set_graph_builder": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -248,8 +250,11 @@ EXPORTED = [
     "deftri_delaunay2d", "deftri_set_mesh_builder", "deftri_debug_delaunay_still_valid", "deftri_debug_delaunay_sweep",
     "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
     "deftri_set_layout_builder", "deftri_debug_plan_layout_stats", "deftri_set_multi_pair_builder",
-    "deftri_set_graph_builder", "deftri_graph_build_info",
+    "deftri_set_graph_builder", "deftri_graph_build_info", "deftri_set_multi_tile_builder", "deftri_debug_plan_tile_digest",
 ]
+
+# the digests of deftri_debug_plan_tile_digest, in its order
+PLAN_TILE_DIGEST_NAMES = ("tile_trow", "tile_tdst", "tile_poff", "tile_nshare", "tile_scalars", "combined")
 
 # the figures of deftri_debug_plan_layout_stats, in its order
 PLAN_LAYOUT_STATS = ("waves", "split_waves", "two_window_waves", "zero_step_waves", "slot_steps", "blocks", "depth_blocks",
@@ -744,8 +749,16 @@ class Context:
         """Whether plan builder 1's device stages also take a problem of several keyframe pairs
         (deftri_set_multi_pair_builder): 0 no (default), 1 yes — one rank, the tile layout requested; plan_build_info
         stages 0x3f, with layout builder 1 0x183f (stage 8b; an upload then keeps pmap and pidx on the device).
-        build_tiles_multi and stage 7 stay on the host.  No effect with plan builder 0 or on one pair."""
+        build_tiles_multi (unless set_multi_tile_builder(1)) and stage 7 stay on the host.  No effect with plan builder 0
+        or on one pair."""
         self._check(self.lib.deftri_set_multi_pair_builder(self.h, int(mode)))
+
+    def set_multi_tile_builder(self, mode):
+        """Who cuts the tile layout of several pairs where set_multi_pair_builder(1)'s device stages apply
+        (deftri_set_multi_tile_builder): 0 the host's build_tiles_multi (default), 1 the device stages — plan_build_info
+        stages 0x3ff, with layout builder 1 0x1bff.  A graph build_tiles_multi refuses goes to the host after the
+        device's rows (0x7).  No effect on one pair or with plan or multi-pair builder 0."""
+        self._check(self.lib.deftri_set_multi_tile_builder(self.h, int(mode)))
 
     def plan_build_info(self):
         """What the last iterative plan build did (deftri_plan_build_info): builder_used, stages (bit mask),
@@ -764,6 +777,17 @@ class Context:
                                                       out.ctypes.data_as(C.POINTER(C.c_uint64)), len(out), C.byref(n)))
         assert n.value == len(PLAN_DIGEST_NAMES), n.value
         return PLAN_DIGEST_NAMES, [int(x) for x in out]
+
+    def debug_plan_tile_digest(self, prob, mode, tile):
+        """FNV-1a digests of the arrays and scalars only a multi-pair tile plan holds, of the plan debug_plan_digest
+        builds (deftri_debug_plan_tile_digest): (PLAN_TILE_DIGEST_NAMES, digests)."""
+        d = prob.to_desc()
+        out = np.zeros(len(PLAN_TILE_DIGEST_NAMES), np.uint64)
+        n = C.c_int32(0)
+        self._check(self.lib.deftri_debug_plan_tile_digest(self.h, C.byref(d), int(mode), int(tile),
+                                                           out.ctypes.data_as(C.POINTER(C.c_uint64)), len(out), C.byref(n)))
+        assert n.value == len(PLAN_TILE_DIGEST_NAMES), n.value
+        return PLAN_TILE_DIGEST_NAMES, [int(x) for x in out]
 
     def debug_plan_layout_stats(self, prob, mode, tile):
         """Figures of the phase-1 blocks and the wave layout of the plan debug_plan_digest builds

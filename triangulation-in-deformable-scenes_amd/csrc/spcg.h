@@ -47,8 +47,8 @@ constexpr int kSpSortWindow = 512;     // rows sorted by entry count inside wind
 constexpr int kSpWaveSplit = 16;       // phase-2 waves with rows of more slots take 32 rows on lane pairs
 constexpr int kSpRowSplit = 1;         // phase 2: waves per row-wave's slot list (DEFTRI_SP_ROW_SPLIT)
 constexpr int kSpP2Step = 8;           // phase 2: slots per step (DEFTRI_SP_P2_STEP = 4 or 8)
-constexpr int kSpGlinGroup = 8;        // k_sp_glin_blocks: owned ARAP blocks per workgroup at most
-constexpr int kSpGlinStep = 8;         // k_sp_glin_rows: slots per step (DEFTRI_SP_GLIN_STEP = 4 or 8)
+constexpr int kSpGlinGroup = 8;        // k_sp_glin's block part: owned ARAP blocks per workgroup at most
+constexpr int kSpGlinStep = 8;         // k_sp_glin's row part: slots per step (DEFTRI_SP_GLIN_STEP = 4 or 8)
 constexpr int kSpGuessMargin = 1;      // CG iterations queued per trial: last converged count + this
 constexpr int kSpHeavySplit = 512;         // heavy sums by one workgroup per heavy vertex above this many blocks
 constexpr int kSpUpdRows = 256;           // rows per k_sp_update workgroup (one thread per dof)
@@ -241,7 +241,7 @@ struct SpDev {
     int32_t nblk = 0, nrb = 0;                         // phase-1 blocks, row blocks
     int32_t include_heavy = 1;                         // this rank counts the replicated heavy dofs in sums
     const int4 *blk = nullptr;
-    const int2 *glb = nullptr;                            // k_sp_glin_blocks' groups: (first block, count)
+    const int2 *glb = nullptr;                            // k_sp_glin's block groups: (first block, count)
     int32_t nglb = 0;
     const int32_t *hv_blk = nullptr;
     const int64_t *hv_blk_off = nullptr;
@@ -259,7 +259,7 @@ struct SpDev {
     // row-waves, nrb2 = ceil(nwaves rs / 4) of them (p.q partials rpart [nrb2])
     int32_t rs = 1, nrb2 = 0;
     int32_t p2u = 8;                                   // phase 2's slots per step (8 or 4)
-    int32_t glu = 8;                                   // k_sp_glin_rows' slots per step (8 or 4)
+    int32_t glu = 8;                                   // k_sp_glin's row slots per step (8 or 4)
     int64_t nslots = 0;                                // wave-layout slots (x 64 lanes)
     const int32_t *rowmap = nullptr, *pmap = nullptr, *pidx = nullptr;
     const int64_t *woff = nullptr;

@@ -5,9 +5,10 @@
 // optimize() at :959-962) with block-Jacobi PCG on an operator that is never assembled.
 //
 // Per LM iteration (after the edges are linearized, kernels.hip k_lin_*):
-//   k_sp_glin_rows    own rows: the row's 3x3 diagonal block of H (incidences + folded single-point
+//   k_sp_glin         one launch, two kinds of workgroup:
+//     rows            own rows: the row's 3x3 diagonal block of H (incidences + folded single-point
 //                     edges), D_v (its reprojection / depth part), b_v, c_e = W J_p J_s per depth edge
-//   k_sp_glin_blocks  per phase-1 block: the heavy vertices' H / b partials (owned edges only)
+//     blocks          per phase-1 block: the heavy vertices' H / b partials (owned edges only)
 //   k_sp_glin_heavy   heavy H / b from the block partials (rank sums; all-reduced by the host)
 // Per CG iteration it (sharded: 6 launches, two all-reduces and the halo exchange of the boundary
 // rows' (z, p); one rank, merged chain (default): 2 launches — phase 1 also forms p.Ap and alpha,
@@ -117,10 +118,7 @@ __device__ __forceinline__ int tri6(int a, int b) { return a * (a + 1) / 2 + b; 
 // GU (G.glu): slots per step — 8 (3 waves per SIMD) or 4 (5 waves per SIMD: a C2-size grid of
 // ~3100 waves then fits the chip in one round)
 template <class JT, int GU>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GU == 4 ? 5 : GU == 6 ? 4 : 1, GU == 4 ? 5 : GU == 6 ? 4 : 3)))
-k_sp_glin_rows(const SpDev G, JT *__restrict__ pj) {
-    __shared__ double red4[4];
-    if (gated_off(G.lgate)) return;
+__device__ __forceinline__ void glin_rows(const SpDev &G, JT *__restrict__ pj, double *red4) {
     const int lb = row_block(blockIdx.x, G.nrb2);
     const int w = lb * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     double mx = 0.0;
@@ -286,10 +284,10 @@ k_sp_glin_rows(const SpDev G, JT *__restrict__ pj) {
 // heavy vertices' H / b partials per phase-1 block (owned ARAP edges: lower 6x6 + 6; depth: 1 + 1);
 // one workgroup per group of blocks (G.glb: consecutive owned ARAP blocks of one pair, their edges
 // contiguous) — the group's sums land in its first block's partial, its other blocks' are zero
-__global__ void __launch_bounds__(256) k_sp_glin_blocks(const SpDev G) {
-    __shared__ double red[kSpLin][4];
-    if (gated_off(G.lgate)) return;
-    const int2 gr = G.glb[blockIdx.x];
+// (b: the group; T: trips of the ARAP edge loop whose loads are in flight together)
+template <int T>
+__device__ __forceinline__ void glin_blocks(const SpDev &G, int b, double (*red)[4]) {
+    const int2 gr = G.glb[b];
     const int4 d = G.blk[gr.x];
     const int kind = d.x & 0xff, owned = d.x >> 8;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -301,17 +299,30 @@ __global__ void __launch_bounds__(256) k_sp_glin_blocks(const SpDev G) {
 #pragma unroll
         for (int k = 0; k < kSpLin; k++) a[k] = 0.0;
         const int iend = G.blk[gr.x + gr.y - 1].w;
-        for (int ii = i; ii < iend; ii += 256) {
-            double J[6];
+        // T trips' loads issued before the first is used (a trip past iend reloads the first and is
+        // skipped); each thread adds its edges in the same order as one trip at a time
+        for (int ii = i; ii < iend; ii += 256 * T) {
+            double Jb[T][6], wb[T], eb[T];
 #pragma unroll
-            for (int r = 0; r < 6; r++) J[r] = G.Ja[(12 + r) * G.jld + ii];
-            const double wv = G.Wa[ii], er = G.Ea[ii];
+            for (int u = 0; u < T; u++) {
+                const int iu = ii + 256 * u < iend ? ii + 256 * u : ii;
 #pragma unroll
-            for (int r = 0; r < 6; r++) {
-                const double jr = J[r] * wv;
+                for (int r = 0; r < 6; r++) Jb[u][r] = G.Ja[(12 + r) * G.jld + iu];
+                wb[u] = G.Wa[iu];
+                eb[u] = G.Ea[iu];
+            }
 #pragma unroll
-                for (int c = 0; c <= r; c++) a[tri6(r, c)] += jr * J[c];
-                a[21 + r] -= J[r] * (wv * er);
+            for (int u = 0; u < T; u++) {
+                if (ii + 256 * u >= iend) break;
+                const double *J = Jb[u];
+                const double wv = wb[u], er = eb[u];
+#pragma unroll
+                for (int r = 0; r < 6; r++) {
+                    const double jr = J[r] * wv;
+#pragma unroll
+                    for (int c = 0; c <= r; c++) a[tri6(r, c)] += jr * J[c];
+                    a[21 + r] -= J[r] * (wv * er);
+                }
             }
         }
         for (int k = threadIdx.x; k < kSpLin * (gr.y - 1); k += 256) out[kSpLin + k] = 0.0;
@@ -329,9 +340,9 @@ __global__ void __launch_bounds__(256) k_sp_glin_blocks(const SpDev G) {
         double h = 0.0, bs = 0.0;
         if (i < d.w) {
             const int le = G.dperm[i];
-            const double js = G.Jd[4 * (int64_t)le + 3];
-            h = G.wss[le];
-            bs = -js * (G.Wd[le] * G.Ed[le]);
+            const double js = G.Jd[4 * (int64_t)le + 3], wt = G.Wd[le];
+            h = (js * wt) * js;                        // = G.wss[le], which the row part stores in this launch
+            bs = -js * (wt * G.Ed[le]);
         }
         h = wave_sum(h);
         bs = wave_sum(bs);
@@ -342,6 +353,18 @@ __global__ void __launch_bounds__(256) k_sp_glin_blocks(const SpDev G) {
             out[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
         }
     }
+}
+
+// rows and block partials in one launch: the first row_grid(G.nrb2) workgroups take the rows (one
+// round of long, gather-bound waves), the G.nglb after them the block groups, which start as the
+// first row workgroups retire and run beside the rest.  The register cap is the row part's
+template <class JT, int GU>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GU == 4 ? 5 : GU == 6 ? 4 : 1, GU == 4 ? 5 : GU == 6 ? 4 : 3)))
+k_sp_glin(const SpDev G, JT *__restrict__ pj, int nrows) {
+    __shared__ double red[kSpLin][4];
+    if (gated_off(G.lgate)) return;
+    if ((int)blockIdx.x < nrows) glin_rows<JT, GU>(G, pj, red[0]);
+    else glin_blocks<GU == 8 ? 4 : 2>(G, blockIdx.x - nrows, red);
 }
 
 // heavy H / b (rank sums) in two levels: one workgroup per chunk of a heavy vertex's block partials
@@ -2222,17 +2245,18 @@ static void launch_phase2(const SpDev &G, int grid, int it, double lambda, const
 }
 
 void sp_launch_glin(const SpDev &G, bool fp32, hipStream_t st) {
+    // (the profile keeps the row pass's name for the launch that now holds the block partials too)
+    const int nrows = sp::row_grid(G.nrb2), grid = nrows + (G.nblk > 0 ? G.nglb : 0);
     if (G.glu == 4) {
-        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin_rows<float, 4>), sp::row_grid(G.nrb2), G, G.pj32);
-        else SPL("sp_glin_rows", (sp::k_sp_glin_rows<double, 4>), sp::row_grid(G.nrb2), G, G.pj);
+        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin<float, 4>), grid, G, G.pj32, nrows);
+        else SPL("sp_glin_rows", (sp::k_sp_glin<double, 4>), grid, G, G.pj, nrows);
     } else if (G.glu == 6) {
-        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin_rows<float, 6>), sp::row_grid(G.nrb2), G, G.pj32);
-        else SPL("sp_glin_rows", (sp::k_sp_glin_rows<double, 6>), sp::row_grid(G.nrb2), G, G.pj);
+        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin<float, 6>), grid, G, G.pj32, nrows);
+        else SPL("sp_glin_rows", (sp::k_sp_glin<double, 6>), grid, G, G.pj, nrows);
     } else {
-        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin_rows<float, 8>), sp::row_grid(G.nrb2), G, G.pj32);
-        else SPL("sp_glin_rows", (sp::k_sp_glin_rows<double, 8>), sp::row_grid(G.nrb2), G, G.pj);
+        if (fp32) SPL("sp_glin_rows", (sp::k_sp_glin<float, 8>), grid, G, G.pj32, nrows);
+        else SPL("sp_glin_rows", (sp::k_sp_glin<double, 8>), grid, G, G.pj, nrows);
     }
-    if (G.nblk > 0) SPL("sp_glin_blocks", sp::k_sp_glin_blocks, G.nglb, G);
     if (G.nch > 0) SPL("sp_glin_heavy", sp::k_sp_glin_heavy, G.nch, G);
 }
 

@@ -331,7 +331,7 @@ int SpSolver::upload(const deftri_problem_desc &d) {
     PUT(inc, H.inc); PUT(inco, H.inc_off); PUT(roff, H.rep_off); PUT(doff, H.dep_off);
     G.blk = reinterpret_cast<const int4 *>(blk);
     {
-        // k_sp_glin_blocks' groups: up to kSpGlinGroup consecutive owned ARAP blocks of one pair with
+        // k_sp_glin's block groups: up to kSpGlinGroup consecutive owned ARAP blocks of one pair with
         // contiguous edges per workgroup (its 27 sums reduced once per group, not per 256 edges); any
         // other block alone
         const int gmax = kSpGlinGroup;

@@ -298,6 +298,32 @@ def test_twice_on_one_context(ctxs):
     assert d1 == d2
 
 
+def test_both_layouts_share_one_tile_arena(ctxs):
+    """one-pair and multi-pair builds in turn on a fresh context with all five switches on: both layouts are cut by one
+    routine into one tile arena (a two-view graph of n correspondences has 2 n points: n = 257 and 65 here).
+    The arena holds 8 bytes per padded entry (E <= entries <= 2 E + 64 tiles), 4 per edge for the order and 12 per cross
+    slot (<= 2 E), and grows to 5/4 of what is asked.  It is allocated by the first build (two views of 257: 1,516
+    edges, at most 225 KB asked, so at most 281 KB held).  (64, 4) asks at most 350 KB, so it holds at most 437 KB
+    after it, grown or not.  Two views of 65 (366 edges) is the first graph's kind at a quarter of its size and runs in
+    an arena left by another layout.  (300, 8) asks at least 12 bytes per edge of about 50,000, over 600 KB: it grows
+    again.  A wrong capacity or a pointer into a freed arena shows as a digest that differs from the host's"""
+    host = ctxs[0]
+
+    def two_view(n):
+        m, _ = sim.simulate_two_view(n=n, seed=3, compact=True)
+        p = host.build_graph(m, 1.0, 2e5, np.float32(0.003))
+        assert p.n_points == 2 * n and p.n_pairs == 1
+        return p
+
+    with capi.Context(0) as dev:
+        for p, stages in ((two_view(257), 0x1fff), (graph_of(host, 64, 4), LAYOUT_STAGES), (two_view(65), 0x1fff),
+                          (graph_of(host, 300, 8), LAYOUT_STAGES)):
+            info, digests = compare(dev, p, layout=1, tile_builder=1)
+            assert triple(info) == (1, 0, stages), info
+            assert digests["tile_tab"] != FNV_BASIS
+            assert (digests["tile_trow"] != FNV_BASIS) == (p.n_pairs > 1)
+
+
 def test_upload_and_lm_solve_bit_for_bit(ctxs):
     """50,624 unknowns: the upload asks for the tile layout itself; pmap and pidx reach the solver on the device"""
     p = graph_of(ctxs[0], 2100, 8)

@@ -1,7 +1,8 @@
 // plan_dev.hip — the one-pair tile plan's sorts, scans and numberings on the device (plan_dev.h), and
 // its tile layout (build_tiles of one rank), its phase-1 blocks and its phase-2 wave layout (§5m); for
 // several pairs the keyframe-major rows, with the same edge stages and wave layout after them (§5o), and their tile
-// layout over (pair, group) units (build_tiles_multi, §5p).
+// layout over (pair, group) units (build_tiles_multi, §5p).  Both tile layouts are cut by cut_tiles(), over groups or
+// over units.
 //
 // No workgroup waits on another: a scan over more than one workgroup's elements is three launches (tile sums,
 // the scan of the sums by one workgroup, the tiles' own scans), a sort by a dense key (a row, a group) is count,
@@ -17,7 +18,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <type_traits>
 
 #include "dev_arena.h"
 #include "spcg.h"
@@ -1052,6 +1052,32 @@ size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 const bool g_timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
 
+void call_once(std::function<void()> *before_alloc) {
+    if (before_alloc && *before_alloc) {
+        (*before_alloc)();
+        *before_alloc = nullptr;
+    }
+}
+
+// a grow-only device arena: at least want_bytes, a quarter more when it grows; before_alloc is called (and cleared) first
+bool grow(char *&buf, size_t &cap, size_t want_bytes, std::function<void()> *before_alloc) {
+    if (want_bytes <= cap) return true;
+    call_once(before_alloc);
+    if (buf) hipFree(buf);
+    buf = nullptr; cap = 0;
+    const size_t bytes = want_bytes + want_bytes / 4;
+    if (hipMalloc((void **)&buf, bytes) != hipSuccess) return false;
+    cap = bytes;
+    return true;
+}
+
+// v = the n elements at base + offset of a download
+template <class V>
+void take(V &v, const char *base, size_t offset, size_t n) {
+    const typename V::value_type *p = (const typename V::value_type *)(base + offset);
+    v.assign(p, p + n);
+}
+
 }  // namespace
 
 #define LAUNCH(k, n, ...)                                                                            \
@@ -1073,18 +1099,9 @@ PlanDevice::~PlanDevice() {
 bool PlanDevice::reserve(size_t dev_bytes, size_t pin_bytes, std::function<void()> *before_alloc) {
     if (!ev_[0])
         for (hipEvent_t &e : ev_) if (hipEventCreate(&e) != hipSuccess) return false;
-    if ((dev_bytes > cap_ || pin_bytes > pin_cap_) && before_alloc && *before_alloc) {
-        (*before_alloc)();
-        *before_alloc = nullptr;
-    }
-    if (dev_bytes > cap_) {
-        if (buf_) hipFree(buf_);
-        buf_ = nullptr; cap_ = 0;
-        const size_t want = dev_bytes + dev_bytes / 4;
-        if (hipMalloc((void **)&buf_, want) != hipSuccess) return false;
-        cap_ = want;
-    }
+    if (!grow(buf_, cap_, dev_bytes, before_alloc)) return false;
     if (pin_bytes > pin_cap_) {
+        call_once(before_alloc);
         if (pin_) hipHostFree(pin_);
         pin_ = nullptr; pin_cap_ = 0;
         const size_t want = pin_bytes + pin_bytes / 4;
@@ -1092,6 +1109,21 @@ bool PlanDevice::reserve(size_t dev_bytes, size_t pin_bytes, std::function<void(
         pin_cap_ = want;
     }
     return true;
+}
+
+bool PlanDevice::sync(const char *what, std::string &err) {
+    hipError_t e = hipStreamSynchronize(st_);
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) return true;
+    err = std::string("plan builder (") + what + "): " + hipGetErrorString(e);
+    return false;
+}
+
+int PlanDevice::refuse(std::vector<int32_t> &gp, const char *what, std::string &err) {
+    hipMemcpyAsync(pin_, buf_ + L_.gp, 4 * (size_t)P_, hipMemcpyDeviceToHost, st_);
+    if (!sync(what, err)) return -1;
+    gp.assign((const int32_t *)pin_, (const int32_t *)pin_ + P_);
+    return 2;
 }
 
 // the exclusive scan of data [n] in place: reduce / scan of the tile sums / apply, or one launch for one tile
@@ -1146,17 +1178,14 @@ void PlanDevice::report(int first, int last, const char *const *names) const {
 
 int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before_alloc, int32_t &ng,
                      std::vector<int32_t> &point_of_row, std::vector<int32_t> &row_of_point, std::vector<int32_t> &gp,
-                     std::string &err, bool with_tiles, bool with_layout, bool multi, bool multi_tiles) {
+                     std::string &err, PlanBuilders on) {
     hipSetDevice(dev_);
-    multi_tiles = multi_tiles && multi;
-    if (multi && (with_tiles || d.n_cams >= (1 << 21))) {
+    on.multi_tiles = on.multi_tiles && on.multi;
+    if (on.multi && (on.tiles || d.n_cams >= (1 << 21))) {
         err = "plan builder: rows() of several pairs with the tile stages, or with 2^21 cameras";
         return -1;
     }
-    with_tiles_ = with_tiles;
-    with_layout_ = with_layout;
-    multi_ = multi;
-    multi_tiles_ = multi_tiles;
+    on_ = on;
     order_on_dev_ = false;
     nloc_ = -1;
     const int32_t P = d.n_points, NR = std::max(d.n_rot, 1);
@@ -1189,7 +1218,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         L.rep_ids = piece(4 * (size_t)R); L.rep_off = piece(4 * (Pz + 1)); L.dep_ids = piece(4 * (size_t)D);
         L.dep_off = piece(4 * (Pz + 1)); L.inc = piece(16 * Ez); L.inc_off = piece(8 * (Pz + 1));
         L.dl2_end = o;
-        if (with_tiles) {
+        if (on.tiles) {
             L.egi = piece(4 * Ez); L.egj = piece(4 * Ez); L.erow = piece(16 * Ez); L.ooff = piece(4 * (Pz + 1)); L.oe = piece(4 * Ez);
             L.okj = piece(4 * Ez); L.pred = piece(4 * Ez); L.tioff = piece(4 * (Pz + 1)); L.ie = piece(4 * Ez);
             L.tend = piece(4 * (Pz + 1)); L.ja = piece(4 * (Pz + 1)); L.jb = piece(4 * (Pz + 1)); L.mark = piece(4 * (Pz + 2));
@@ -1197,11 +1226,11 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
             L.tcut = piece(4 * (Pz + 2)); L.thdr = piece(4 * kHdrWords);
         }
         L.dl3 = L.dl3_end = o;
-        if (with_layout) {
+        if (on.layout) {
             // at most nbm blocks, ni wave starts (every 32 rows) and as many waves; several pairs: stage 8b alone,
             // so stage 7's pieces (D7 depth edges, nbm blocks, P7 block keys) are empty
-            const size_t ni = (Pz + 31) / 32, Dz = (size_t)D, D7 = multi ? 0 : Dz, P7 = multi ? 0 : Pz + 1;
-            const size_t nbm = multi ? 0 : Ez / kSpBlock + (size_t)D / kSpBlock + 4;
+            const size_t ni = (Pz + 31) / 32, Dz = (size_t)D, D7 = on.multi ? 0 : Dz, P7 = on.multi ? 0 : Pz + 1;
+            const size_t nbm = on.multi ? 0 : Ez / kSpBlock + (size_t)D / kSpBlock + 4;
             L.dscale = piece(4 * Dz); L.dflag = piece(4 * (D7 + 1)); L.bkey = piece(4 * nbm); L.boff = piece(4 * P7);
             L.bord = piece(4 * nbm); L.blk0 = piece(16 * nbm); L.order = piece(4 * Pz); L.scnt = piece(4 * Pz);
             L.wnext = piece(4 * (ni + 1)); L.wsteps = piece(4 * (ni + 1)); L.wsp = piece(4 * (ni + 1)); L.wja = piece(4 * (ni + 1));
@@ -1212,16 +1241,16 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
             L.dl3_end = o;
         }
         L.pxy = L.rcam = L.rfirst = L.pcam = L.cbox = o;
-        if (multi) {
+        if (on.multi) {
             // the points' own coordinates (with order_xy: beside it), the edges' cameras, per point its first edge and
             // its camera, per camera (and the bucket without one) its box
             L.pxy = piece(d.order_xy ? 24 * Pz : 0); L.rcam = piece(4 * (size_t)R); L.rfirst = piece(4 * Pz); L.pcam = piece(4 * Pz);
             L.cbox = piece(32 * ((size_t)std::max(d.n_cams, 1) + 1));
         }
         L.mpair = L.mdscale = o;
-        if (multi_tiles) {
+        if (on.multi_tiles) {
             L.mpair = piece(4 * Ez);
-            L.mdscale = with_layout ? L.dscale : piece(4 * (size_t)D);
+            L.mdscale = on.layout ? L.dscale : piece(4 * (size_t)D);
         }
         L.total = o;
     }
@@ -1244,18 +1273,18 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     const int *d_ng = d_hdr + kHdrNg;
 
     // one upload of the inputs
-    hipEventRecord(ev_[0], st_);
+    hipEventRecord(ev_[kEvRows], st_);
     hipMemcpyAsync(d_ap, d.arap_pts, 16 * Ez, hipMemcpyHostToDevice, st_);
     hipMemcpyAsync(B + L.rot, d.arap_rot, 8 * Ez, hipMemcpyHostToDevice, st_);
     if (R > 0) hipMemcpyAsync(B + L.rep_point, d.rep_point, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
     if (D > 0) hipMemcpyAsync(B + L.dep_point, d.dep_point, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
     hipMemcpyAsync(d_xy, xy, 8 * (size_t)stride * Pz, hipMemcpyHostToDevice, st_);
-    if (with_layout && D > 0) hipMemcpyAsync(B + L.dscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
-    if (multi && R > 0) hipMemcpyAsync(B + L.rcam, d.rep_cam, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
-    if (multi && d.order_xy) hipMemcpyAsync(B + L.pxy, d.points, 24 * Pz, hipMemcpyHostToDevice, st_);
-    if (multi_tiles) hipMemcpyAsync(B + L.mpair, d.arap_pair, 4 * Ez, hipMemcpyHostToDevice, st_);
-    if (multi_tiles && !with_layout && D > 0) hipMemcpyAsync(B + L.mdscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
-    hipEventRecord(ev_[1], st_);
+    if (on.layout && D > 0) hipMemcpyAsync(B + L.dscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
+    if (on.multi && R > 0) hipMemcpyAsync(B + L.rcam, d.rep_cam, 4 * (size_t)R, hipMemcpyHostToDevice, st_);
+    if (on.multi && d.order_xy) hipMemcpyAsync(B + L.pxy, d.points, 24 * Pz, hipMemcpyHostToDevice, st_);
+    if (on.multi_tiles) hipMemcpyAsync(B + L.mpair, d.arap_pair, 4 * Ez, hipMemcpyHostToDevice, st_);
+    if (on.multi_tiles && !on.layout && D > 0) hipMemcpyAsync(B + L.mdscale, d.dep_scale, 4 * (size_t)D, hipMemcpyHostToDevice, st_);
+    hipEventRecord(ev_[kEvRows + 1], st_);
     // 1. groups
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
     hipMemsetAsync(d_flag + P, 0, 4, st_);
@@ -1264,7 +1293,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     LAUNCH(k_uf_flatten, P, P, d_par, d_root, d_flag, d_hdr);
     scan(d_flag, (int64_t)P + 1);
     LAUNCH(k_groups, P, P, (const int *)d_root, (const int *)d_flag, d_gid, d_grep, d_hdr);
-    hipEventRecord(ev_[2], st_);
+    hipEventRecord(ev_[kEvRows + 2], st_);
     // 2. Morton order (ng stays on the device: the launches are sized by P, the kernels read ng)
     hipLaunchKernelGGL(dev::k_minmax_part, dim3(mm_grid), dim3(kBlk), 0, st_, d_ng, (const int *)d_grep, (const double *)d_xy, stride,
                        d_mm);
@@ -1272,12 +1301,12 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
     LAUNCH(k_keys, P, d_ng, (const int *)d_grep, (const double *)d_xy, stride, (const double *)d_lohi, d_key[0], d_id[0]);
     int cur = radix_sort(d_key, d_id, d_hist, nullptr, d_ng, rtile, kRadixPasses);
     LAUNCH(k_gpos, P, d_ng, (const int *)d_id[cur], d_gpos);
-    hipEventRecord(ev_[3], st_);
+    hipEventRecord(ev_[kEvRows + 3], st_);
     // 3. rows: the points by (gpos[gid[p]], p)
     LAUNCH(k_gp, P, P, (const int *)d_gid, (const int *)d_gpos, d_gp);
     int *d_start = d_flag;                                  // the groups' offsets (P + 1: keys past ng are empty)
     sort_by_row(P, d_gp, P, d_start, d_por, d_hdr);
-    if (multi) {
+    if (on.multi) {
         // several pairs: by (camera, curve key in the camera's box, point) instead, when every point has one camera.
         // The camera is the key's bits from 42 up: ceil(bits(C) / 7) more passes of the same sort
         const int C = std::max(d.n_cams, 1);
@@ -1297,19 +1326,14 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
         LAUNCH(k_rows_pick, P, P, (const int *)d_hdr, (const int *)d_id[cur], d_por);
     }
     LAUNCH(k_inverse, P, (int64_t)P, (const int *)d_por, d_rop);
-    hipEventRecord(ev_[4], st_);
+    hipEventRecord(ev_[kEvRows + 4], st_);
     // (gp is the region's last piece: the tile stages read it on the device, so it stays there)
-    hipMemcpyAsync(pin_, B + L.dl1, (with_tiles || multi_tiles ? L.gp : L.dl1_end) - L.dl1, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[5], st_);
-    hipError_t e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (rows): ") + hipGetErrorString(e);
-        return -1;
-    }
+    hipMemcpyAsync(pin_, B + L.dl1, (on.tiles || on.multi_tiles ? L.gp : L.dl1_end) - L.dl1, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[kEvRows + 5], st_);
+    if (!sync("rows", err)) return -1;
     static const char *const names[] = {"dev upload inputs", "dev 1 groups (union-find)", "dev 2 Morton order", "dev 3 rows",
                                         "dev download rows"};
-    report(0, 5, names);
+    report(kEvRows, kEvRows + 5, names);
     const int *hdr = (const int *)(pin_ + (L.hdr - L.dl1));
     if (hdr[kHdrBound]) return 1;
     ng = hdr[kHdrNg];
@@ -1321,7 +1345,7 @@ int PlanDevice::rows(const deftri_problem_desc &d, std::function<void()> *before
                   *gpp = (const int32_t *)(pin_ + (L.gp - L.dl1));
     point_of_row.assign(por, por + P);
     row_of_point.assign(rop, rop + P);
-    if (with_tiles || multi_tiles) gp.clear();
+    if (on.tiles || on.multi_tiles) gp.clear();
     else gp.assign(gpp, gpp + P);
     return 0;
 }
@@ -1348,10 +1372,10 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
     int64_t *d_inc_off = (int64_t *)(B + L.inc_off);
 
     nloc_ = -1;
-    hipEventRecord(ev_[6], st_);
+    hipEventRecord(ev_[kEvEdges], st_);
     if (order_on_dev_ && nloc == E) hipMemcpyAsync(d_aid, order_dev_, 4 * (size_t)nloc, hipMemcpyDeviceToDevice, st_);
     else hipMemcpyAsync(d_aid, H.arap_ids.data(), 4 * (size_t)nloc, hipMemcpyHostToDevice, st_);
-    hipEventRecord(ev_[7], st_);
+    hipEventRecord(ev_[kEvEdges + 1], st_);
     // 4. rotation rows numbered in first-encounter order over the positions 2 le + k
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
     hipMemsetAsync(d_rflag + npos, 0, 4, st_);
@@ -1361,31 +1385,25 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
     LAUNCH(k_rflag, npos, npos, (const int *)d_rv, (const int *)d_first, d_rflag);
     scan(d_rflag, npos + 1);
     LAUNCH(k_rot_write, npos, npos, (const int *)d_rv, (const int *)d_first, (const int *)d_rflag, d_rot_ids, d_arl, d_hdr);
-    hipEventRecord(ev_[8], st_);
+    hipEventRecord(ev_[kEvEdges + 2], st_);
     // 5. reprojection / depth edges by row
     LAUNCH(k_key_edge, R, R, (const int *)d_rep_point, (const int *)d_rop, d_kr);
     sort_by_row(R, d_kr, P, d_rep_off, d_rep_ids, d_hdr);
     LAUNCH(k_key_edge, D, D, (const int *)d_dep_point, (const int *)d_rop, d_kd);
     sort_by_row(D, d_kd, P, d_dep_off, d_dep_ids, d_hdr);
-    hipEventRecord(ev_[9], st_);
+    hipEventRecord(ev_[kEvEdges + 3], st_);
     // 6. incidences le << 2 | role by row
     LAUNCH(k_key_inc, n4, n4, (const int *)d_aid, (const int *)d_ap, (const int *)d_rop, d_ki);
     sort_by_row(n4, d_ki, P, d_ioff, d_inc, d_hdr);
     LAUNCH(k_widen, (int64_t)P + 1, (int64_t)P + 1, (const int *)d_ioff, d_inc_off);
-    hipEventRecord(ev_[10], st_);
+    hipEventRecord(ev_[kEvEdges + 4], st_);
     hipMemcpyAsync(pin_, B + L.dl2, L.dl2_end - L.dl2, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[11], st_);
-    hipError_t e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (edges): ") + hipGetErrorString(e);
-        return -1;
-    }
+    hipEventRecord(ev_[kEvEdges + 5], st_);
+    if (!sync("edges", err)) return -1;
     static const char *const names[] = {"dev upload arap_ids", "dev 5 rotation numbering", "dev 6 rep / depth by row",
                                         "dev 8 incidences", "dev download edges"};
-    report(6, 11, names);
-    auto at = [&](size_t off) { return pin_ + (off - L.dl2); };
-    const int *hdr = (const int *)at(L.hdr2);
+    report(kEvEdges, kEvEdges + 5, names);
+    const int *hdr = (const int *)(pin_ + (L.hdr2 - L.dl2));
     if (hdr[kHdrBound]) return 1;
     const int nrot = nloc > 0 ? hdr[kHdrNrot] : 0;
     if (nrot < 0 || nrot > std::min<int64_t>(NR, npos)) {
@@ -1393,21 +1411,182 @@ int PlanDevice::edges(const deftri_problem_desc &d, SpPlanHost &H, std::string &
         return -1;
     }
     const auto t0 = std::chrono::steady_clock::now();
-    auto take = [&](auto &v, size_t off, size_t n) {
-        using T = typename std::remove_reference<decltype(v)>::type::value_type;
-        const T *p = (const T *)at(off);
-        v.assign(p, p + n);
-    };
-    take(H.rot_ids, L.rot_ids, (size_t)nrot);
-    take(H.arap_rot_local, L.arl, (size_t)npos);
-    take(H.rep_ids, L.rep_ids, (size_t)R);
-    take(H.rep_off, L.rep_off, (size_t)P + 1);
-    take(H.dep_ids, L.dep_ids, (size_t)D);
-    take(H.dep_off, L.dep_off, (size_t)P + 1);
-    take(H.inc, L.inc, (size_t)n4);
-    take(H.inc_off, L.inc_off, (size_t)P + 1);
+    take(H.rot_ids, pin_, L.rot_ids - L.dl2, (size_t)nrot);
+    take(H.arap_rot_local, pin_, L.arl - L.dl2, (size_t)npos);
+    take(H.rep_ids, pin_, L.rep_ids - L.dl2, (size_t)R);
+    take(H.rep_off, pin_, L.rep_off - L.dl2, (size_t)P + 1);
+    take(H.dep_ids, pin_, L.dep_ids - L.dl2, (size_t)D);
+    take(H.dep_off, pin_, L.dep_off - L.dl2, (size_t)P + 1);
+    take(H.inc, pin_, L.inc - L.dl2, (size_t)n4);
+    take(H.inc_off, pin_, L.inc_off - L.dl2, (size_t)P + 1);
     nloc_ = nloc;
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> plan arrays", ms_since(t0));
+    return 0;
+}
+
+// cut_tiles(): its scratch on the device, over n nodes (groups, or units) and E edges
+struct PlanDevice::TileScratch {
+    int *hdr;                         // the stages' header: zeroed, then marked by the front end's kernels
+    const int *start;                 // [n + 1] the nodes' first rows
+    int *egi, *egj, *erow;            // per edge its two nodes and its four rows, written by the front end
+    int *ooff, *oe, *okj, *pred, *ioff, *ie, *tend, *ja, *jb, *mark, *midx, *tstart, *tne, *tnh, *tcut;
+    int *cur, *part;                  // the scratch of sort_by_row and scan (null: the arena's own pieces)
+    const int *gp, *por;              // one pair: a tile's rows are its groups' points (else null)
+    const int *urow, *upair;          // several pairs: the units' two rows and their pairs (else null)
+};
+
+// what a layout of several pairs adds to cut_tiles(): the depth edges' and the rows' checks and the tile row list's
+// entries by (row, entry) before the partition; the shares, the rows' share counts and the pairs' tile offsets after
+// the fill, four more arrays of the download
+struct PlanDevice::MultiExtras {
+    int32_t Q, ng;
+    int64_t D;
+    const int *dep_point, *dscale, *gp, *rop, *uid, *uidx;
+    int *soff, *sk, *spos;
+};
+
+int PlanDevice::cut_tiles(const TileScratch &s, const MultiExtras *mx, int32_t n, int units_max, int lds_budget,
+                          std::function<void()> *before_alloc, SpPlanHost &H, std::vector<int32_t> &order, std::vector<int32_t> &gp,
+                          std::string &err) {
+    const char *what = mx ? "tiles of several pairs" : "tiles";
+    const int32_t P = P_;
+    const int64_t E = E_, nodes = (int64_t)n + 1, n2 = mx ? 2 * (int64_t)n : 0;
+    const size_t Pz = (size_t)P, Ez = (size_t)E;
+    const dim3 tgrid((unsigned)std::min(n, kGridMax));
+    // a. the edges by node: the out-edges by (ni, e), the in-edges by (nj, e)
+    sort_by_row(E, s.egi, n, s.ooff, s.oe, s.hdr, s.cur, s.part);
+    LAUNCH(k_tile_deg, n, n, (const int *)s.ooff, s.hdr);
+    sort_by_row(E, s.egj, n, s.ioff, s.ie, s.hdr, s.cur, s.part);
+    LAUNCH(k_tile_pred, E, E, (const int *)s.oe, (const int *)s.egi, (const int *)s.egj, (const int *)s.ioff, (const int *)s.ie, s.okj,
+           s.pred, (const int *)s.hdr);
+    if (mx) {
+        LAUNCH(k_mu_depth, mx->D, mx->D, mx->dep_point, mx->dscale, mx->gp, mx->rop, mx->Q, mx->ng, mx->uid, s.urow, s.hdr);
+        sort_by_row(n2, s.urow, P, mx->soff, mx->sk, s.hdr, s.cur, s.part);
+        LAUNCH(k_inverse, n2, n2, (const int *)mx->sk, mx->spos);
+        LAUNCH(k_mu_rows, P, P, (const int *)mx->soff, s.hdr);
+    }
+    hipEventRecord(ev_[kEvCut + 1], st_);
+    // b. partition: the cut from every start (several pairs: a tile ends with its pair), the chain from node 0 marked
+    // by pointer doubling and compacted
+    LAUNCH(k_tile_end, nodes, n, s.start, (const int *)s.ooff, (const int *)s.okj, (const int *)s.pred, (const int *)s.ioff,
+           (const int *)s.ie, (const int *)s.egi, units_max, lds_budget, (int)kSpTileLdsFixed, s.tend, (const int *)s.hdr, s.upair);
+    hipMemsetAsync(s.mark, 0, 4 * ((size_t)n + 2), st_);
+    LAUNCH(k_fill, 1, (int64_t)1, s.mark, 1);
+    {
+        int rounds = 1;
+        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
+        const int *jin = s.tend;
+        int *jout = s.ja;
+        for (int r = 0; r < rounds; r++) {
+            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, s.mark, (const int *)s.hdr);
+            jin = jout;
+            jout = jout == s.ja ? s.jb : s.ja;
+        }
+    }
+    LAUNCH(k_tile_midx, nodes, n, (const int *)s.mark, s.midx);
+    scan(s.midx, nodes, s.part);
+    LAUNCH(k_tile_tstart, nodes, n, (const int *)s.mark, (const int *)s.midx, s.tstart, s.hdr);
+    hipEventRecord(ev_[kEvCut + 2], st_);
+    // c (counts). per tile its padded entries, halo rows and cut entries; their scans are the tiles' bases
+    hipMemsetAsync(s.tne, 0, 4 * ((size_t)n + 1), st_);
+    hipMemsetAsync(s.tnh, 0, 4 * ((size_t)n + 1), st_);
+    hipMemsetAsync(s.tcut, 0, 4 * ((size_t)n + 1), st_);
+    hipLaunchKernelGGL(dev::k_tile_count, tgrid, dim3(kBlk), 0, st_, (const int *)s.tstart, s.start, (const int *)s.ooff,
+                       (const int *)s.okj, (const int *)s.pred, (int)kSpTileLdsFixed, s.tne, s.tnh, s.tcut, s.hdr);
+    scan(s.tne, nodes, s.part);
+    scan(s.tnh, nodes, s.part);
+    scan(s.tcut, nodes, s.part);
+    hipLaunchKernelGGL(dev::k_tile_totals, dim3(1), dim3(64), 0, st_, n, (const int *)s.tne, (const int *)s.tnh, (const int *)s.tcut,
+                       s.hdr);
+    hipEventRecord(ev_[kEvCut + 3], st_);
+    hipMemcpyAsync(pin_, s.hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[kEvCut + 4], st_);
+    if (!sync(what, err)) return -1;
+    static const char *const names1[] = {"dev 4a groups, edges by group", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
+    static const char *const names1m[] = {"dev 4a edges by unit, shares", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
+    report(kEvCut, kEvCut + 4, mx ? names1m : names1);
+    int hdr[kHdrWords];
+    std::memcpy(hdr, pin_, sizeof(hdr));
+    // the host's builder refuses this graph (with its own reason): it runs there from these rows
+    if (hdr[kHdrRefuse]) return refuse(gp, what, err);
+    if (hdr[kHdrBound]) return 1;
+    const int32_t nt = hdr[kHdrNt], planes = mx ? hdr[kHdrPlanes] : 0;
+    const int64_t ne = hdr[kHdrEntries], nhr = hdr[kHdrHalo], nx = 2 * (int64_t)hdr[kHdrCut];
+    if (nt < 1 || nt > n || ne < 64 * (int64_t)nt || ne % 64 || ne > 2 * E + 64 * (int64_t)nt || nhr < 0 || nhr > 2 * E || nx < 0 ||
+        nx > 2 * E || (mx && (planes < 0 || planes >= mx->Q))) {
+        err = "plan builder: the device wrote impossible tile counts";
+        return -1;
+    }
+    // the tile arrays: one download region (header, tile arrays, the edge order, several pairs: their four arrays),
+    // then the cross slots' scratch
+    const size_t nrs = mx ? (size_t)n2 : Pz;                // tile_rs: per row, or the units' two rows
+    size_t o = 0;
+    auto piece = [&](size_t bytes) { const size_t at = o; o += pad(bytes); return at; };
+    const size_t o_hdr = piece(4 * kHdrWords), o_tab = piece(32 * (size_t)nt), o_m0 = piece(4 * (size_t)ne), o_m1 = piece(4 * (size_t)ne),
+                 o_chunk = piece(8 * (size_t)(ne / 64)), o_rs = piece(4 * nrs), o_halo = piece(4 * (size_t)nhr),
+                 o_xoff = piece(4 * (Pz + 1)), o_xdst = piece(4 * (size_t)nx), o_order = piece(4 * Ez), o_trow = piece(4 * (size_t)n2),
+                 o_tdst = piece(4 * (size_t)n2), o_poff = piece(mx ? 4 * ((size_t)mx->Q + 1) : 0), o_nshare = piece(mx ? 4 * Pz : 0);
+    const size_t dl = o;
+    const size_t o_xrow = piece(4 * (size_t)nx), o_xs = piece(4 * (size_t)nx);
+    if (!grow(tbuf_, tcap_, o, before_alloc) || !reserve(cap_, dl, before_alloc)) { err = "plan builder: allocation failed"; return -1; }
+    char *T = tbuf_;
+    int *d_hdr3 = (int *)(T + o_hdr), *d_xoff = (int *)(T + o_xoff), *d_xdst = (int *)(T + o_xdst), *d_xs = (int *)(T + o_xs);
+    dev::TileOut out;
+    out.tab = (int *)(T + o_tab); out.chunk = (int *)(T + o_chunk); out.rs = (int *)(T + o_rs); out.halo = (int *)(T + o_halo);
+    out.xrow = (int *)(T + o_xrow); out.m0 = (uint32_t *)(T + o_m0); out.m1 = (uint32_t *)(T + o_m1);
+    hipEventRecord(ev_[kEvFill], st_);
+    // c. entries and slots (several pairs: and own rows), one workgroup per tile; the shares from the sort by (row, entry)
+    hipMemsetAsync(d_hdr3, 0, 4 * kHdrWords, st_);
+    hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)s.tstart, s.start, s.gp,
+                       s.por, (const int *)s.ooff, (const int *)s.oe, (const int *)s.okj, (const int *)s.pred, (const int *)s.ioff,
+                       (const int *)s.ie, (const int *)s.egi, (const int4 *)s.erow, (const int *)s.tne, (const int *)s.tnh,
+                       (const int *)s.tcut, out, d_hdr3, (const int *)s.hdr, s.urow, s.upair);
+    if (mx) {
+        LAUNCH(k_mu_shares, n2, n2, s.urow, (const int *)mx->soff, (const int *)mx->spos, (int *)(T + o_trow), (int *)(T + o_tdst));
+        LAUNCH(k_mu_nshare, P, P, (const int *)mx->soff, (int *)(T + o_nshare));
+        LAUNCH(k_mu_poff, (int64_t)mx->Q + 1, mx->Q, mx->ng, mx->uidx, (const int *)s.midx, (int *)(T + o_poff));
+    }
+    hipEventRecord(ev_[kEvFill + 1], st_);
+    // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
+    sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3, s.cur, s.part);
+    LAUNCH(k_inverse, nx, nx, (const int *)d_xs, d_xdst);
+    hipMemcpyAsync(T + o_order, s.oe, 4 * Ez, hipMemcpyDeviceToDevice, st_);
+    hipEventRecord(ev_[kEvFill + 2], st_);
+    hipMemcpyAsync(pin_, T, dl, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[kEvFill + 3], st_);
+    if (!sync(what, err)) return -1;
+    static const char *const names2[] = {"dev 4a entries, slots", "dev 4a cross slots", "dev download tiles"};
+    static const char *const names2m[] = {"dev 4a entries, slots, shares", "dev 4a cross slots", "dev download tiles"};
+    report(kEvFill, kEvFill + 3, mx ? names2m : names2);
+    const int *hdr3 = (const int *)(pin_ + o_hdr);
+    if (hdr3[kHdrBound] || hdr3[kHdrRefuse]) return 1;
+    const auto t0 = std::chrono::steady_clock::now();
+    take(H.tile_tab, pin_, o_tab, 8 * (size_t)nt);
+    take(H.tile_m0, pin_, o_m0, (size_t)ne);
+    take(H.tile_m1, pin_, o_m1, (size_t)ne);
+    take(H.tile_chunk, pin_, o_chunk, 2 * (size_t)(ne / 64));
+    take(H.tile_rs, pin_, o_rs, nrs);
+    take(H.tile_halo, pin_, o_halo, (size_t)nhr);
+    take(H.tile_xoff, pin_, o_xoff, Pz + 1);
+    take(H.tile_xdst, pin_, o_xdst, (size_t)nx);
+    take(order, pin_, o_order, Ez);
+    if (mx) {
+        take(H.tile_trow, pin_, o_trow, (size_t)n2);
+        take(H.tile_tdst, pin_, o_tdst, (size_t)n2);
+        take(H.tile_poff, pin_, o_poff, (size_t)mx->Q + 1);
+        take(H.tile_nshare, pin_, o_nshare, Pz);
+        H.tile_planes = planes;
+        H.tile_multi = true;
+    }
+    H.ntile = nt;
+    H.tile_entries = ne;
+    H.tile_cross = nx;
+    H.tile_segmax = std::max(1, hdr[kHdrSegmax]);
+    H.tile_lds = hdr[kHdrLds];
+    H.tile_halo_rows = nhr;
+    order_on_dev_ = true;
+    order_dev_ = s.oe;
+    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
     return 0;
 }
 
@@ -1417,172 +1596,25 @@ int PlanDevice::tiles(const deftri_problem_desc &d, int32_t ng, int units_max, i
     const Layout &L = L_;
     const int32_t P = P_;
     const int64_t E = E_;
-    if (!buf_ || !with_tiles_ || P != d.n_points || E != d.n_arap || ng < 1 || ng > P) {
+    if (!buf_ || !on_.tiles || P != d.n_points || E != d.n_arap || ng < 1 || ng > P) {
         err = "plan builder: tiles() without the rows of this problem";
         return -1;
     }
     char *B = buf_;
-    const int *d_ap = (const int *)(B + L.ap), *d_start = (const int *)(B + L.flag), *d_gp = (const int *)(B + L.gp),
-              *d_rop = (const int *)(B + L.rop), *d_por = (const int *)(B + L.por);
-    int *d_egi = (int *)(B + L.egi), *d_egj = (int *)(B + L.egj), *d_erow = (int *)(B + L.erow), *d_ooff = (int *)(B + L.ooff),
-        *d_oe = (int *)(B + L.oe), *d_okj = (int *)(B + L.okj), *d_pred = (int *)(B + L.pred), *d_ioff = (int *)(B + L.tioff),
-        *d_ie = (int *)(B + L.ie), *d_tend = (int *)(B + L.tend), *d_ja = (int *)(B + L.ja), *d_jb = (int *)(B + L.jb),
-        *d_mark = (int *)(B + L.mark), *d_midx = (int *)(B + L.midx), *d_tstart = (int *)(B + L.tstart), *d_tne = (int *)(B + L.tne),
-        *d_tnh = (int *)(B + L.tnh), *d_tcut = (int *)(B + L.tcut), *d_hdr = (int *)(B + L.thdr);
-    const int64_t nodes = (int64_t)ng + 1;
-    const dim3 tgrid((unsigned)std::min(ng, kGridMax));
+    auto ip = [&](size_t off) { return (int *)(B + off); };
+    const int *d_ap = ip(L.ap), *d_rop = ip(L.rop);
+    TileScratch s{};
+    s.hdr = ip(L.thdr); s.start = ip(L.flag); s.egi = ip(L.egi); s.egj = ip(L.egj); s.erow = ip(L.erow); s.ooff = ip(L.ooff);
+    s.oe = ip(L.oe); s.okj = ip(L.okj); s.pred = ip(L.pred); s.ioff = ip(L.tioff); s.ie = ip(L.ie); s.tend = ip(L.tend); s.ja = ip(L.ja);
+    s.jb = ip(L.jb); s.mark = ip(L.mark); s.midx = ip(L.midx); s.tstart = ip(L.tstart); s.tne = ip(L.tne); s.tnh = ip(L.tnh);
+    s.tcut = ip(L.tcut); s.gp = ip(L.gp); s.por = ip(L.por);
 
-    hipEventRecord(ev_[12], st_);
-    // a. groups and edges by group: the out-edges by (gi, e), the in-edges by (gj, e)
-    hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
-    LAUNCH(k_tile_groups, ng, ng, d_start, d_hdr);
-    LAUNCH(k_tile_edges, E, E, (const int4 *)d_ap, d_gp, d_rop, d_egi, d_egj, (int4 *)d_erow, d_hdr);
-    sort_by_row(E, d_egi, ng, d_ooff, d_oe, d_hdr);
-    LAUNCH(k_tile_deg, ng, ng, (const int *)d_ooff, d_hdr);
-    sort_by_row(E, d_egj, ng, d_ioff, d_ie, d_hdr);
-    LAUNCH(k_tile_pred, E, E, (const int *)d_oe, (const int *)d_egi, (const int *)d_egj, (const int *)d_ioff, (const int *)d_ie, d_okj,
-           d_pred, (const int *)d_hdr);
-    hipEventRecord(ev_[13], st_);
-    // b. partition: the cut from every start, the chain from group 0 marked by pointer doubling and compacted
-    LAUNCH(k_tile_end, nodes, ng, d_start, (const int *)d_ooff, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
-           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr,
-           (const int *)nullptr);
-    hipMemsetAsync(d_mark, 0, 4 * ((size_t)ng + 2), st_);
-    LAUNCH(k_fill, 1, (int64_t)1, d_mark, 1);
-    {
-        int rounds = 1;
-        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
-        const int *jin = d_tend;
-        int *jout = d_ja;
-        for (int r = 0; r < rounds; r++) {
-            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, d_mark, (const int *)d_hdr);
-            jin = jout;
-            jout = jout == d_ja ? d_jb : d_ja;
-        }
-    }
-    LAUNCH(k_tile_midx, nodes, ng, (const int *)d_mark, d_midx);
-    scan(d_midx, nodes);
-    LAUNCH(k_tile_tstart, nodes, ng, (const int *)d_mark, (const int *)d_midx, d_tstart, d_hdr);
-    hipEventRecord(ev_[14], st_);
-    // c (counts). per tile its padded entries, halo rows and cut entries; their scans are the tiles' bases
-    hipMemsetAsync(d_tne, 0, 4 * ((size_t)ng + 1), st_);
-    hipMemsetAsync(d_tnh, 0, 4 * ((size_t)ng + 1), st_);
-    hipMemsetAsync(d_tcut, 0, 4 * ((size_t)ng + 1), st_);
-    hipLaunchKernelGGL(dev::k_tile_count, tgrid, dim3(kBlk), 0, st_, (const int *)d_tstart, d_start, (const int *)d_ooff,
-                       (const int *)d_okj, (const int *)d_pred, (int)kSpTileLdsFixed, d_tne, d_tnh, d_tcut, d_hdr);
-    scan(d_tne, nodes);
-    scan(d_tnh, nodes);
-    scan(d_tcut, nodes);
-    hipLaunchKernelGGL(dev::k_tile_totals, dim3(1), dim3(64), 0, st_, ng, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut,
-                       d_hdr);
-    hipEventRecord(ev_[15], st_);
-    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[16], st_);
-    hipError_t e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
-        return -1;
-    }
-    static const char *const names1[] = {"dev 4a groups, edges by group", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
-    report(12, 16, names1);
-    int hdr[kHdrWords];
-    std::memcpy(hdr, pin_, sizeof(hdr));
-    if (hdr[kHdrRefuse]) {
-        // build_tiles refuses this graph (with its own reason): it runs on the host from these rows, and needs gp
-        hipMemcpyAsync(pin_, d_gp, 4 * (size_t)P, hipMemcpyDeviceToHost, st_);
-        e = hipStreamSynchronize(st_);
-        if (e != hipSuccess) {
-            err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
-            return -1;
-        }
-        gp.assign((const int32_t *)pin_, (const int32_t *)pin_ + P);
-        return 2;
-    }
-    if (hdr[kHdrBound]) return 1;
-    const int32_t nt = hdr[kHdrNt];
-    const int64_t ne = hdr[kHdrEntries], nhr = hdr[kHdrHalo], nx = 2 * (int64_t)hdr[kHdrCut];
-    if (nt < 1 || nt > ng || ne < 64 * (int64_t)nt || ne % 64 || ne > 2 * E + 64 * (int64_t)nt || nhr < 0 || nhr > 2 * E || nx < 0 ||
-        nx > 2 * E) {
-        err = "plan builder: the device wrote impossible tile counts";
-        return -1;
-    }
-    // the tile arrays: one download region (header, tile arrays, the edge order), then the cross slots' scratch
-    const size_t Pz = (size_t)P;
-    size_t o = 0;
-    auto piece = [&](size_t bytes) { const size_t at = o; o += pad(bytes); return at; };
-    const size_t o_hdr = piece(4 * kHdrWords), o_tab = piece(32 * (size_t)nt), o_m0 = piece(4 * (size_t)ne), o_m1 = piece(4 * (size_t)ne),
-                 o_chunk = piece(8 * (size_t)(ne / 64)), o_rs = piece(4 * Pz), o_halo = piece(4 * (size_t)nhr),
-                 o_xoff = piece(4 * (Pz + 1)), o_xdst = piece(4 * (size_t)nx), o_order = piece(4 * (size_t)E);
-    const size_t dl = o;
-    const size_t o_xrow = piece(4 * (size_t)nx), o_xs = piece(4 * (size_t)nx);
-    if ((o > tcap_ || dl > pin_cap_) && before_alloc && *before_alloc) {
-        (*before_alloc)();
-        *before_alloc = nullptr;
-    }
-    if (o > tcap_) {
-        if (tbuf_) hipFree(tbuf_);
-        tbuf_ = nullptr; tcap_ = 0;
-        const size_t want = o + o / 4;
-        if (hipMalloc((void **)&tbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
-        tcap_ = want;
-    }
-    if (!reserve(cap_, dl, nullptr)) { err = "plan builder: allocation failed"; return -1; }
-    char *T = tbuf_;
-    int *d_hdr3 = (int *)(T + o_hdr), *d_xoff = (int *)(T + o_xoff), *d_xdst = (int *)(T + o_xdst), *d_xs = (int *)(T + o_xs);
-    dev::TileOut out;
-    out.tab = (int *)(T + o_tab); out.chunk = (int *)(T + o_chunk); out.rs = (int *)(T + o_rs); out.halo = (int *)(T + o_halo);
-    out.xrow = (int *)(T + o_xrow); out.m0 = (uint32_t *)(T + o_m0); out.m1 = (uint32_t *)(T + o_m1);
-    hipEventRecord(ev_[17], st_);
-    // c. entries and slots, one workgroup per tile
-    hipMemsetAsync(d_hdr3, 0, 4 * kHdrWords, st_);
-    hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)d_tstart, d_start, d_gp,
-                       d_por, (const int *)d_ooff, (const int *)d_oe, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
-                       (const int *)d_ie, (const int *)d_egi, (const int4 *)d_erow, (const int *)d_tne, (const int *)d_tnh,
-                       (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr, (const int *)nullptr, (const int *)nullptr);
-    hipEventRecord(ev_[18], st_);
-    // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
-    sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3);
-    LAUNCH(k_inverse, nx, nx, (const int *)d_xs, d_xdst);
-    hipMemcpyAsync(T + o_order, d_oe, 4 * (size_t)E, hipMemcpyDeviceToDevice, st_);
-    hipEventRecord(ev_[19], st_);
-    hipMemcpyAsync(pin_, T, dl, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[20], st_);
-    e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (tiles): ") + hipGetErrorString(e);
-        return -1;
-    }
-    static const char *const names2[] = {"dev 4a entries, slots", "dev 4a cross slots", "dev download tiles"};
-    report(17, 20, names2);
-    const int *hdr3 = (const int *)(pin_ + o_hdr);
-    if (hdr3[kHdrBound] || hdr3[kHdrRefuse]) return 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto take = [&](auto &v, size_t off, size_t n) {
-        using V = typename std::remove_reference<decltype(v)>::type::value_type;
-        const V *p = (const V *)(pin_ + off);
-        v.assign(p, p + n);
-    };
-    take(H.tile_tab, o_tab, 8 * (size_t)nt);
-    take(H.tile_m0, o_m0, (size_t)ne);
-    take(H.tile_m1, o_m1, (size_t)ne);
-    take(H.tile_chunk, o_chunk, 2 * (size_t)(ne / 64));
-    take(H.tile_rs, o_rs, Pz);
-    take(H.tile_halo, o_halo, (size_t)nhr);
-    take(H.tile_xoff, o_xoff, Pz + 1);
-    take(H.tile_xdst, o_xdst, (size_t)nx);
-    take(order, o_order, (size_t)E);
-    H.ntile = nt;
-    H.tile_entries = ne;
-    H.tile_cross = nx;
-    H.tile_segmax = std::max(1, hdr[kHdrSegmax]);
-    H.tile_lds = hdr[kHdrLds];
-    H.tile_halo_rows = nhr;
-    order_on_dev_ = true;
-    order_dev_ = d_oe;
-    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
-    return 0;
+    hipEventRecord(ev_[kEvCut], st_);
+    // the groups' checks, and per edge its groups and rows
+    hipMemsetAsync(s.hdr, 0, 4 * kHdrWords, st_);
+    LAUNCH(k_tile_groups, ng, ng, s.start, s.hdr);
+    LAUNCH(k_tile_edges, E, E, (const int4 *)d_ap, s.gp, d_rop, s.egi, s.egj, (int4 *)s.erow, s.hdr);
+    return cut_tiles(s, nullptr, ng, units_max, lds_budget, before_alloc, H, order, gp, err);
 }
 
 int PlanDevice::tiles_multi(const deftri_problem_desc &d, int32_t ng, int units_max, int lds_budget, std::function<void()> *before_alloc,
@@ -1590,34 +1622,25 @@ int PlanDevice::tiles_multi(const deftri_problem_desc &d, int32_t ng, int units_
     hipSetDevice(dev_);
     const Layout &L = L_;
     const int32_t P = P_, Q = d.n_pairs;
-    const int64_t E = E_, D = d.n_depth;
-    if (!buf_ || !multi_tiles_ || P != d.n_points || E != d.n_arap || ng < 1 || ng > P || Q < 2 || E < 1) {
+    const int64_t E = E_;
+    const char *what = "tiles of several pairs";
+    if (!buf_ || !on_.multi_tiles || P != d.n_points || E != d.n_arap || ng < 1 || ng > P || Q < 2 || E < 1) {
         err = "plan builder: tiles_multi() without the rows of this problem";
         return -1;
     }
     char *B = buf_;
     const int *d_ap = (const int *)(B + L.ap), *d_gp = (const int *)(B + L.gp), *d_rop = (const int *)(B + L.rop),
-              *d_pair = (const int *)(B + L.mpair), *d_dscale = (const int *)(B + L.mdscale), *d_dep_point = (const int *)(B + L.dep_point);
+              *d_pair = (const int *)(B + L.mpair);
     const double *d_pts = d.order_xy ? (const double *)(B + L.pxy) : (const double *)(B + L.xy);
-    hipError_t e = hipSuccess;
-    // build_tiles_multi refuses this graph, or a count leaves the int range: it runs on the host from these rows, and needs gp
-    auto to_host = [&]() {
-        hipMemcpyAsync(pin_, d_gp, 4 * (size_t)P, hipMemcpyDeviceToHost, st_);
-        e = hipStreamSynchronize(st_);
-        if (e != hipSuccess) {
-            err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
-            return -1;
-        }
-        gp.assign((const int32_t *)pin_, (const int32_t *)pin_ + P);
-        return 2;
-    };
     // the int ranges: a unit's flat index q ng + g, a unit id shifted by 2 bits, the padded entries <= 2 E + 64 tiles
+    // (outside them build_tiles_multi runs on the host from these rows)
     const int64_t nU64 = (int64_t)Q * ng, nmax64 = std::min<int64_t>(nU64, 2 * E);
-    if (d.n_scales != 2 * Q || nU64 >= (1LL << 28) || 2 * E + 64 * nmax64 >= (1LL << 31)) return to_host();
+    if (d.n_scales != 2 * Q || nU64 >= (1LL << 28) || 2 * E + 64 * nmax64 >= (1LL << 31)) return refuse(gp, what, err);
     const int nU = (int)nU64, nmax = (int)nmax64;             // nmax: the units at most (every edge end flags one)
     const size_t Ez = (size_t)E, Uz = (size_t)nU, Nz = (size_t)nmax, Pz = (size_t)P;
     const int rtile = (int)((Nz + kPlanRadixTile - 1) / kPlanRadixTile);
     const int64_t scan_max = std::max<int64_t>({(int64_t)nU + 1, (int64_t)kRadixDigits * rtile, (int64_t)P + 1});
+    // the scratch is an arena of its own, laid out here because it follows the group count
     size_t o = 0;
     auto piece = [&](size_t bytes) { const size_t at = o; o += pad(bytes); return at; };
     const size_t o_hdr = piece(4 * kHdrWords), o_uflag = piece(4 * Uz), o_uidx = piece(4 * (Uz + 1)), o_upt = piece(4 * Uz),
@@ -1630,224 +1653,62 @@ int PlanDevice::tiles_multi(const deftri_problem_desc &d, int32_t ng, int units_
                  o_ja = piece(4 * (Nz + 1)), o_jb = piece(4 * (Nz + 1)), o_mark = piece(4 * (Nz + 2)), o_midx = piece(4 * (Nz + 2)),
                  o_tstart = piece(4 * (Nz + 2)), o_tne = piece(4 * (Nz + 2)), o_tnh = piece(4 * (Nz + 2)), o_tcut = piece(4 * (Nz + 2)),
                  o_soff = piece(4 * (Pz + 1)), o_sk = piece(8 * Nz), o_spos = piece(8 * Nz);
-    if (o > mcap_) {
-        if (before_alloc && *before_alloc) {
-            (*before_alloc)();
-            *before_alloc = nullptr;
-        }
-        if (mbuf_) hipFree(mbuf_);
-        mbuf_ = nullptr; mcap_ = 0;
-        const size_t want = o + o / 4;
-        if (hipMalloc((void **)&mbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
-        mcap_ = want;
-    }
+    if (!grow(mbuf_, mcap_, o, before_alloc)) { err = "plan builder: allocation failed"; return -1; }
     if (g_timing) std::fprintf(stderr, "[deftri plan] arena of the units %.1f MiB of %.1f\n", o / 1048576.0, mcap_ / 1048576.0);
     char *M = mbuf_;
     auto ip = [&](size_t off) { return (int *)(M + off); };
-    int *d_hdr = ip(o_hdr), *d_uflag = ip(o_uflag), *d_uidx = ip(o_uidx), *d_upt = ip(o_upt), *d_upt2 = ip(o_upt2), *d_uid = ip(o_uid),
-        *d_hist = ip(o_hist), *d_part = ip(o_part), *d_cur = ip(o_cur), *d_urow = ip(o_urow), *d_upair = ip(o_upair),
-        *d_ustart = ip(o_ustart), *d_egi = ip(o_egi), *d_egj = ip(o_egj), *d_erow = ip(o_erow), *d_ooff = ip(o_ooff), *d_oe = ip(o_oe),
-        *d_okj = ip(o_okj), *d_pred = ip(o_pred), *d_ioff = ip(o_ioff), *d_ie = ip(o_ie), *d_tend = ip(o_tend), *d_ja = ip(o_ja),
-        *d_jb = ip(o_jb), *d_mark = ip(o_mark), *d_midx = ip(o_midx), *d_tstart = ip(o_tstart), *d_tne = ip(o_tne), *d_tnh = ip(o_tnh),
-        *d_tcut = ip(o_tcut), *d_soff = ip(o_soff), *d_sk = ip(o_sk), *d_spos = ip(o_spos);
+    int *d_uflag = ip(o_uflag), *d_uidx = ip(o_uidx), *d_upt = ip(o_upt), *d_upt2 = ip(o_upt2), *d_uid = ip(o_uid), *d_hist = ip(o_hist),
+        *d_urow = ip(o_urow), *d_upair = ip(o_upair), *d_ustart = ip(o_ustart);
     unsigned long long *d_box = (unsigned long long *)(M + o_box);
     uint64_t *d_key[2] = {(uint64_t *)(M + o_key0), (uint64_t *)(M + o_key1)};
     int *d_id[2] = {ip(o_id0), ip(o_id1)};
+    TileScratch s{};
+    s.hdr = ip(o_hdr); s.start = d_ustart; s.egi = ip(o_egi); s.egj = ip(o_egj); s.erow = ip(o_erow); s.ooff = ip(o_ooff); s.oe = ip(o_oe);
+    s.okj = ip(o_okj); s.pred = ip(o_pred); s.ioff = ip(o_ioff); s.ie = ip(o_ie); s.tend = ip(o_tend); s.ja = ip(o_ja); s.jb = ip(o_jb);
+    s.mark = ip(o_mark); s.midx = ip(o_midx); s.tstart = ip(o_tstart); s.tne = ip(o_tne); s.tnh = ip(o_tnh); s.tcut = ip(o_tcut);
+    s.cur = ip(o_cur); s.part = ip(o_part); s.urow = d_urow; s.upair = d_upair;
+    MultiExtras mx{};
+    mx.Q = Q; mx.ng = ng; mx.D = d.n_depth; mx.dep_point = (const int *)(B + L.dep_point); mx.dscale = (const int *)(B + L.mdscale);
+    mx.gp = d_gp; mx.rop = d_rop; mx.uid = d_uid; mx.uidx = d_uidx; mx.soff = ip(o_soff); mx.sk = ip(o_sk); mx.spos = ip(o_spos);
 
-    hipEventRecord(ev_[28], st_);
-    // a. the units: flags and points, the pairs' boxes, the keys, the sort by (q, key, g) from ascending (q, g)
-    hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
+    hipEventRecord(ev_[kEvUnits], st_);
+    // the units: flags and points, the pairs' boxes, the keys, the sort by (q, key, g) from ascending (q, g)
+    hipMemsetAsync(s.hdr, 0, 4 * kHdrWords, st_);
     hipMemsetAsync(d_uflag, 0, 4 * Uz, st_);
     LAUNCH(k_fill, nU, (int64_t)nU, d_upt, INT_MAX);
     LAUNCH(k_fill, nU, (int64_t)nU, d_upt2, INT_MAX);
     LAUNCH(k_fill, nU, (int64_t)nU, d_uid, -1);
-    LAUNCH(k_mu_flag, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, d_uflag, d_upt, d_upt2, d_hdr);
+    LAUNCH(k_mu_flag, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, d_uflag, d_upt, d_upt2, s.hdr);
     hipMemcpyAsync(d_uidx, d_uflag, 4 * Uz, hipMemcpyDeviceToDevice, st_);
     hipMemsetAsync(d_uidx + nU, 0, 4, st_);
-    scan(d_uidx, (int64_t)nU + 1, d_part);
+    scan(d_uidx, (int64_t)nU + 1, s.part);
     LAUNCH(k_box_init, 4 * Q, 4 * Q, d_box);
     LAUNCH(k_mu_box, nU, nU, ng, (const int *)d_uflag, (const int *)d_upt, d_pts, d_box);
     LAUNCH(k_mu_keys, nU, nU, ng, (const int *)d_uflag, (const int *)d_uidx, (const int *)d_upt, d_pts, (const unsigned long long *)d_box,
-           d_key[0], d_id[0], d_hdr);
+           d_key[0], d_id[0], s.hdr);
     int qbits = 0;
     while (Q >> qbits) qbits++;
-    const int cur = radix_sort(d_key, d_id, d_hist, d_part, d_hdr + kHdrNu, rtile, kRadixPasses + (qbits + kPlanRadixBits - 1) / kPlanRadixBits);
+    const int cur = radix_sort(d_key, d_id, d_hist, s.part, s.hdr + kHdrNu, rtile, kRadixPasses + (qbits + kPlanRadixBits - 1) / kPlanRadixBits);
     LAUNCH(k_mu_units, (int64_t)nmax + 2, nmax, ng, (const int *)d_id[cur], (const int *)d_upt, (const int *)d_upt2, d_rop, d_uid, d_urow,
-           d_upair, d_ustart, (const int *)d_hdr);
-    hipEventRecord(ev_[29], st_);
-    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[30], st_);
-    e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
-        return -1;
-    }
+           d_upair, d_ustart, (const int *)s.hdr);
+    hipEventRecord(ev_[kEvUnits + 1], st_);
+    hipMemcpyAsync(pin_, s.hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
+    hipEventRecord(ev_[kEvUnits + 2], st_);
+    if (!sync(what, err)) return -1;
     static const char *const names0[] = {"dev 4a units", "dev download unit count"};
-    report(28, 30, names0);
-    int hdr[kHdrWords];
-    std::memcpy(hdr, pin_, sizeof(hdr));
-    if (hdr[kHdrRefuse]) return to_host();
+    report(kEvUnits, kEvUnits + 2, names0);
+    const int *hdr = (const int *)pin_;
+    if (hdr[kHdrRefuse]) return refuse(gp, what, err);
     const int32_t nu = hdr[kHdrNu];
     if (nu < 2 || nu > nmax) {
         err = "plan builder: the device wrote an impossible unit count";
         return -1;
     }
-    const int64_t nodes = (int64_t)nu + 1, n2 = 2 * (int64_t)nu;
-    const dim3 tgrid((unsigned)std::min(nu, kGridMax));
-
-    hipEventRecord(ev_[31], st_);
-    // the edges by unit: the out-edges by (ui, e), the in-edges by (uj, e); the depth edges' and the rows' checks; the
-    // tile row list's entries by (row, entry) for the shares
-    LAUNCH(k_mu_edges, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, (const int *)d_uid, (const int *)d_upt, (const int *)d_upt2, d_egi,
-           d_egj, (int4 *)d_erow, d_hdr);
-    sort_by_row(E, d_egi, nu, d_ooff, d_oe, d_hdr, d_cur, d_part);
-    LAUNCH(k_tile_deg, nu, nu, (const int *)d_ooff, d_hdr);
-    sort_by_row(E, d_egj, nu, d_ioff, d_ie, d_hdr, d_cur, d_part);
-    LAUNCH(k_tile_pred, E, E, (const int *)d_oe, (const int *)d_egi, (const int *)d_egj, (const int *)d_ioff, (const int *)d_ie, d_okj,
-           d_pred, (const int *)d_hdr);
-    LAUNCH(k_mu_depth, D, D, d_dep_point, d_dscale, d_gp, d_rop, Q, ng, (const int *)d_uid, (const int *)d_urow, d_hdr);
-    sort_by_row(n2, d_urow, P, d_soff, d_sk, d_hdr, d_cur, d_part);
-    LAUNCH(k_inverse, n2, n2, (const int *)d_sk, d_spos);
-    LAUNCH(k_mu_rows, P, P, (const int *)d_soff, d_hdr);
-    hipEventRecord(ev_[32], st_);
-    // b. partition: the cut from every start (a tile ends with its pair), the chain from unit 0 marked and compacted
-    LAUNCH(k_tile_end, nodes, nu, (const int *)d_ustart, (const int *)d_ooff, (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff,
-           (const int *)d_ie, (const int *)d_egi, units_max, lds_budget, (int)kSpTileLdsFixed, d_tend, (const int *)d_hdr,
-           (const int *)d_upair);
-    hipMemsetAsync(d_mark, 0, 4 * ((size_t)nu + 2), st_);
-    LAUNCH(k_fill, 1, (int64_t)1, d_mark, 1);
-    {
-        int rounds = 1;
-        while (((int64_t)1 << (rounds - 1)) < nodes) rounds++;
-        const int *jin = d_tend;
-        int *jout = d_ja;
-        for (int r = 0; r < rounds; r++) {
-            LAUNCH(k_tile_jump, nodes, nodes, jin, jout, d_mark, (const int *)d_hdr);
-            jin = jout;
-            jout = jout == d_ja ? d_jb : d_ja;
-        }
-    }
-    LAUNCH(k_tile_midx, nodes, nu, (const int *)d_mark, d_midx);
-    scan(d_midx, nodes, d_part);
-    LAUNCH(k_tile_tstart, nodes, nu, (const int *)d_mark, (const int *)d_midx, d_tstart, d_hdr);
-    hipEventRecord(ev_[33], st_);
-    // c (counts). per tile its padded entries, halo rows and cut entries; their scans are the tiles' bases
-    hipMemsetAsync(d_tne, 0, 4 * ((size_t)nu + 1), st_);
-    hipMemsetAsync(d_tnh, 0, 4 * ((size_t)nu + 1), st_);
-    hipMemsetAsync(d_tcut, 0, 4 * ((size_t)nu + 1), st_);
-    hipLaunchKernelGGL(dev::k_tile_count, tgrid, dim3(kBlk), 0, st_, (const int *)d_tstart, (const int *)d_ustart, (const int *)d_ooff,
-                       (const int *)d_okj, (const int *)d_pred, (int)kSpTileLdsFixed, d_tne, d_tnh, d_tcut, d_hdr);
-    scan(d_tne, nodes, d_part);
-    scan(d_tnh, nodes, d_part);
-    scan(d_tcut, nodes, d_part);
-    hipLaunchKernelGGL(dev::k_tile_totals, dim3(1), dim3(64), 0, st_, nu, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut, d_hdr);
-    hipEventRecord(ev_[34], st_);
-    hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[35], st_);
-    e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
-        return -1;
-    }
-    static const char *const names1[] = {"dev 4a edges by unit, shares", "dev 4a partition", "dev 4a tile counts", "dev download counts"};
-    report(31, 35, names1);
-    std::memcpy(hdr, pin_, sizeof(hdr));
-    if (hdr[kHdrRefuse]) return to_host();
-    if (hdr[kHdrBound]) return 1;
-    const int32_t nt = hdr[kHdrNt], planes = hdr[kHdrPlanes];
-    const int64_t ne = hdr[kHdrEntries], nhr = hdr[kHdrHalo], nx = 2 * (int64_t)hdr[kHdrCut];
-    if (nt < 1 || nt > nu || ne < 64 * (int64_t)nt || ne % 64 || ne > 2 * E + 64 * (int64_t)nt || nhr < 0 || nhr > 2 * E || nx < 0 ||
-        nx > 2 * E || planes < 0 || planes >= Q) {
-        err = "plan builder: the device wrote impossible tile counts";
-        return -1;
-    }
-    // the tile arrays: one download region (header, tile arrays, the edge order), then the cross slots' scratch
-    o = 0;
-    const size_t t_hdr = piece(4 * kHdrWords), t_tab = piece(32 * (size_t)nt), t_m0 = piece(4 * (size_t)ne), t_m1 = piece(4 * (size_t)ne),
-                 t_chunk = piece(8 * (size_t)(ne / 64)), t_rs = piece(4 * (size_t)n2), t_halo = piece(4 * (size_t)nhr),
-                 t_xoff = piece(4 * (Pz + 1)), t_xdst = piece(4 * (size_t)nx), t_order = piece(4 * Ez), t_trow = piece(4 * (size_t)n2),
-                 t_tdst = piece(4 * (size_t)n2), t_poff = piece(4 * ((size_t)Q + 1)), t_nshare = piece(4 * Pz);
-    const size_t dl = o;
-    const size_t t_xrow = piece(4 * (size_t)nx), t_xs = piece(4 * (size_t)nx);
-    if ((o > tcap_ || dl > pin_cap_) && before_alloc && *before_alloc) {
-        (*before_alloc)();
-        *before_alloc = nullptr;
-    }
-    if (o > tcap_) {
-        if (tbuf_) hipFree(tbuf_);
-        tbuf_ = nullptr; tcap_ = 0;
-        const size_t want = o + o / 4;
-        if (hipMalloc((void **)&tbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
-        tcap_ = want;
-    }
-    if (!reserve(cap_, dl, nullptr)) { err = "plan builder: allocation failed"; return -1; }
-    char *T = tbuf_;
-    int *d_hdr3 = (int *)(T + t_hdr), *d_xoff = (int *)(T + t_xoff), *d_xdst = (int *)(T + t_xdst), *d_xs = (int *)(T + t_xs);
-    dev::TileOut out;
-    out.tab = (int *)(T + t_tab); out.chunk = (int *)(T + t_chunk); out.rs = (int *)(T + t_rs); out.halo = (int *)(T + t_halo);
-    out.xrow = (int *)(T + t_xrow); out.m0 = (uint32_t *)(T + t_m0); out.m1 = (uint32_t *)(T + t_m1);
-    hipEventRecord(ev_[36], st_);
-    // c. entries, slots and own rows, one workgroup per tile; the shares from the sort by (row, entry)
-    hipMemsetAsync(d_hdr3, 0, 4 * kHdrWords, st_);
-    hipLaunchKernelGGL(dev::k_tile_fill, dim3((unsigned)std::min(nt, kGridMax)), dim3(kBlk), 0, st_, (const int *)d_tstart,
-                       (const int *)d_ustart, (const int *)nullptr, (const int *)nullptr, (const int *)d_ooff, (const int *)d_oe,
-                       (const int *)d_okj, (const int *)d_pred, (const int *)d_ioff, (const int *)d_ie, (const int *)d_egi,
-                       (const int4 *)d_erow, (const int *)d_tne, (const int *)d_tnh, (const int *)d_tcut, out, d_hdr3, (const int *)d_hdr,
-                       (const int *)d_urow, (const int *)d_upair);
-    LAUNCH(k_mu_shares, n2, n2, (const int *)d_urow, (const int *)d_soff, (const int *)d_spos, (int *)(T + t_trow), (int *)(T + t_tdst));
-    LAUNCH(k_mu_nshare, P, P, (const int *)d_soff, (int *)(T + t_nshare));
-    LAUNCH(k_mu_poff, (int64_t)Q + 1, Q, ng, (const int *)d_uidx, (const int *)d_midx, (int *)(T + t_poff));
-    hipEventRecord(ev_[37], st_);
-    // d. cross slots by (target row, slot): a row's offsets, and every slot's place in that order
-    sort_by_row(nx, out.xrow, P, d_xoff, d_xs, d_hdr3, d_cur, d_part);
-    LAUNCH(k_inverse, nx, nx, (const int *)d_xs, d_xdst);
-    hipMemcpyAsync(T + t_order, d_oe, 4 * Ez, hipMemcpyDeviceToDevice, st_);
-    hipEventRecord(ev_[38], st_);
-    hipMemcpyAsync(pin_, T, dl, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[39], st_);
-    e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (tiles of several pairs): ") + hipGetErrorString(e);
-        return -1;
-    }
-    static const char *const names2[] = {"dev 4a entries, slots, shares", "dev 4a cross slots", "dev download tiles"};
-    report(36, 39, names2);
-    const int *hdr3 = (const int *)(pin_ + t_hdr);
-    if (hdr3[kHdrBound] || hdr3[kHdrRefuse]) return 1;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto take = [&](auto &v, size_t off, size_t n) {
-        using V = typename std::remove_reference<decltype(v)>::type::value_type;
-        const V *p = (const V *)(pin_ + off);
-        v.assign(p, p + n);
-    };
-    take(H.tile_tab, t_tab, 8 * (size_t)nt);
-    take(H.tile_m0, t_m0, (size_t)ne);
-    take(H.tile_m1, t_m1, (size_t)ne);
-    take(H.tile_chunk, t_chunk, 2 * (size_t)(ne / 64));
-    take(H.tile_rs, t_rs, (size_t)n2);
-    take(H.tile_halo, t_halo, (size_t)nhr);
-    take(H.tile_xoff, t_xoff, Pz + 1);
-    take(H.tile_xdst, t_xdst, (size_t)nx);
-    take(order, t_order, Ez);
-    take(H.tile_trow, t_trow, (size_t)n2);
-    take(H.tile_tdst, t_tdst, (size_t)n2);
-    take(H.tile_poff, t_poff, (size_t)Q + 1);
-    take(H.tile_nshare, t_nshare, Pz);
-    H.tile_planes = planes;
-    H.tile_multi = true;
-    H.ntile = nt;
-    H.tile_entries = ne;
-    H.tile_cross = nx;
-    H.tile_segmax = std::max(1, hdr[kHdrSegmax]);
-    H.tile_lds = hdr[kHdrLds];
-    H.tile_halo_rows = nhr;
-    order_on_dev_ = true;
-    order_dev_ = d_oe;
-    if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> tile arrays", ms_since(t0));
-    return 0;
+    hipEventRecord(ev_[kEvCut], st_);
+    // per edge its units and rows
+    LAUNCH(k_mu_edges, E, E, (const int4 *)d_ap, d_pair, d_gp, Q, ng, (const int *)d_uid, (const int *)d_upt, (const int *)d_upt2, s.egi,
+           s.egj, (int4 *)s.erow, s.hdr);
+    return cut_tiles(s, &mx, nu, units_max, lds_budget, before_alloc, H, order, gp, err);
 }
 
 int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *before_alloc, SpPlanHost &H, bool download_slots,
@@ -1858,13 +1719,13 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
     const int32_t P = P_, S = d.n_scales;
     const int64_t E = E_, D = d.n_depth, nloc = (int64_t)H.arap_ids.size();
     const int32_t nao = H.n_arap_owned;
-    if (!buf_ || !with_layout_ || nloc_ < 0 || nloc_ != nloc || P != d.n_points || E != d.n_arap ||
-        (multi_ ? d.n_pairs < 2 : d.n_pairs != 1 || S > 2) || S < 0 || nao < 0 || nao > nloc || (int64_t)H.dep_ids.size() != D || (D > 0 && S < 1) || H.lo != 0 || H.hi != P || P < 1) {
+    if (!buf_ || !on_.layout || nloc_ < 0 || nloc_ != nloc || P != d.n_points || E != d.n_arap ||
+        (on_.multi ? d.n_pairs < 2 : d.n_pairs != 1 || S > 2) || S < 0 || nao < 0 || nao > nloc || (int64_t)H.dep_ids.size() != D || (D > 0 && S < 1) || H.lo != 0 || H.hi != P || P < 1) {
         err = "plan builder: layout() without the edges of this problem";
         return -1;
     }
-    // several pairs (multi_): stage 7 is written for one pair and two scales, so it stays on the host
-    const bool dev7 = !multi_;
+    // several pairs (on_.multi): stage 7 is written for one pair and two scales, so it stays on the host
+    const bool dev7 = !on_.multi;
     int n0 = 0;                                           // depth edges of scale 0
     for (int64_t e = 0; dev7 && e < D; e++) n0 += d.dep_scale[e] == 0;
     auto blocks = [](int64_t n) { return (n + kSpBlock - 1) / kSpBlock; };
@@ -1887,7 +1748,7 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
     int4 *d_blk0 = (int4 *)(B + L.blk0), *d_blk = (int4 *)(B + L.blk);
     uint8_t *d_wsplit = (uint8_t *)(B + L.wsplit);
 
-    hipEventRecord(ev_[21], st_);
+    hipEventRecord(ev_[kEvLayout], st_);
     // 7. dperm, the blocks, their dispatch order, the heavy vertices' lists
     hipMemsetAsync(d_hdr, 0, 4 * kHdrWords, st_);
     hipMemsetAsync(d_hvoff, 0, 4 * 4, st_);
@@ -1901,7 +1762,7 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
         LAUNCH(k_blk_deal, nb, (int)nb, (const int *)d_bord, (const int4 *)d_blk0, d_blk);
         hipLaunchKernelGGL(dev::k_blk_heavy, dim3(1), dim3(1024), 0, st_, (int)nb, 1 + S, (const int4 *)d_blk, d_hvb, d_hvoff);
     }
-    hipEventRecord(ev_[22], st_);
+    hipEventRecord(ev_[kEvLayout + 1], st_);
     // 8b. the windows' rows by slot count, the wave cut from every multiple of 32, the chain from row 0
     if (waves) {
         const int64_t nodes = (int64_t)ni + 1;
@@ -1925,19 +1786,13 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
         LAUNCH(k_wave_write, 64 * (int64_t)ni, P, ni, (const int *)d_wmark, (const int *)d_widx, (const int *)d_wsoff, (const int *)d_wsp,
                (const int *)d_order, d_rowmap, d_woff, d_wsplit, d_hdr);
     }
-    hipEventRecord(ev_[23], st_);
+    hipEventRecord(ev_[kEvLayout + 2], st_);
     hipMemcpyAsync(pin_, B + L.dl3, (waves ? L.dl3_end : L.rowmap) - L.dl3, hipMemcpyDeviceToHost, st_);
-    hipEventRecord(ev_[24], st_);
-    hipError_t e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (layout): ") + hipGetErrorString(e);
-        return -1;
-    }
+    hipEventRecord(ev_[kEvLayout + 3], st_);
+    if (!sync("layout", err)) return -1;
     static const char *const names1[] = {"dev 7 phase-1 blocks", "dev 8b row sort, wave cut", "dev download layout"};
-    report(21, 24, names1);
-    auto at = [&](size_t off) { return pin_ + (off - L.dl3); };
-    const int *hdr = (const int *)at(L.lhdr), *hvoff = (const int *)at(L.hvoff);
+    report(kEvLayout, kEvLayout + 3, names1);
+    const int *hdr = (const int *)(pin_ + (L.lhdr - L.dl3)), *hvoff = (const int *)(pin_ + (L.hvoff - L.dl3));
     if (hdr[kHdrBound]) return 1;
     const int32_t nw = waves ? hdr[kLhNw] : 0;
     const int64_t nsl = waves ? hdr[kLhSlots] : 0;
@@ -1946,48 +1801,33 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
         return -1;
     }
     auto t0 = std::chrono::steady_clock::now();
-    auto take = [&](auto &v, size_t off, size_t n) {
-        using V = typename std::remove_reference<decltype(v)>::type::value_type;
-        const V *p = (const V *)at(off);
-        v.assign(p, p + n);
-    };
     if (dev7) {
-        take(H.dperm, L.dperm, (size_t)D);
-        take(H.blk, L.blk, 4 * (size_t)nb);
-        take(H.hv_blk, L.hvb, (size_t)hvoff[1 + S]);
+        take(H.dperm, pin_, L.dperm - L.dl3, (size_t)D);
+        take(H.blk, pin_, L.blk - L.dl3, 4 * (size_t)nb);
+        take(H.hv_blk, pin_, L.hvb - L.dl3, (size_t)hvoff[1 + S]);
         H.hv_blk_off.assign(hvoff, hvoff + 1 + S + 1);
         ran |= 1;
     }
     // (the host builds stage 8b when 64 x slots does not fit an int)
     if (!waves || 64 * nsl >= (1LL << 31)) return 0;
-    take(H.rowmap, L.rowmap, 64 * (size_t)nw);
-    take(H.wsplit, L.wsplit, (size_t)nw);
+    take(H.rowmap, pin_, L.rowmap - L.dl3, 64 * (size_t)nw);
+    take(H.wsplit, pin_, L.wsplit - L.dl3, (size_t)nw);
     {
-        const int *wo = (const int *)at(L.woff);
+        const int *wo = (const int *)(pin_ + (L.woff - L.dl3));
         H.woff.assign(wo, wo + nw + 1);
     }
     if (g_timing) std::fprintf(stderr, "[deftri plan] %-28s %8.2f ms\n", "dev staging -> layout arrays", ms_since(t0));
     // the slot arrays: pmap | pidx in a buffer of their own, kept for the solver's device-to-device copy
     const size_t nel = 64 * (size_t)nsl, half = pad(4 * nel), need = 2 * half;
-    if (need > scap_) {
-        if (before_alloc && *before_alloc) {
-            (*before_alloc)();
-            *before_alloc = nullptr;
-        }
-        if (sbuf_) hipFree(sbuf_);
-        sbuf_ = nullptr; scap_ = 0;
-        const size_t want = need + need / 4;
-        if (hipMalloc((void **)&sbuf_, want) != hipSuccess) { err = "plan builder: allocation failed"; return -1; }
-        scap_ = want;
-    }
+    if (!grow(sbuf_, scap_, need, before_alloc)) { err = "plan builder: allocation failed"; return -1; }
     int *d_pmap = (int *)sbuf_, *d_pidx = (int *)(sbuf_ + half);
-    hipEventRecord(ev_[25], st_);
+    hipEventRecord(ev_[kEvSlots], st_);
     if (nel > 0) {
         hipMemsetAsync(sbuf_, 0xff, need, st_);
         LAUNCH(k_slot_fill, 64 * (int64_t)nw, nw, (int)nsl, (const int *)d_rowmap, (const int *)d_woff, (const uint8_t *)d_wsplit, d_ioff,
                d_inc, d_dep_off, d_dep_ids, d_dscale, d_pmap, d_pidx, d_hdr);
     }
-    hipEventRecord(ev_[26], st_);
+    hipEventRecord(ev_[kEvSlots + 1], st_);
     hipMemcpyAsync(pin_, d_hdr, 4 * kHdrWords, hipMemcpyDeviceToHost, st_);
     if (download_slots && nel > 0) {
         H.pmap.resize(nel);
@@ -1995,15 +1835,10 @@ int PlanDevice::layout(const deftri_problem_desc &d, std::function<void()> *befo
         hipMemcpyAsync(H.pmap.data(), d_pmap, 4 * nel, hipMemcpyDeviceToHost, st_);
         hipMemcpyAsync(H.pidx.data(), d_pidx, 4 * nel, hipMemcpyDeviceToHost, st_);
     }
-    hipEventRecord(ev_[27], st_);
-    e = hipStreamSynchronize(st_);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) {
-        err = std::string("plan builder (layout): ") + hipGetErrorString(e);
-        return -1;
-    }
+    hipEventRecord(ev_[kEvSlots + 2], st_);
+    if (!sync("layout", err)) return -1;
     static const char *const names2[] = {"dev 8b slot fill", "dev download slots"};
-    report(25, 27, names2);
+    report(kEvSlots, kEvSlots + 2, names2);
     if (((const int *)pin_)[kHdrBound]) return 1;
     H.pmap_dev = nel > 0 ? d_pmap : nullptr;
     H.pidx_dev = nel > 0 ? d_pidx : nullptr;

@@ -204,8 +204,10 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // where they apply (one rank, one pair, at most two scales, ARAP edges, the tile layout requested, pd not null)
 // and the host passes elsewhere; info says what ran.  Returns 0, DEFTRI_E_ARG (err) when the problem cannot be
 // planned, DEFTRI_E_HIP (err) after a HIP error in the builder.  before_alloc (may be null): called and cleared
-// before the builder's arena grows.  tile_mode (deftri_set_tile_builder) 1: where mode 1 applies, build_tiles on
-// `pd` as well (PlanDevice::tiles; stages bits 6-9).  layout_mode (deftri_set_layout_builder) 1: where the device
+// before the builder's arena grows.  The five context switches that follow become one PlanBuilders value here, which
+// build_impl narrows to what the problem allows and hands to `pd`.
+// tile_mode (deftri_set_tile_builder) 1: where mode 1 applies, build_tiles on `pd` as well (PlanDevice::tiles; stages
+// bits 6-9).  layout_mode (deftri_set_layout_builder) 1: where the device
 // built the tile layout, stages 7 and 8b on `pd` too (PlanDevice::layout; stages bits 10-12); keep_slots then
 // leaves pmap and pidx on the device (out.pmap_dev, out.pidx_dev) — unless DEFTRI_PLAN_DIGEST asks for the digest.
 // multi_mode (deftri_set_multi_pair_builder) 1: mode 1 applies to several pairs on one rank as well (any number of
@@ -215,8 +217,7 @@ bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32
 // (PlanDevice::tiles_multi; stages bits 6-9)
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &out, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
-                       int tile_mode = 0, int layout_mode = 0, bool keep_slots = false, int multi_mode = 0,
-                       int multi_tile_mode = 0);
+                       int tile_mode, int layout_mode, bool keep_slots, int multi_mode, int multi_tile_mode);
 // FNV-1a digests of the plan: the combined digest DEFTRI_PLAN_DIGEST=1 prints (returned), and when `each` is
 // not null one digest per array in that block's order (names: kPlanDigestNames)
 uint64_t plan_digests(const SpPlanHost &H, std::vector<uint64_t> *each);

@@ -180,14 +180,14 @@ uint64_t plan_tile_digests(const SpPlanHost &H, std::vector<uint64_t> *each) {
 }
 
 // pd: the device builder for stages 1-3, 5, 6 and 8 (the caller has checked that they apply), else null;
-// stages: the bit mask of the stages it ran.  layout_dev (deftri_set_layout_builder): 1 stages 7 and 8b on pd too
-// where it built the tile layout, 2 the same with pmap and pidx left on the device (H.pmap_dev, H.pidx_dev).
-// Several pairs (deftri_set_multi_pair_builder; the caller has checked one rank and the tile request): pd numbers the
-// rows keyframe-major and layout_dev runs stage 8b alone; build_tiles_multi stays on the host unless
-// mtiles_dev (deftri_set_multi_tile_builder) asks pd for it first (PlanDevice::tiles_multi)
+// stages: the bit mask of the stages it ran.  on: the further builders the context's switches ask of pd, narrowed
+// below to what this problem allows.  on.layout: stages 7 and 8b on pd too where it built the tile layout, with
+// on.keep_slots pmap and pidx left on the device (H.pmap_dev, H.pidx_dev).  Several pairs (on.multi; the caller has
+// checked one rank and the tile request, and passes pd for them only with on.multi): pd numbers the rows keyframe-major
+// and on.layout runs stage 8b alone; build_tiles_multi stays on the host unless on.multi_tiles asks pd
+// for it first (PlanDevice::tiles_multi)
 static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
-                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, bool tiles_dev = false,
-                      int layout_dev = 0, bool mtiles_dev = false) {
+                      bool tile, PlanDevice *pd, std::function<void()> *before_alloc, int32_t *stages, PlanBuilders on) {
     static const bool timing = std::getenv("DEFTRI_PLAN_TIMING") != nullptr;
     static const bool digest = std::getenv("DEFTRI_PLAN_DIGEST") != nullptr;
     auto t_prev = std::chrono::steady_clock::now();
@@ -210,20 +210,22 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
 
     std::vector<int32_t> gid, gpos, gp_dev;   // group of each point; the groups' Morton positions; gpos[gid[p]]
     int32_t ng = 0;
-    const bool multi_dev = pd && Q > 1;
     if (pd) {
-        // stages 1-3 on the device (plan_dev.hip): the same groups, order and rows
+        // what of `on` this problem allows: the one place that decides it, for rows() and for the stages below
+        const bool tiles_fit = tile && E > 0 && sp_tile_lds_budget() < (1LL << 30);
+        on.multi = on.multi && Q > 1;
         // (the tile stages' int counts: padded entries <= 2 E + 64 ng, and a group id shifted by 2 bits)
-        tiles_dev = tiles_dev && tile && Q == 1 && S <= 2 && E > 0 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31) &&
-                    sp_tile_lds_budget() < (1LL << 30);
+        on.tiles = on.tiles && tiles_fit && Q == 1 && S <= 2 && P < (1 << 28) && 2 * E + 64 * (int64_t)P < (1LL << 31);
         // (several pairs: tiles_multi() checks its own int ranges once it knows the groups)
-        mtiles_dev = mtiles_dev && multi_dev && tile && E > 0 && sp_tile_lds_budget() < (1LL << 30);
-        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, tiles_dev,
-                                (tiles_dev || multi_dev) && layout_dev, multi_dev, mtiles_dev);
+        on.multi_tiles = on.multi_tiles && on.multi && tiles_fit;
+        on.layout = on.layout && (on.tiles || on.multi);
+        // stages 1-3 on the device (plan_dev.hip): the same groups, order and rows
+        const int rc = pd->rows(d, before_alloc, ng, H.point_of_row, H.row_of_point, gp_dev, err, on);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         *stages |= 7;
         stage("1-3 on the device (wall)");
     } else {
+        on = PlanBuilders();                     // no device: every stage below on the host
         // 1. keyframe-copy groups: union-find over the ARAP edges' (p1_i, p2_i) and (p1_j, p2_j)
         //    on host threads: a root is only ever linked under a smaller root (compare-and-swap), so every
         //    tree's root is its smallest point id and the partition and roots do not depend on the order
@@ -360,23 +362,26 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     stage("4 rank ranges");
     // 4a. tile mode (one rank, one pair; spcg_tile.cpp): the groups cut into tiles in Morton order,
     //     the ARAP edges in tile-entry order; the rows keep the Morton group order (no 4b sort: a
-    //     tile's rows are one contiguous range)
+    //     tile's rows are one contiguous range).  Several pairs on one rank: tiles per pair over
+    //     (pair, group) units
     std::vector<int32_t> tile_order, tile_foreign;
-    bool tiles_built_dev = false;                 // the device built the tile layout (not refused)
-    if (tile && Q == 1 && S <= 2 && E > 0) {
+    bool tiles_built_dev = false;                 // the device built the one-pair tile layout (not refused)
+    const bool one_pair = Q == 1 && S <= 2;
+    if (tile && E > 0 && (one_pair || (Q > 1 && nranks == 1))) {
         H.lo = H.rank_row_begin[rank];
         H.hi = H.rank_row_begin[rank + 1];
         std::vector<int32_t> gp;
         bool built = false;
-        if (pd && tiles_dev) {
-            // build_tiles on the device (plan_dev.hip); 2: a graph build_tiles refuses — the host's
-            // build_tiles below then says why, from the device's rows and groups
-            const int rc = pd->tiles(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err);
+        if (one_pair ? on.tiles : on.multi_tiles) {
+            // build_tiles / build_tiles_multi on the device (plan_dev.hip); 2: a graph it refuses —
+            // the host's builder below then says why, from the device's rows and groups
+            const int rc = one_pair ? pd->tiles(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err)
+                                    : pd->tiles_multi(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err);
             if (rc == 1 || rc < 0) return rc > 0 ? kPlanBound : kPlanHip;
             built = rc == 0;
             if (built) {
                 H.tile = true;
-                tiles_built_dev = true;
+                tiles_built_dev = one_pair;
                 *stages |= 0x3c0;
             }
         } else if (pd) gp.swap(gp_dev);
@@ -386,43 +391,16 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
         }
         TileInput ti;
         ti.P = P; ti.ng = ng; ti.E = E; ti.ap = ap; ti.gpos = gp.data(); ti.row_of_point = H.row_of_point.data();
+        if (Q > 1) {
+            ti.Q = Q; ti.S = S; ti.pair = d.arap_pair; ti.D = D; ti.dep_point = d.dep_point; ti.dep_scale = d.dep_scale;
+            ti.points = d.points;
+        }
         std::string why;
-        if (!built) H.tile = build_tiles(ti, H, tile_order, tile_foreign, why);
+        if (!built) H.tile = one_pair ? build_tiles(ti, H, tile_order, tile_foreign, why) : build_tiles_multi(ti, H, tile_order, why);
         if (!H.tile) {
             H.tile_why = why;
             tile_order.clear();
             tile_foreign.clear();
-        }
-    } else if (tile && Q > 1 && nranks == 1 && E > 0) {
-        // several pairs on one rank: tiles per pair over (pair, group) units (spcg_tile.cpp)
-        H.lo = H.rank_row_begin[rank];
-        H.hi = H.rank_row_begin[rank + 1];
-        std::vector<int32_t> gp;
-        bool built = false;
-        if (pd && mtiles_dev) {
-            // build_tiles_multi on the device (plan_dev.hip); 2: a graph it refuses — the host's below then
-            // says why, from the device's rows and groups
-            const int rc = pd->tiles_multi(d, ng, sp_tile_units(), (int)sp_tile_lds_budget(), before_alloc, H, tile_order, gp, err);
-            if (rc == 1 || rc < 0) return rc > 0 ? kPlanBound : kPlanHip;
-            built = rc == 0;
-            if (built) {
-                H.tile = true;
-                *stages |= 0x3c0;
-            }
-        } else if (pd) gp.swap(gp_dev);
-        else {
-            gp.resize(P);
-            for (int32_t p = 0; p < P; p++) gp[p] = gpos[gid[p]];
-        }
-        TileInput ti;
-        ti.P = P; ti.ng = ng; ti.E = E; ti.ap = ap; ti.gpos = gp.data(); ti.row_of_point = H.row_of_point.data();
-        ti.Q = Q; ti.S = S; ti.pair = d.arap_pair; ti.D = D; ti.dep_point = d.dep_point; ti.dep_scale = d.dep_scale;
-        ti.points = d.points;
-        std::string why;
-        if (!built) H.tile = build_tiles_multi(ti, H, tile_order, why);
-        if (!H.tile) {
-            H.tile_why = why;
-            tile_order.clear();
         }
     } else if (tile) {
         H.tile_why = Q != 1 ? "more than one keyframe pair on a sharded plan" : S > 2 ? "more than two depth scales" : "no ARAP edges";
@@ -593,9 +571,9 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
     // deftri_set_layout_builder: stages 7 and 8b on the device (plan_dev.hip) from the arrays edges()
     // left there; what it did not run (ran's bits clear) stays with the host code below
     bool dev7 = false, dev8b = false;
-    if (dev_edges && (tiles_built_dev || multi_dev) && layout_dev) {
+    if (dev_edges && (tiles_built_dev || on.multi) && on.layout) {
         int32_t ran = 0;
-        const int rc = pd->layout(d, before_alloc, H, layout_dev == 1 || digest, ran, err);
+        const int rc = pd->layout(d, before_alloc, H, !on.keep_slots || digest, ran, err);
         if (rc) return rc > 0 ? kPlanBound : kPlanHip;
         dev7 = (ran & 1) != 0;
         dev8b = (ran & 6) == 6;
@@ -841,12 +819,18 @@ static int build_impl(const deftri_problem_desc &d, int rank, int nranks, bool f
 
 bool build_sp_plan(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                    bool tile) {
-    return build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr) == kPlanOk;
+    return build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr, {}) == kPlanOk;
 }
 
 int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool fp32_jac, SpPlanHost &H, std::string &err,
                        bool tile, int mode, PlanDevice *pd, std::function<void()> *before_alloc, PlanBuildInfo &info,
                        int tile_mode, int layout_mode, bool keep_slots, int multi_mode, int multi_tile_mode) {
+    PlanBuilders on;
+    on.tiles = tile_mode == 1;
+    on.layout = layout_mode == 1;
+    on.keep_slots = on.layout && keep_slots;
+    on.multi = multi_mode == 1;
+    on.multi_tiles = on.multi && multi_tile_mode == 1;
     const auto t0 = std::chrono::steady_clock::now();
     info = PlanBuildInfo();
     auto done = [&](int rc) {
@@ -856,14 +840,13 @@ int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool 
     // the condition of stage 4a's one-pair tile branch, and a device; with deftri_set_multi_pair_builder that of its
     // multi-pair branch as well (the camera is the sort key's bits from 42 up: below 2^21 cameras)
     const bool one_pair = d.n_pairs == 1 && d.n_scales <= 2;
-    const bool multi_pair = multi_mode == 1 && d.n_pairs > 1 && d.n_cams < (1 << 21);
+    const bool multi_pair = on.multi && d.n_pairs > 1 && d.n_cams < (1 << 21);
     const bool applies = mode == 1 && pd && nranks == 1 && (one_pair || multi_pair) && d.n_arap > 0 &&
                          d.n_arap < (1LL << 29) && tile;
     if (mode == 1 && !applies) info.reason = 1;
     if (applies) {
         int32_t stages = 0;
-        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, tile_mode == 1,
-                                  layout_mode == 1 ? (keep_slots ? 2 : 1) : 0, multi_pair && multi_tile_mode == 1);
+        const int rc = build_impl(d, rank, nranks, fp32_jac, H, err, tile, pd, before_alloc, &stages, on);
         if (rc == kPlanOk) {
             info.builder_used = 1;
             info.stages = stages;
@@ -873,7 +856,7 @@ int build_sp_plan_with(const deftri_problem_desc &d, int rank, int nranks, bool 
         if (rc == kPlanBad) return done(DEFTRI_E_ARG);
         info.reason = 2;                               // a bounded loop reached its bound: the whole build on the host
     }
-    return done(build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr) == kPlanOk ? 0 : DEFTRI_E_ARG);
+    return done(build_impl(d, rank, nranks, fp32_jac, H, err, tile, nullptr, nullptr, nullptr, {}) == kPlanOk ? 0 : DEFTRI_E_ARG);
 }
 
 // Host emulation of one sharded product q = (H + lambda I) p on this rank's plan, with the device

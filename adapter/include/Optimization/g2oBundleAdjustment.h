@@ -3,7 +3,8 @@
 // argument is the reference's, so Modules/System (SLAM.cc:127,145) and Modules/Mapping call the
 // adapter exactly as they call g2oBundleAdjustment.cc today.  In the reference tree this file is
 // not needed: the reference's own header declares the same functions, and adapter/src/*.cc replaces
-// g2oBundleAdjustment.cc as their definition.  Only the Open3D include is absent: getInvUncertainty's
+// g2oBundleAdjustment.cc as their definition — arapOpen3DOptimization included, whose Open3D algorithm
+// the library restates.  Only the Open3D include is absent: getInvUncertainty's
 // mesh type is forward-declared (its single call site, g2oBundleAdjustment.cc:887, lies in the
 // replaced arapOptimization body, whose result it never used).
 #ifndef SLAM_G2OBUNDLEADJUSTMENT_H
@@ -42,7 +43,8 @@ void arapOptimization(Map *pMap, double repBalanceWeight, double globalBalanceWe
                       double alphaWeight, double betaWeight, float DepthError, int nOptIterations,
                       double *optimizationUpdate = nullptr);
 
-// Open3D's DeformAsRigidAsPossible (:1010-): out of scope, reports and leaves the map unchanged
+// Open3D's DeformAsRigidAsPossible on every keyframe pair's mesh (:1010-1104), restated in libdeftri.so
+// (deftri_arap_open3d_optimization): the MapPoints' positions are written back, nothing else
 void arapOpen3DOptimization(Map *pMap);
 
 double getInvUncertainty(std::shared_ptr<open3d::geometry::TriangleMesh> mesh, std::vector<Eigen::Vector3d> v1Positions,

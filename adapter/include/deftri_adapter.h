@@ -41,6 +41,8 @@ public:
     // arapOptimization's write-back (g2oBundleAdjustment.cc:967-1007): depth scales, fp32 positions of
     // every slot's MapPoint, and insertGlobalKeyFramesTransformation(0, 1, T_g)
     void write_back(Map *pMap);
+    // arapOpen3DOptimization's write-back (:1079-1082): the fp32 positions of every slot's MapPoint, nothing else
+    void write_back_positions();
 
 private:
     struct Arrays {

@@ -1,7 +1,7 @@
 // optimization_adapter.cc — definitions of the reference's ARAP entry points over the C-ABI:
 //   arapOptimization        g2oBundleAdjustment.cc:608-1008
 //   deformationOptimization g2oBundleAdjustment.cc:446-606 (+ outerObjective, nloptOptimization.cc:4-37)
-//   arapOpen3DOptimization  g2oBundleAdjustment.cc:1010- (Open3D; out of scope: reports, map unchanged)
+//   arapOpen3DOptimization  g2oBundleAdjustment.cc:1010-1104 (Open3D's DeformAsRigidAsPossible restated in libdeftri.so)
 //   calculatePixelsStandDev Modules/Utils/Geometry.cc:370-498
 // The Map is read through its public members only (KeyFrame / MapPoint getters, the observation
 // and global-transformation tables) and written back through the setters the reference uses.  The
@@ -199,17 +199,20 @@ MapView::MapView(Map *pMap) {
     }
 }
 
-void MapView::write_back(Map *pMap) {
+void MapView::write_back_positions() {
     for (size_t k = 0; k < order_.size(); k++) {
-        KeyFrame &kf = *order_[k];
-        kf.setEstimatedDepthScale(kfs_[k].depth_scale);                    // (:967-972)
-        std::vector<std::shared_ptr<MapPoint>> &slots = kf.getMapPoints();
+        std::vector<std::shared_ptr<MapPoint>> &slots = order_[k]->getMapPoints();
         for (size_t i = 0; i < slots.size(); i++) {
             if (!slots[i]) continue;
             Eigen::Vector3f p(arr_[k].pos[3 * i], arr_[k].pos[3 * i + 1], arr_[k].pos[3 * i + 2]);
-            slots[i]->setWorldPosition(p);                                 // (:978-990)
+            slots[i]->setWorldPosition(p);                                 // (:978-990, :1079-1082)
         }
     }
+}
+
+void MapView::write_back(Map *pMap) {
+    for (size_t k = 0; k < order_.size(); k++) order_[k]->setEstimatedDepthScale(kfs_[k].depth_scale);   // (:967-972)
+    write_back_positions();
     const Sophus::SE3f Tg = se3f_from7(m_.global_t);                      // (:999-1007)
     pMap->insertGlobalKeyFramesTransformation(0, 1, Tg);
 }
@@ -238,10 +241,15 @@ void arapOptimization(Map *pMap, double repBalanceWeight, double globalBalanceWe
 }
 
 void arapOpen3DOptimization(Map *pMap) {
-    (void)pMap;
-    std::cerr << "deftri: arapOpen3DOptimization (Open3D DeformAsRigidAsPossible) is not part of the device path; "
-                 "map unchanged"
-              << std::endl;
+    deftri_ctx *ctx = deftri_adapter::context();
+    if (!ctx) return;                                                      // map unchanged
+    MapView view(pMap);
+    const int rc = deftri_arap_open3d_optimization(ctx, view.map(), nullptr);
+    if (rc) {
+        std::cerr << "deftri: arapOpen3DOptimization: " << deftri_last_error(ctx) << " (error " << rc << ")" << std::endl;
+        return;                                                            // map unchanged
+    }
+    view.write_back_positions();                                          // the MapPoints alone (:1079-1082)
 }
 
 double getInvUncertainty(std::shared_ptr<open3d::geometry::TriangleMesh> mesh, std::vector<Eigen::Vector3d> v1Positions,

@@ -403,7 +403,8 @@ int deftri_profile_trial(deftri_ctx *ctx, double lambda, deftri_kernel_stat *sta
    10 deftri_deformation_eval, 11 deftri_depth_image, 12 deftri_real_abs_errors,
    14 deftri_feature_grid, 15 deftri_fast_params, 16 deftri_fast_report, 17 deftri_orb_params,
    18 deftri_orb_report, 20 deftri_projection_report, 22 deftri_essential_report,
-   23 deftri_triangulation_match_report (13, 19 and 21 are unassigned and answer -1, like every other
+   23 deftri_triangulation_match_report, 24 deftri_delaunay_report, 25 deftri_arap_deform_params,
+   26 deftri_arap_deform_report (13, 19 and 21 are unassigned and answer -1, like every other
    index). */
 int64_t deftri_sizeof(int32_t which);
 
@@ -1260,6 +1261,64 @@ int deftri_delaunay2d(deftri_ctx *ctx, int32_t n, const double *xy, int32_t tris
    memo nor the structure memo supplies the mesh: 0 (default) the host sweep, 1 deftri_delaunay2d's path on this
    context (the same triangles, so the same graph bit for bit).  deftri_graph_stats / _repairs keep their meaning. */
 int deftri_set_mesh_builder(deftri_ctx *ctx, int32_t mode);
+
+/* ---- as-rigid-as-possible mesh deformation (arap_deform.hip) ------------------------------
+   Open3D's TriangleMesh::DeformAsRigidAsPossible restated (the local/global iteration of Sorkine and Alexa;
+   not run against Open3D): the constraints C[cid[k]] = cpos[k] for k < min(n_cid, n_cpos) (a repeated id keeps
+   its last position); edge weights w_ij the mean over the edge's opposite vertices of a.b / |a x b|, clamped at
+   0; p = v, then max_iter times, always: the local step R_i = V diag(1, 1, det(V U^T)) U^T of S_i = sum_j w_ij
+   (v_i - v_j)(p_i - p_j)^T = U S V^T (Smoothed, from the second iteration on: S = 2 S + (4 alpha area / nb_i)
+   (sum_j R_old_j)^T), the global step L p = b with unit rows for the constrained vertices and b_i = sum_j
+   (w_ij / 2)(R_i + R_j)(v_i - v_j), and the energy E = sum_i sum_j w_ij |(p_i - p_j) - R_i (v_i - v_j)|^2
+   (Smoothed: + alpha area sum_i sum_j |R_i - R_j|_F^2), returned per iteration.
+   The global step eliminates the constrained rows and solves the symmetric positive definite rest by a
+   diagonally preconditioned CG over the three coordinate columns at once, from the previous iterate; a column
+   stops when r.r <= cg_tol^2 b.b, tested before the first iteration too.  A device context keeps every array on
+   the device for the whole call (one upload, one download; the host reads only the convergence flags); a
+   host-only context runs the same arithmetic in plain loops.  Every sum over vertices is taken in a fixed
+   order, so two calls with equal arguments give equal bits. */
+typedef struct deftri_arap_deform_params {   /* deftri_sizeof(25) */
+    int32_t max_iter;            /* Open3D default 50; the reference passes 500 */
+    int32_t energy;              /* 0 Spokes, 1 Smoothed */
+    double  smoothed_alpha;      /* 0.01 */
+    double  cg_tol;              /* relative residual per column; <= 0 means 1e-12 */
+    int32_t cg_max_iterations;   /* per global step; <= 0 means 10 n + 100 */
+    int32_t reserved;
+} deftri_arap_deform_params;
+
+typedef struct deftri_arap_deform_report {   /* deftri_sizeof(26) */
+    int32_t iterations, n_constraints, n_free, zero_weight_edges;
+    int32_t cg_max_in_step, cg_unconverged_steps, on_device, reserved;
+    int64_t cg_iterations;                   /* summed over steps and columns */
+    double  energy_first, energy_last, area;
+    double  ms_total, ms_local, ms_global;
+} deftri_arap_deform_report;
+
+/* DEFTRI_E_ARG: n < 3, a triangle or constraint index out of range, no effective constraint, max_iter < 0, an
+   energy other than 0 or 1, a null required pointer.  DEFTRI_E_GRAPH (before any solve): a connected component
+   of the positive-weight edges holds no constrained vertex (a vertex whose weights sum to 0 is such a
+   component) — Open3D's factorization fails there, and CG would return an arbitrary translation of it.
+   DEFTRI_E_NUMERIC: a non-finite iterate, det R <= 0, a global step that did not reach cg_tol within
+   cg_max_iterations (counted in cg_unconverged_steps; *rep is filled up to that step).  On every error out and
+   energies are untouched.  prm NULL: the defaults (50, Spokes, 0.01). */
+int deftri_arap_deform(deftri_ctx *ctx, int32_t n, const double *vertices /*[3n]*/,
+                       int32_t n_tris, const int32_t *tris /*[3 n_tris]*/,
+                       int32_t n_cid, const int32_t *cid, int32_t n_cpos, const double *cpos /*[3 n_cpos]*/,
+                       const deftri_arap_deform_params *prm,
+                       double *out /*[3n]*/, double *energies /*[max_iter] or NULL*/,
+                       deftri_arap_deform_report *rep);
+
+/* arapOpen3DOptimization(Map*) (g2oBundleAdjustment.cc:1010-1104): per keyframe pair in the order of
+   deftri_arap_optimization (keyframe 1 the later one), the Delaunay mesh of keyframe 1's positions (the mesh
+   builder switch applies), createVectorMap and its inverse, then deftri_arap_deform with the reference's
+   arguments — ten constraint ids 0, every position of keyframe 2 as constraint positions, 500 iterations,
+   Spokes — and the reference's write-back: for every slot index below keyframe 1's slot count that the
+   inverse map holds as a position index (the slot/compaction quirk, kept), keyframe 1's MapPoint of that slot
+   takes float(mesh vertex) and then keyframe 2's takes float(deformed vertex); a MapPoint is one object, so
+   each write reaches every slot with its id.  Pairs run in sequence on the updated positions.  DEFTRI_E_ARG: a
+   found slot that is empty or past the end in either keyframe (the reference dereferences it).  The map is
+   written only when every pair succeeded.  rep (may be NULL): the last pair's report. */
+int deftri_arap_open3d_optimization(deftri_ctx *ctx, deftri_map *map, deftri_arap_deform_report *rep);
 /* Who builds the iterative plan at the next deftri_problem_upload (and in the uploads inside
    deftri_arap_optimization / deftri_deformation_optimization): 0 (default) the host passes of
    csrc/spcg_plan.cpp; 1 the device stages of csrc/plan_dev.hip where they apply, the host passes elsewhere.

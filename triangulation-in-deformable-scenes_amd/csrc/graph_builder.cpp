@@ -263,6 +263,15 @@ bool mesh_adjacency(const std::vector<double> &pos, int n, std::vector<std::vect
     return true;
 }
 
+bool keyframe_mesh(const std::vector<double> &pos, int n, const MeshSource *mesh_src, std::vector<int32_t> &tris,
+                   std::vector<int32_t> &pos_index, std::string &err) {
+    Mesh M;
+    if (!build_mesh(pos, n, M, err, false, nullptr, mesh_src)) return false;
+    tris = std::move(M.tris);
+    pos_index = vector_map(pos, n);
+    return true;
+}
+
 void procrustes_rotation(const double S[9], double R[9]) { procrustes_rotation_hd(S, R); }
 
 namespace {

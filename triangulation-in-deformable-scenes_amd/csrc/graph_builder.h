@@ -162,6 +162,11 @@ void writeback_arap(deftri_map &map, const GraphResult &g, const std::vector<dou
 bool mesh_adjacency(const std::vector<double> &pos, int n, std::vector<std::vector<int32_t>> &adj,
                     std::vector<int32_t> &pos_index, double &area, std::string &err);
 
+// The mesh and the vector map that build_arap_graph makes for a keyframe 1 with these positions (the
+// triangles of mesh_src, or of the host sweep when it is null), for arapOpen3DOptimization (arap_deform_host.cpp)
+bool keyframe_mesh(const std::vector<double> &pos, int n, const MeshSource *mesh_src, std::vector<int32_t> &tris,
+                   std::vector<int32_t> &pos_index, std::string &err);
+
 // 3x3 helpers exported for tests
 void procrustes_rotation(const double S[9], double R[9]);
 

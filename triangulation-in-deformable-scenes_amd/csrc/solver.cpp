@@ -45,6 +45,7 @@
 #include "undistort.h"
 #include "delaunay.h"
 #include "delaunay_dev.h"
+#include "arap_deform.h"
 
 using namespace deftri;
 
@@ -1675,6 +1676,8 @@ int64_t deftri_sizeof(int32_t which) {
         case 22: return (int64_t)sizeof(deftri_essential_report);
         case 23: return (int64_t)sizeof(deftri_triangulation_match_report);
         case 24: return (int64_t)sizeof(deftri_delaunay_report);
+        case 25: return (int64_t)sizeof(deftri_arap_deform_params);
+        case 26: return (int64_t)sizeof(deftri_arap_deform_report);
         default: return -1;
     }
 }
@@ -2841,6 +2844,23 @@ int deftri_arap_optimization(deftri_ctx *ctx, deftri_map *map, double rep_weight
         std::fprintf(stderr, "[deftri call] graph %.1f ms, upload %.1f, LM %.1f, download + write-back %.1f, total %.1f\n", ms_graph,
                      ms_upload, ms_lm, ms_since(t3), ms_since(t0));
     return 0;
+}
+
+// ---- as-rigid-as-possible mesh deformation (arap_deform.h) ----
+int deftri_arap_deform(deftri_ctx *ctx, int32_t n, const double *vertices, int32_t n_tris, const int32_t *tris, int32_t n_cid,
+                       const int32_t *cid, int32_t n_cpos, const double *cpos, const deftri_arap_deform_params *prm, double *out,
+                       double *energies, deftri_arap_deform_report *rep) {
+    if (!ctx) return DEFTRI_E_ARG;
+    std::string err;
+    const int rc = arap::deform(ctx->device, ctx->st, n, vertices, n_tris, tris, n_cid, cid, n_cpos, cpos, prm, out, energies, rep, err);
+    return rc ? fail(ctx, rc, err) : 0;
+}
+
+int deftri_arap_open3d_optimization(deftri_ctx *ctx, deftri_map *map, deftri_arap_deform_report *rep) {
+    if (!ctx || !map) return DEFTRI_E_ARG;
+    std::string err;
+    const int rc = arap_open3d_map(ctx->device, ctx->st, *map, ctx->pair_window, mesh_source(ctx), rep, err);
+    return rc ? fail(ctx, rc, err) : 0;
 }
 
 }  // extern "C"

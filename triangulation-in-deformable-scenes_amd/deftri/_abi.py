@@ -245,6 +245,22 @@ class DelaunayReport(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ArapDeformParams(C.Structure):
+    _fields_ = [("max_iter", i32), ("energy", i32), ("smoothed_alpha", f64), ("cg_tol", f64), ("cg_max_iterations", i32),
+                ("reserved", i32)]
+
+
+class ArapDeformReport(C.Structure):
+    _fields_ = [("iterations", i32), ("n_constraints", i32), ("n_free", i32), ("zero_weight_edges", i32),
+                ("cg_max_in_step", i32), ("cg_unconverged_steps", i32), ("on_device", i32), ("reserved", i32),
+                ("cg_iterations", i64), ("energy_first", f64), ("energy_last", f64), ("area", f64), ("ms_total", f64),
+                ("ms_local", f64), ("ms_global", f64)]
+
+    def as_dict(self):
+        """The counters and energies; the times (ms_*) are measurements, not results."""
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 class PlanInfo(C.Structure):
     _fields_ = [("plan", i32), ("rank", i32), ("nranks", i32), ("own_rows", i32), ("halo_rows", i64),
                 ("local_arap_edges", i64), ("n_unknowns", i64), ("phase1_blocks", i32), ("row_blocks", i32),

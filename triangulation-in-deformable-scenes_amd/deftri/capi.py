@@ -93,6 +93,10 @@ def load():
                                                  P(_abi.FeatureGrid), P(C.c_int32), P(C.c_int32), P(C.c_uint8)]),
         "deftri_delaunay2d": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), P(_abi.DelaunayReport)]),
         "deftri_set_mesh_builder": (C.c_int, [C.c_void_p, C.c_int32]),
+        "deftri_arap_deform": (C.c_int, [C.c_void_p, C.c_int32, P(C.c_double), C.c_int32, P(C.c_int32), C.c_int32, P(C.c_int32),
+                                         C.c_int32, P(C.c_double), P(_abi.ArapDeformParams), P(C.c_double), P(C.c_double),
+                                         P(_abi.ArapDeformReport)]),
+        "deftri_arap_open3d_optimization": (C.c_int, [C.c_void_p, P(_abi.MapC), P(_abi.ArapDeformReport)]),
         "deftri_set_plan_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_tile_builder": (C.c_int, [C.c_void_p, C.c_int32]),
         "deftri_set_layout_builder": (C.c_int, [C.c_void_p, C.c_int32]),
@@ -251,6 +255,7 @@ EXPORTED = [
     "deftri_set_plan_builder", "deftri_plan_build_info", "deftri_debug_plan_digest", "deftri_set_tile_builder",
     "deftri_set_layout_builder", "deftri_debug_plan_layout_stats", "deftri_set_multi_pair_builder",
     "deftri_set_graph_builder", "deftri_graph_build_info", "deftri_set_multi_tile_builder", "deftri_debug_plan_tile_digest",
+    "deftri_arap_deform", "deftri_arap_open3d_optimization",
 ]
 
 # the digests of deftri_debug_plan_tile_digest, in its order
@@ -811,6 +816,52 @@ class Context:
         self._check(self.lib.deftri_delaunay2d(self.h, n, _dp(xy), cap, tris.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(rep)))
         return tris[:rep.n_tris].copy(), rep.as_dict()
 
+    def arap_deform(self, vertices, tris, constraint_ids, constraint_positions, max_iter=50, energy="spokes",
+                    smoothed_alpha=0.01, cg_tol=None, cg_max_iterations=None):
+        """As-rigid-as-possible deformation of the mesh (vertices [n, 3], tris [T, 3]) with the handles
+        constraint_ids -> constraint_positions (deftri_arap_deform: Open3D's DeformAsRigidAsPossible restated, the
+        global step by PCG on this context's device, or in host loops on a host-only context).  energy "spokes" or
+        "smoothed".  Returns (positions [n, 3], energies [max_iter], report dict).  A DeftriError raised by the call
+        carries the report filled so far as `.report`."""
+        v = np.ascontiguousarray(vertices, np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(tris, np.int32).reshape(-1, 3)
+        cid = np.ascontiguousarray(constraint_ids, np.int32).reshape(-1)
+        cpos = np.ascontiguousarray(constraint_positions, np.float64).reshape(-1, 3)
+        codes = {"spokes": 0, "smoothed": 1}
+        prm = _abi.ArapDeformParams()
+        prm.max_iter = int(max_iter)
+        prm.energy = codes[energy.lower()] if isinstance(energy, str) else int(energy)
+        prm.smoothed_alpha = float(smoothed_alpha)
+        prm.cg_tol = 0.0 if cg_tol is None else float(cg_tol)
+        prm.cg_max_iterations = 0 if cg_max_iterations is None else int(cg_max_iterations)
+        out = np.zeros_like(v)
+        en = np.zeros(max(int(max_iter), 0), np.float64)
+        rep = _abi.ArapDeformReport()
+        rc = self.lib.deftri_arap_deform(self.h, len(v), _dp(v), len(t), _ip(t), len(cid), _ip(cid), len(cpos), _dp(cpos),
+                                         C.byref(prm), _dp(out), _dp(en) if len(en) else None, C.byref(rep))
+        try:
+            self._check(rc)
+        except DeftriError as e:
+            e.report = rep.as_dict()
+            raise
+        return out, en, rep.as_dict()
+
+    def arap_open3d_optimization(self, m):
+        """arapOpen3DOptimization(Map*) (g2oBundleAdjustment.cc:1010-1104; deftri_arap_open3d_optimization): every
+        keyframe pair's mesh deformed by arap_deform with the reference's arguments, the map's positions written back
+        as fp32.  Returns the last pair's report dict.  On an error the map is unchanged."""
+        mc, keep = m.to_c()
+        rep = _abi.ArapDeformReport()
+        t = time.perf_counter()
+        rc = self.lib.deftri_arap_open3d_optimization(self.h, C.byref(mc), C.byref(rep))
+        self.last_call_s = time.perf_counter() - t
+        self._check(rc)
+        for kid, _pid, pos, *_rest in keep["arrays"]:      # positions only: this entry moves nothing else (:1079-1082)
+            for i, mp in enumerate(m.keyframes[kid].map_points):
+                if mp is not None:
+                    mp.position = pos[i].copy()
+        return rep.as_dict()
+
     def graph_repairs(self):
         """(keyframe meshes of full graph builds repaired from the previous build's triangulation, their
         flips) over this context's life."""
@@ -1274,7 +1325,15 @@ class Context:
         evaluation log."""
         settings.validate_for_solver()
         if settings.selection == "open3DArap":
-            raise NotImplementedError("open3DArap (Open3D DeformAsRigidAsPossible) is out of scope")
+            # optimizationUpdate is never written on this branch and stays 100: every round runs (:481-485)
+            n = max(int(settings.n_optimizations), 0)
+            t = time.perf_counter()
+            for _ in range(n):
+                self.arap_open3d_optimization(m)
+            return {"rounds": n, "arap_calls": 0, "weights": [float(settings.rep), float(settings.global_), float(settings.arap)],
+                    "minf": 0.0, "nlopt_result": 0, "update": 100.0, "seconds": time.perf_counter() - t, "evaluations": [],
+                    "round_update": [100.0] * min(n, 64),
+                    "round_weights": [[float(settings.rep), float(settings.global_), float(settings.arap)]] * min(n, 64)}
         prm = _abi.DeformationParams()
         # any other selection is the fixed-weight round (:565-568); "twoOptimizations" with a
         # weightsSelection other than "nlopt" too (the Eigen LM returns before evaluating, deftri.h)

@@ -46,6 +46,15 @@ def arapOptimization(pMap, repBalanceWeight, globalBalanceWeight, arapBalanceWei
     return upd
 
 
+def arapOpen3DOptimization(pMap, device=0, report=None):
+    """g2oBundleAdjustment.cc:1010-1104: every keyframe pair's Delaunay mesh deformed as rigidly as possible
+    (Open3D's DeformAsRigidAsPossible restated, deftri_arap_open3d_optimization) with the reference's arguments;
+    positions written back as fp32."""
+    rep = _ctx(device).arap_open3d_optimization(pMap)
+    if isinstance(report, dict):
+        report.update(rep)
+
+
 def outerObjective(x, pMap, settings, arap_fn=None, device=0):
     """nloptOptimization.cc:5-38: arapOptimization on a clone of the map with weights x = (rep,
     global, arap), then (log desvc1)^2 + (log desvc2)^2 of calculatePixelsStandDev."""
@@ -86,6 +95,19 @@ def deformationOptimization(pMap, settings, originalPoints=None, movedPoints=Non
     GPUs at once (the search and its result are those of the sequential run); both use the host loop."""
     from .nlopt_nm import nelder_mead
     settings.validate_for_solver()
+    if settings.selection == "open3DArap":
+        # optimizationUpdate is never written on this branch and stays 100, so every round runs (:481-485)
+        n = max(int(settings.n_optimizations), 0)
+        if native:
+            _ctx(device).deformation_optimization(pMap, settings)
+        else:
+            for _ in range(n):
+                arapOpen3DOptimization(pMap, device=device)
+        rounds = [{"round": i, "update": 100.0} for i in range(1, n + 1)]
+        if log:
+            for info in rounds:
+                log(info)
+        return rounds
     if native and arap_fn is None and workers is None:
         r = _ctx(device).deformation_optimization(pMap, settings)
         rounds = []
@@ -99,8 +121,6 @@ def deformationOptimization(pMap, settings, originalPoints=None, movedPoints=Non
             if log:
                 log(info)
         return rounds
-    if settings.selection == "open3DArap":
-        raise NotImplementedError("open3DArap is a different algorithm (Open3D DeformAsRigidAsPossible), out of scope")
     # weightsSelection other than "nlopt" (the Eigen LM, :531-564): Eigen::LevenbergMarquardt::minimize
     # returns ImproperInputParameters before any evaluation (the functor declares 2 values for the 3
     # weights, m < n, EigenOptimization.h:31), so the round is arapOptimization at the unchanged weights
